@@ -13,9 +13,15 @@ four margins > 0) into fixed-capacity records and one all_gather (RCCL over xGMI
 rank all objects' survivors (distributed.py).  Per-GPU work is fixed as N grows
 (weak scaling).
 
-  python bench.py [--gpus N --steps K --warmup W --E 4096 --n-inducing 2000]
+  python bench.py [--gpus N --steps K --warmup W --E 4096 --n-inducing 2000] [--dump-outputs DIR] [--full]
   N > 1: python -m torch.distributed.run --nproc-per-node N bench.py --gpus N ...
 Rank 0 prints one JSON line.
+
+A plain run sets up, warms up, times the K steps (and the exchange behind them), writes the last timed
+step's outputs if --dump-outputs is given, and prints the headline figures.  --full adds everything else
+the line has carried: the per-stage times and the three GEMM kernels' rooflines (HIP events in the timed
+steps and a pass of its own after them), the first / last steps' stream times, the repeated exchange, the
+screen's report, the config-4 blocks and the CPU baseline (--no-config4 / --no-cpu-baseline drop those two).
 """
 from __future__ import annotations
 
@@ -42,10 +48,17 @@ def parse():
     ap.add_argument("--E", type=int, default=4096, help="candidates per GPU")
     ap.add_argument("--n-inducing", type=int, default=2000)
     ap.add_argument("--hand", default="allegro")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also: stage times, rooflines, step stream times, repeated exchange, screen report, "
+                         "config 4, CPU baseline")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (what the closure's caller receives, and the "
+                         "exchange's survivor records) as DIR/<name>.npy; non-finite entries are written as 0 "
+                         "and marked in DIR/<name>_nonfinite.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
     ap.add_argument("--cpu-E", type=int, default=256)
     ap.add_argument("--backend", default="nccl", help="nccl (= RCCL, default) or gloo (rehearsal on one GPU)")
-    ap.add_argument("--no-config4", action="store_true", help="skip the config-4 SDF/Kin block (N = 1)")
+    ap.add_argument("--no-config4", action="store_true", help="(--full) skip the config-4 blocks (N = 1)")
     ap.add_argument("--config4-iters", type=int, default=1000)  # (the reference's Kin loop default: 1000 per call)
     return ap.parse_args()
 
@@ -341,6 +354,52 @@ def config4_closure(args, dev, gpis):
     return out
 
 
+DUMP_BYTES = 64 << 20  # --dump-outputs writes at most this much in all
+
+
+def last_outputs(opt, params, records):
+    """What the timed path's caller holds after the last timed step, as host arrays (float32 / float64): the
+    closure's per-candidate loss and margins, the gradients it left on the five parameters, its Kabsch reflection
+    flags, and the survivor records the exchange behind it returned."""
+    import numpy as np
+    names = ("grad_q", "grad_comp", "grad_target", "grad_palm_pos", "grad_palm_ori")
+    t = {"total_loss": opt.total_loss, "total_margin": opt.total_margin, "pregrasp_tip_pose": opt.pregrasp_tip_pose,
+         **{n: p.grad for n, p in zip(names, params)}, "kabsch_flip": opt.kabsch_flip, "survivor_records": records}
+    out = {}
+    for k, v in t.items():
+        a = v.detach().cpu().numpy()
+        out[k] = np.array(a if a.dtype in (np.float32, np.float64) else a.astype(np.float32))
+    return out
+
+
+def write_outputs(path, arrays):
+    """DIR/<name>.npy for each array; an array over its share of DUMP_BYTES is cut to a fixed, seeded sample of
+    its rows (in row order).  Every file holds finite numbers only: where an array has non-finite entries (the
+    closure's loss is NaN for a candidate with a non-positive contact margin, the reference's unclamped log,
+    optimize_pregrasp.py:708-709), <name>.npy has 0 there and DIR/<name>_nonfinite.npy, same shape and dtype, says
+    what stood there (1 NaN, 2 +inf, 3 -inf, else 0), so two builds still compare entry for entry.  Half of each
+    array's share is kept for that file.  Returns {name: shape written}."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_BYTES // (2 * len(arrays))
+    shapes = {}
+    for k, a in arrays.items():
+        if a.nbytes > share:
+            rows = max(1, share // (a.nbytes // a.shape[0]))
+            a = a[np.sort(np.random.default_rng(2024).choice(a.shape[0], rows, replace=False))]
+        bad, side = ~np.isfinite(a), os.path.join(path, k + "_nonfinite.npy")
+        if os.path.exists(side):
+            os.remove(side)  # (an earlier run's, in a reused DIR)
+        if bad.any():
+            code = np.where(np.isnan(a), 1, np.where(a > 0, 2, 3)) * bad
+            np.save(side, code.astype(a.dtype))
+            shapes[k + "_nonfinite"] = list(a.shape)
+            a = np.where(bad, 0, a).astype(a.dtype)
+        np.save(os.path.join(path, k + ".npy"), a)
+        shapes[k] = list(a.shape)
+    return shapes
+
+
 def main():
     args = parse()
     import numpy as np
@@ -402,8 +461,11 @@ def main():
     # clock the warm-up reached: the profiling event pool (cdx_profile_enable creates 49 152 events on
     # first use) and the exchange's first run (pack kernels, communicator setup, one host read), here on
     # the parameters with zero losses / margins (no survivors; the same buffer shapes).
-    N.check(lib.cdx_profile_enable((1 << N.PROF_STAGES) - 1), "cdx_profile_enable")
-    N.check(lib.cdx_profile_enable(0), "cdx_profile_enable")
+    # (the event pool only with --full: a plain run records no stage events)
+    full = args.full
+    if full:
+        N.check(lib.cdx_profile_enable((1 << N.PROF_STAGES) - 1), "cdx_profile_enable")
+        N.check(lib.cdx_profile_enable(0), "cdx_profile_enable")
     opt.total_loss = torch.zeros(E, dtype=torch.float64, device=dev)
     opt.total_margin = torch.zeros(E, ct.shape[1], dtype=torch.float64, device=dev)
     exchange()  # warms the pack kernels and the communicator (RCCL sets up its rings on first use)
@@ -414,7 +476,8 @@ def main():
     # (each record costs stream time: only the dominant kernel's — the exact-pass refine, whose roofline
     # is the headline — is marked in the timed steps; the screen and ∇std kernels in the pass after)
     PROF_TIMED = int(os.environ.get("CDX_BENCH_PROF_TIMED", str(1 << 2)))  # gpis_std_var (refine)
-    N.check(lib.cdx_profile_enable(PROF_TIMED), "cdx_profile_enable")
+    if full:
+        N.check(lib.cdx_profile_enable(PROF_TIMED), "cdx_profile_enable")
     torch.cuda.synchronize()
     if world > 1:
         dist.barrier()
@@ -422,8 +485,8 @@ def main():
     # per-step stream times of the first and last 5 timed steps (the clock ramp): events between those
     # steps on the closure's stream — each record costs ≈ 8 µs of stream time (profiles/r04b_ab_*: 1.058
     # vs 1.050 ms per step with one between every step), so only the 12 boundaries are marked
-    # (CDX_BENCH_STEP_EVENTS=0 drops them, =all marks every step)
-    mode = os.environ.get("CDX_BENCH_STEP_EVENTS", "1")
+    # (CDX_BENCH_STEP_EVENTS=0 drops them, =all marks every step; a plain run marks none)
+    mode = os.environ.get("CDX_BENCH_STEP_EVENTS", "1") if full else "0"
     K = args.steps
     marks = set() if mode == "0" else (set(range(K + 1)) if mode == "all" else
                                         set(range(min(6, K + 1))) | set(range(max(0, K - 5), K + 1)))
@@ -447,6 +510,43 @@ def main():
     if world > 1:
         dist.barrier()
     t1 = time.perf_counter()
+    # the last timed step's outputs, copied before any later pass overwrites them
+    dumped = last_outputs(opt, (qt, ct, tt, pp, po), records) if args.dump_outputs and rank == 0 else None
+    nan_candidates = int((~torch.isfinite(opt.total_loss)).sum())
+    elapsed, gather_s = t1 - t0, eg0.elapsed_time(eg1) * 1e-3
+    if world > 1:
+        t = torch.tensor([elapsed, gather_s], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed, gather_s = float(t[0]), float(t[1])
+    ms_per_step = 1e3 * elapsed / args.steps
+    value = E * world / (elapsed / args.steps)
+    n_ind = args.n_inducing
+    head = {
+        "metric": "candidate-grasp cost+grad evals/sec (GPIS+FK+SDF), 1/2/4/8 GPU",
+        "value": value, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        "dtype": "f64", "data": "synthetic", "full": full,
+        "config": {"workload": (f"config {'2' if world == 1 else '3'}: prob-mode closure fwd+bwd, "
+                                f"{E} candidates/GPU, {args.hand} FK (f32), 3 pregrasp levels; one object per GPU "
+                                f"({', '.join(CONFIG3[:world])}), each an N={n_ind} GPIS (in-repo fit recipe; "
+                                f"rank 0 = config 2's banana); ends with one all_gather of surviving grasps"),
+                   "candidates_per_gpu": E, "n_inducing": n_ind, "hand": args.hand,
+                   "parallelism": f"one object per GPU over {world} GPU(s), survivors all-gathered"},
+        "exchange": {"collective": "all_gather" if world > 1 else None,
+                     "backend": (args.backend if world > 1 else None), "ms": gather_s * 1e3,
+                     "bytes_per_rank": int(buf.numel() * 8), "records_gathered": n_records,
+                     "overflow": D.overflow(bufs)},
+        "native": N.build_info(),
+        "nan_candidates": nan_candidates,  # reference semantics: unclamped log in :708-709
+    }
+    if dumped is not None:
+        head["dumped_outputs"] = write_outputs(args.dump_outputs, dumped)
+    if not full:
+        if rank == 0:
+            print(json.dumps(head), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
     # informational: the same exchange repeated outside the timed region (median host wall time)
     reps = []
     for _ in range(int(os.environ.get("CDX_BENCH_EXCHANGE_REPEAT", "10"))):
@@ -472,23 +572,14 @@ def main():
     for i in range(N.PROF_STAGES):
         if not cnt[i]:
             ms[i], cnt[i] = ms_all[i], cnt_all[i]
-    elapsed, gather_s = t1 - t0, eg0.elapsed_time(eg1) * 1e-3
-    if world > 1:
-        t = torch.tensor([elapsed, gather_s], dtype=torch.float64, device=dev if args.backend == "nccl" else "cpu")
-        dist.all_reduce(t, op=dist.ReduceOp.MAX)
-        elapsed, gather_s = float(t[0]), float(t[1])
-    nan_candidates = int((~torch.isfinite(opt.total_loss)).sum())
 
     step_ms = [evs[i].elapsed_time(evs[i + 1]) for i in range(K) if i in evs and i + 1 in evs]
-    ms_per_step = 1e3 * elapsed / args.steps
-    value = E * world / (elapsed / args.steps)
     stage_names = ["queries", "gpis_mean", "gpis_std_var", "cost_bwd", "gpis_std_grad", "gpis_screen"]
     stage_ms = {n: (ms[i] / cnt[i] if cnt[i] else None) for i, n in enumerate(stage_names)}
     lq = opt.problem(gpis, 1).n_query_levels
     m_std, m_grad = lq * E * 4, lq * E
     scr = opt.screen_stats(gpis, E)  # rows of the exact fp64 pass (screened closure), None: all m_std
     m_exact = scr["exact_rows"] if scr else m_std
-    n_ind = args.n_inducing
     # algorithmic flops per launch (unpadded N): V = K*·L⁻ᵀ is triangular, N(N+1)/2 MACs per
     # query; W = V·L⁻¹ (= (E11⁻¹k)ᵀ) at the variance cost's argmax fingertip only, also triangular;
     # the screen runs the triangular product for every all-tip row as 3 fp16 slice products
@@ -509,20 +600,8 @@ def main():
 
     if rank == 0:
         out = {
-            "metric": "candidate-grasp cost+grad evals/sec (GPIS+FK+SDF), 1/2/4/8 GPU",
-            "value": value, "unit": "evals/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": ms_per_step, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            "dtype": "f64", "data": "synthetic",
-            "config": {"workload": (f"config {'2' if world == 1 else '3'}: prob-mode closure fwd+bwd, "
-                                    f"{E} candidates/GPU, {args.hand} FK (f32), 3 pregrasp levels; one object per GPU "
-                                    f"({', '.join(CONFIG3[:world])}), each an N={n_ind} GPIS (in-repo fit recipe; "
-                                    f"rank 0 = config 2's banana); ends with one all_gather of surviving grasps"),
-                       "candidates_per_gpu": E, "n_inducing": n_ind, "hand": args.hand,
-                       "parallelism": f"one object per GPU over {world} GPU(s), survivors all-gathered"},
-            "exchange": {"collective": "all_gather" if world > 1 else None,
-                         "backend": (args.backend if world > 1 else None), "ms": gather_s * 1e3,
-                         "bytes_per_rank": int(buf.numel() * 8), "records_gathered": n_records,
-                         "overflow": D.overflow(bufs),
+            **head,
+            "exchange": {**head["exchange"],
                          "ms_repeat_median": (1e3 * sorted(reps)[len(reps) // 2]) if reps else None,
                          "note": "pack (cdx_pack_survivors: per-tile counts + rows, two launches, device "
                                  "compaction, header counts on device) + the shape check (one all_reduce, N > 1) "
@@ -536,7 +615,6 @@ def main():
                          "steps_marked": len(step_ms), **({"all": step_ms} if mode == "all" else {}),
                          "note": "rank 0's stream time of the first and last 5 timed steps (HIP events between "
                                  "them): the clock ramp shows as first5_mean > last5_mean"} if step_ms else None),
-            "native": N.build_info(),
             "stage_ms": stage_ms,
             "stage_ms_note": "gpis_std_var (the refine kernel, the headline roofline): HIP events over "
                               "the timed steps; the other stages from a 10-step all-stage pass after the timed "
@@ -561,7 +639,6 @@ def main():
                               "flops_per_launch": flops_g,
                               "note": f"{m_grad} queries (the variance cost's argmax fingertip) x N(N+1), "
                                       f"from the whitened vectors the std pass keeps"},
-            "nan_candidates": nan_candidates,  # reference semantics: unclamped log in :708-709
         }
         if scr:
             out["roofline_screen"] = {

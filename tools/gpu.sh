@@ -5,7 +5,7 @@
 # call there.  Outputs under gpurun_out/ (scratch; summaries worth keeping go to profiles/).
 #   tests            pytest -m gpu (all GPU tests)          tests=EXPR   only -k EXPR
 #   smoke            __graft_entry__.smoke()
-#   bench            python bench.py (STEPS / WARMUP env, default 50 / 20)
+#   bench            python bench.py --full (STEPS / WARMUP env, default 50 / 20)
 #   trace            rocprofv3 --kernel-trace --stats over a short bench (prof_TAG/)
 #   pmc              HBM traffic: FETCH_SIZE and WRITE_SIZE, one rocprofv3 run each (pmc_*_TAG/)
 #   mfma             SQ_VALU_MFMA_BUSY_CYCLES & co. over a short bench (pmc_mfma_TAG/)
@@ -42,22 +42,22 @@ for STEP in "$@"; do
       timeout -k 10 180 python -c "import __graft_entry__ as g; g.smoke()" > "$OUT/smoke_$TAG.log" 2>&1
       rc=$?; echo "smoke rc=$rc"; tail -2 "$OUT/smoke_$TAG.log"; stop_if_fault $rc ;;
     bench)
-      timeout -k 10 300 python bench.py --steps "$STEPS" --warmup "$WARMUP" > "$OUT/bench_$TAG.log" 2>&1
+      timeout -k 10 300 python bench.py --full --steps "$STEPS" --warmup "$WARMUP" > "$OUT/bench_$TAG.log" 2>&1
       rc=$?; echo "bench rc=$rc"; tail -c 3000 "$OUT/bench_$TAG.log"; stop_if_fault $rc ;;
     trace)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d "$OUT/prof_$TAG" -o run -- \
-        python3 "$ROOT/bench.py" --steps 30 --warmup 20 --no-cpu-baseline --no-config4 > "$OUT/rocprof_$TAG.log" 2>&1
+        python3 "$ROOT/bench.py" --steps 30 --warmup 20 --full --no-cpu-baseline --no-config4 > "$OUT/rocprof_$TAG.log" 2>&1
       rc=$?; echo "rocprof rc=$rc"; tail -2 "$OUT/rocprof_$TAG.log"; stop_if_fault $rc ;;
     pmc)
       for C in FETCH_SIZE WRITE_SIZE; do
         timeout -k 10 -s KILL 300 rocprofv3 --pmc $C --output-format csv -d "$OUT/pmc_${C}_$TAG" -o run -- \
-          python3 "$ROOT/bench.py" --steps 3 --warmup 1 --no-cpu-baseline --no-config4 > "$OUT/pmc_${C}_$TAG.log" 2>&1
+          python3 "$ROOT/bench.py" --steps 3 --warmup 1 --full --no-cpu-baseline --no-config4 > "$OUT/pmc_${C}_$TAG.log" 2>&1
         rc=$?; echo "pmc $C rc=$rc"; stop_if_fault $rc
       done ;;
     mfma)
       timeout -k 10 -s KILL 200 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CU_CYCLES GRBM_GUI_ACTIVE SQ_INSTS_MFMA \
         SQ_WAVE_CYCLES --output-format csv -d "$OUT/pmc_mfma_$TAG" -o run -- \
-        python3 "$ROOT/bench.py" --steps 3 --warmup 2 --no-cpu-baseline --no-config4 > "$OUT/pmc_mfma_$TAG.log" 2>&1
+        python3 "$ROOT/bench.py" --steps 3 --warmup 2 --full --no-cpu-baseline --no-config4 > "$OUT/pmc_mfma_$TAG.log" 2>&1
       rc=$?; echo "pmc mfma rc=$rc"; stop_if_fault $rc ;;
     timeline)
       python3 tools/closure_timeline.py "$OUT/prof_$TAG/run_kernel_trace.csv" > "$OUT/closure_timeline_$TAG.txt" 2>&1
@@ -115,7 +115,7 @@ for STEP in "$@"; do
             if [ -n "$ENVS" ]; then for kv in ${ENVS//+/ }; do export "$kv"; done; fi
             if [ "$L" = base ]; then export CDX_LIB=$ROOT/compliancedex_amd/lib/libcdx.so
             else export CDX_LIB=$ROOT/compliancedex_amd/lib/libcdx_$L.so; fi
-            timeout -k 10 200 python3 "$ROOT/bench.py" --steps "$STEPS" --warmup "$WARMUP" --no-cpu-baseline --no-config4 \
+            timeout -k 10 200 python3 "$ROOT/bench.py" --steps "$STEPS" --warmup "$WARMUP" --full --no-cpu-baseline --no-config4 \
               > "$OUT/ab_run_$TAG.log" 2>&1
           )
           rc=$?; [ $rc -ne 0 ] && { echo "$SPEC rc=$rc"; tail -5 "$OUT/ab_run_$TAG.log"; exit $rc; }

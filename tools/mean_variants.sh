@@ -22,6 +22,6 @@ for r in 1 2; do
   for lib in libcdx.so $(for v in $VARIANTS; do echo libcdx_mean_${v%%:*}.so; done); do
     echo "== $lib round $r"
     CDX_LIB=$ROOT/compliancedex_amd/lib/$lib timeout -k 10 120 python -u tools/time_mean.py 53248 2000 50
-    CDX_LIB=$ROOT/compliancedex_amd/lib/$lib CDX_FORK_MEAN=0 timeout -k 10 120 python -u bench.py --steps 50 --warmup 20 --no-cpu-baseline | python -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('unforked bench', round(d['ms_per_step'],4), 'ms', d['stage_ms'])"
+    CDX_LIB=$ROOT/compliancedex_amd/lib/$lib CDX_FORK_MEAN=0 timeout -k 10 120 python -u bench.py --full --steps 50 --warmup 20 --no-cpu-baseline | python -c "import json,sys; d=json.loads([l for l in sys.stdin if l.startswith('{')][-1]); print('unforked bench', round(d['ms_per_step'],4), 'ms', d['stage_ms'])"
   done
 done
