@@ -83,6 +83,28 @@ class CdxKinOptBuffers(C.Structure):
                                             "opt_comp", "any", "tips", "fk_state")])
 
 
+class CdxGpisModeParams(C.Structure):
+    _fields_ = [("mode", C.c_int32), ("_pad", C.c_int32), ("fe", CdxForceEq), ("uncertainty", C.c_double),
+                ("ref_q", C.c_double * MAX_DOFS), ("palm_offset", C.c_double * 3)]
+
+
+class CdxGpisModeOpt(C.Structure):
+    _fields_ = [("lr", C.c_double * 3), ("alpha", C.c_double), ("eps", C.c_double),
+                ("box_lb", C.c_double * (MAX_TIPS * 3)), ("box_ub", C.c_double * (MAX_TIPS * 3)),
+                ("comp_min", C.c_double)]
+
+
+GPIS_MODE_FIELDS = ["pose", "target", "comp", "tips", "mean", "gmean", "normal", "std", "gstd", "tmean", "tgmean",
+                    "g_pose", "g_target", "g_comp", "g_tip", "v_pose", "v_target", "v_comp", "loss"]
+
+
+class CdxGpisModeBuffers(C.Structure):
+    _fields_ = ([(n, C.c_void_p) for n in GPIS_MODE_FIELDS] +
+                [("margin", C.c_void_p * 2), ("normal_slot", C.c_void_p * 2)] +
+                [(n, C.c_void_p) for n in ("opt_value", "opt_margin", "opt_normal", "opt_pose", "opt_target",
+                                            "opt_comp", "any")])
+
+
 class CdxSdfBatchQuery(C.Structure):
     _fields_ = [("mesh", C.c_void_p), ("faces", C.c_void_p), ("F", C.c_int64), ("points", C.c_void_p), ("P", C.c_int64),
                 ("sqdist", C.c_void_p), ("sign", C.c_void_p), ("normals", C.c_void_p), ("clst", C.c_void_p),
@@ -182,6 +204,14 @@ _SIGS = {
     "cdx_kin_iteration": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxKinParams), C.POINTER(CdxKinOpt),
                                     C.POINTER(CdxKinOptBuffers), _I64, C.c_int32] + [_P] * 10 +
                           [C.c_uint64, C.c_int32, _P]),
+    "cdx_gpis_mode_cost": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxGpisModeParams), C.POINTER(CdxGpisModeBuffers),
+                                     _I64, C.c_int32, _P, C.c_uint64, C.c_int32, _P]),
+    "cdx_gpis_mode_step": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxGpisModeParams), C.POINTER(CdxGpisModeOpt),
+                                     C.POINTER(CdxGpisModeBuffers), _I64, C.c_int32, C.c_int32, C.c_int32, _P]),
+    "cdx_gpis_mode_iteration": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxGpisModeParams), C.POINTER(CdxGpisModeOpt),
+                                          C.POINTER(CdxGpisModeBuffers), _I64, C.c_int32, _P, C.c_uint64, C.c_int32,
+                                          _P]),
+    "cdx_gpis_mode_abi_sizes": (None, [C.POINTER(C.c_size_t)]),
 }
 
 _lib = None
@@ -215,6 +245,11 @@ def load():
                 C.sizeof(CdxSdfBatchQuery)]
         if list(sizes) != mine:
             raise ImportError(f"ABI struct size mismatch: library {list(sizes)} vs binding {mine}")
+        sizes = (C.c_size_t * 3)()
+        lib.cdx_gpis_mode_abi_sizes(sizes)
+        mine = [C.sizeof(CdxGpisModeParams), C.sizeof(CdxGpisModeOpt), C.sizeof(CdxGpisModeBuffers)]
+        if list(sizes) != mine:
+            raise ImportError(f"ABI struct size mismatch (GPIS mode): library {list(sizes)} vs binding {mine}")
         info = build_info()
         if not info["matches"] and "CDX_LIB" not in os.environ:
             import warnings

@@ -1,5 +1,5 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
-// cdx_sdf.h.
+// cdx_sdf.h / cdx_gpis_mode.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
@@ -8,6 +8,7 @@
 
 #include "cdx_collision.h"
 #include "cdx_cost.h"
+#include "cdx_gpis_mode.h"
 #include "cdx_sdf.h"
 
 namespace {
@@ -146,6 +147,57 @@ void cdxh_force_eq(const cdx_force_eq* p, int64_t B, const double* tip, const do
       g_comp[b * T + f] = gc[f];
     }
   }
+}
+
+// The GPIS-mode optimiser iteration (cdx_gpis_mode_cost / cdx_gpis_mode_step) over a batch of host arrays: the same
+// per-candidate code, the same argument checks, the `any` flags kept as the device keeps them.
+int cdxh_gpis_mode_cost(const cdx_chain* chain, const cdx_gpis_mode_params* p, const cdx_gpis_mode_buffers* buf,
+                        int64_t E, int32_t n_tips, const double* noise, uint64_t seed, int32_t iteration) {
+  if (cdx::gpis_mode_check(chain, p, E, n_tips) || iteration < 0) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (cdx::gpis_mode_check_cost(p, buf)) return CDX_EINVAL;
+  const cdx_gpis_mode_buffers& b = *buf;
+  const int slot = iteration & 1;
+  const bool fk = p->mode == 1;
+  const bool shallow = fk && cdx::chain_max_depth(*chain) <= 8;
+  const cdx_chain none{};
+  float fk_g[CDX_MAX_DOFS];
+  for (int64_t e = 0; e < E; ++e) {
+    if (fk && shallow)  // (the depth bound the device picks: it selects the FK backward's form)
+      cdx::gpis_mode_cost_candidate<0, 8, true>(
+          *chain, *p, n_tips, e, b.pose, b.tips, b.target, b.comp, noise, seed, b.mean, b.gmean, b.normal, b.std, b.gstd,
+          b.tmean, b.tgmean, b.loss, b.margin[slot], b.normal_slot[slot], b.g_pose, b.g_target, b.g_comp, b.g_tip, fk_g, 1);
+    else if (fk)
+      cdx::gpis_mode_cost_candidate<0, CDX_MAX_DEPTH, true>(
+          *chain, *p, n_tips, e, b.pose, b.tips, b.target, b.comp, noise, seed, b.mean, b.gmean, b.normal, b.std, b.gstd,
+          b.tmean, b.tgmean, b.loss, b.margin[slot], b.normal_slot[slot], b.g_pose, b.g_target, b.g_comp, b.g_tip, fk_g, 1);
+    else
+      cdx::gpis_mode_cost_candidate<0, CDX_MAX_DEPTH, false>(
+          none, *p, n_tips, e, nullptr, b.pose, b.target, b.comp, noise, seed, b.mean, b.gmean, b.normal, b.std, b.gstd,
+          b.tmean, b.tgmean, b.loss, b.margin[slot], b.normal_slot[slot], nullptr, b.g_target, b.g_comp, b.g_pose, fk_g, 1);
+  }
+  return CDX_OK;
+}
+
+int cdxh_gpis_mode_step(const cdx_chain* chain, const cdx_gpis_mode_params* p, const cdx_gpis_mode_opt* opt,
+                        const cdx_gpis_mode_buffers* buf, int64_t E, int32_t n_tips, int32_t iteration,
+                        int32_t finalize) {
+  if (cdx::gpis_mode_check(chain, p, E, n_tips) || !opt) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (cdx::gpis_mode_check_step(opt, buf, iteration, finalize)) return CDX_EINVAL;
+  const cdx_gpis_mode_buffers& b = *buf;
+  const int s = iteration;
+  const cdx_chain none{};
+  if (s > 0 && b.any[(s - 1) % 3])
+    for (int64_t e = 0; e < E; ++e) cdx::gpis_mode_commit(b, n_tips, e, (s - 1) & 1);
+  if (finalize) return CDX_OK;
+  b.any[(s + 1) % 3] = 0u;
+  for (int64_t e = 0; e < E; ++e) {
+    const bool flag = p->mode == 1 ? cdx::gpis_mode_step_candidate<true>(*chain, *p, *opt, b, n_tips, e)
+                                   : cdx::gpis_mode_step_candidate<false>(none, *p, *opt, b, n_tips, e);
+    if (flag) b.any[s % 3] |= 1u;
+  }
+  return CDX_OK;
 }
 
 void cdxh_svd3(const double* H, double* U, double* S, double* V) { cdx::svd3(H, U, S, V); }

@@ -516,19 +516,179 @@ class SDFGraspOptimizer:
         return st.best()
 
 
+_MEAN_TILE = 32  # queries per workgroup of cdx_gpis_mean
+
+
+class _GpisModeLoop:
+    """Device state of a fused GPIS / KinGPIS loop (cdx_gpis_mode_*): the query points [tips; targets] in one
+    buffer, the per-point GPIS outputs, the gradients, RMSprop's square averages, the two margin / normal slots and
+    the best iterate.  Per iteration the loop is ONE cdx_gpis_mean launch over the 2·E·T points (mean, ∇mean, normal),
+    ONE cdx_gpis_std launch over the E·T fingertips (the reference's variance of the targets is never used) and
+    cdx_gpis_mode_iteration: no autograd graph, no host sync."""
+
+    loss_slot = _FusedLoop.loss_slot
+    loss_sums = _FusedLoop.loss_sums
+
+    def __init__(self, mode, pose, target, comp, gpis, dev):
+        f64 = dict(dtype=torch.float64, device=dev)
+        E, T = target.shape[0], target.shape[1]
+        self.E, self.T, self.mode = E, T, mode
+        self.state = gpis.native_state()
+        self.hist = None
+        # the iteration's query points in one buffer: the fingertips, then — from the next multiple of the mean
+        # kernel's 32-query workgroup on, so that every row is computed exactly as by a launch of its own, a workgroup
+        # holding a non-finite query included — the targets; the rows between hold a finite filler point
+        M = E * T
+        Mp = (M + _MEAN_TILE - 1) // _MEAN_TILE * _MEAN_TILE
+        self.Mp = Mp
+        self.X = self.state.X1[:1].repeat(Mp + M, 1).contiguous()
+        self.tips, self.target = self.X[:M].view(E, T, 3), self.X[Mp:].view(E, T, 3)
+        self.target.copy_(target)
+        if mode == 0:
+            self.tips.copy_(pose)
+            self.pose = self.tips
+        else:
+            self.pose = pose.detach().clone().contiguous()
+        self.comp = comp.detach().clone().contiguous()
+        Q = Mp + M
+        self.mean, self.gmean, self.nrm = torch.empty(Q, **f64), torch.empty(Q, 3, **f64), torch.empty(Q, 3, **f64)
+        self.std, self.gstd = torch.empty(M, **f64), torch.empty(M, 3, **f64)
+        self.ws = self.state.workspace(M)
+        self.loss = torch.empty(E, **f64)
+        self.margin = [torch.zeros(E, T, **f64) for _ in range(2)]
+        self.normal = [torch.zeros(M, 3, **f64) for _ in range(2)]
+        params = (self.pose, self.target, self.comp)
+        self.g = [torch.zeros_like(x) for x in params]
+        self.g_tip = torch.zeros(M, 3, **f64) if mode == 1 else None
+        self.v = [torch.zeros_like(x) for x in params]
+        self.opt_value = torch.full((E,), float("inf"), **f64)
+        self.opt_margin = torch.zeros(E, T, **f64)
+        self.opt_normal = torch.zeros(M, 3, **f64)
+        self.opt = [x.clone() for x in params]
+        self.any = torch.zeros(3, dtype=torch.int32, device=dev)
+        b = N.CdxGpisModeBuffers()
+        for name, t in (("pose", self.pose), ("target", self.target), ("comp", self.comp),
+                        ("tips", self.tips if mode == 1 else None), ("mean", self.mean[:M]), ("gmean", self.gmean[:M]),
+                        ("normal", self.nrm[:M]), ("std", self.std), ("gstd", self.gstd), ("tmean", self.mean[Mp:]),
+                        ("tgmean", self.gmean[Mp:]), ("g_pose", self.g[0]), ("g_target", self.g[1]),
+                        ("g_comp", self.g[2]), ("g_tip", self.g_tip), ("v_pose", self.v[0]), ("v_target", self.v[1]),
+                        ("v_comp", self.v[2]), ("loss", self.loss), ("opt_value", self.opt_value),
+                        ("opt_margin", self.opt_margin), ("opt_normal", self.opt_normal), ("opt_pose", self.opt[0]),
+                        ("opt_target", self.opt[1]), ("opt_comp", self.opt[2]), ("any", self.any)):
+            setattr(b, name, N.ptr(t))
+        for i in range(2):
+            b.margin[i], b.normal_slot[i] = N.ptr(self.margin[i]), N.ptr(self.normal[i])
+        self.buffers = b
+
+    def queries(self, lib, stream):
+        """The iteration's two GPIS launches: mean / ∇mean / normal at [tips; targets], std / ∇std at the tips."""
+        M = self.E * self.T
+        N.check(lib.cdx_gpis_mean(self.state.desc, N.ptr(self.X), self.Mp + M, N.ptr(self.mean), N.ptr(self.gmean),
+                                  N.ptr(self.nrm), stream), "cdx_gpis_mean")
+        N.check(lib.cdx_gpis_std(self.state.desc, N.ptr(self.X), M, N.ptr(self.std), N.ptr(self.gstd), N.ptr(self.ws),
+                                 stream), "cdx_gpis_std")
+
+    def best(self):
+        return self.opt[0], self.opt[2], self.opt[1], (self.opt_margin > 0.0).all()
+
+
+def _gpis_mode_run(self, mode, chain, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step):
+    """The fused loop of the two GPIS-mode optimisers on the loop state ``st``."""
+    lib = N.load()
+    dev = self.device
+    E, T = st.E, st.T
+    stream = N.stream_ptr(dev)
+    loss = None
+    if self.loop_events:
+        self.loop_events[0].record()
+    for s in range(self.num_iters):
+        nz = _noise(kabsch_noise, s)
+        nz = None if nz is None else nz.detach().to(device=dev, dtype=torch.float64).contiguous()
+        self._seed += 1
+        loss = st.loss_slot(s, self.num_iters)
+        st.queries(lib, stream)
+        if not verbose and not split_step:  # cost, backward and step in one launch (four fingertips)
+            N.check(lib.cdx_gpis_mode_iteration(chain, prm, cfg, st.buffers, E, T, N.ptr(nz), self._seed, s, stream),
+                    "cdx_gpis_mode_iteration")
+        else:
+            N.check(lib.cdx_gpis_mode_cost(chain, prm, st.buffers, E, T, N.ptr(nz), self._seed, s, stream),
+                    "cdx_gpis_mode_cost")
+            if verbose:
+                print("Loss:", float(loss.sum()))
+            N.check(lib.cdx_gpis_mode_step(chain, prm, cfg, st.buffers, E, T, s, 0, stream), "cdx_gpis_mode_step")
+        if st.hist is None:
+            self.loss_history.append(loss.sum())  # device scalar, no sync
+        if trace_rows:
+            self.loss_rows.append(loss.clone())
+    N.check(lib.cdx_gpis_mode_step(chain, prm, cfg, st.buffers, E, T, self.num_iters, 1, stream), "cdx_gpis_mode_step")
+    st.loss_sums(self.loss_history)
+    if self.loop_events:
+        self.loop_events[1].record()
+    if verbose:
+        print(st.opt_margin, st.opt_normal)
+    self.best_loss = st.opt_value
+    self._loop_state = st if self._keep_loop_state else None
+    return st.best()
+
+
+def _gpis_mode_inputs(name, dev, **tensors):
+    """The fused GPIS-mode loops take float64 device tensors (the reference runs these two modes in double)."""
+    from .gpis import _require_cuda
+    for k, t in tensors.items():
+        _require_cuda(t, f"{name} {k}")
+        if t.dtype != torch.float64:
+            raise ValueError(f"{name}: {k} must be float64 (the reference's dtype on this path), got {t.dtype}")
+
+
+def _gpis_mode_setup(self, mode, T, friction_mu, lrs):
+    prm = N.CdxGpisModeParams()
+    prm.mode = mode
+    prm.fe = force_eq_descriptor(T, friction_mu, self.mass, 10.0 if self.gravity else None, 2.0, self.com)
+    prm.uncertainty = float(self.uncertainty)
+    cfg = N.CdxGpisModeOpt()
+    cfg.lr[0], cfg.lr[1], cfg.lr[2] = lrs
+    cfg.alpha, cfg.eps, cfg.comp_min = 0.99, 1e-8, 40.0  # torch.optim.RMSprop defaults (:348 / :454); :401 / :506
+    lb = self.tip_bounding_box[0].to(torch.float64).expand(T, 3).reshape(-1).cpu().tolist()
+    ub = self.tip_bounding_box[1].to(torch.float64).expand(T, 3).reshape(-1).cpu().tolist()
+    for i in range(3 * T):
+        cfg.box_lb[i], cfg.box_ub[i] = lb[i], ub[i]
+    return prm, cfg
+
+
 class GPISGraspOptimizer:
     """Fingertip-space optimiser on the GPIS distance and variance (optimize_pregrasp.py:322-406)."""
 
     def __init__(self, tip_bounding_box, num_iters=2000, optimize_target=False, mass=0.1, com=(0.0, 0.0, 0.0),
-                 gravity=True, uncertainty=20.0, device="cuda"):
+                 gravity=True, uncertainty=20.0, device="cuda", seed=0):
+        """``seed``: key of the fused loop's on-device Kabsch noise (as KinGraspOptimizer's)."""
         self.device = torch.device(device)
+        self._seed = int(seed)
+        self.loop_events = None  # optional (start, end) CUDA events recorded around the iterations, eager or fused
+        self._keep_loop_state = False  # tests: keep the fused loop's device state in ``_loop_state`` after the call
         self.tip_bounding_box = [torch.tensor(tip_bounding_box[0]).to(self.device).view(-1, 3),
                                  torch.tensor(tip_bounding_box[1]).to(self.device).view(-1, 3)]
         self.num_iters = num_iters
         self.optimize_target = optimize_target
         self.mass, self.com, self.gravity, self.uncertainty = mass, list(com), gravity, uncertainty
 
-    def optimize(self, tip_pose, target_pose, compliance, friction_mu, gpis, verbose=True, kabsch_noise=None):
+    def optimize(self, tip_pose, target_pose, compliance, friction_mu, gpis, verbose=True, kabsch_noise=None,
+                 fused=False, trace_rows=False, split_step=False):
+        """``fused``: per iteration ONE cdx_gpis_mean launch over [tips; targets], ONE cdx_gpis_std launch over the
+        tips and ONE cost / backward / RMSprop / best-iterate / clamp launch (cdx_gpis_mode_iteration; with
+        ``split_step`` or ``verbose`` cdx_gpis_mode_cost then cdx_gpis_mode_step) — no autograd graph, no host sync,
+        float64 device inputs, the caller's tensors untouched; ``fused=False`` (default): the autograd loop with
+        torch.optim.RMSprop, as the reference writes it.  ``trace_rows``: also keep every iteration's per-candidate
+        loss in ``loss_rows`` (device)."""
+        self.loss_rows = []
+        if fused:
+            self.loss_history = []
+            _gpis_mode_inputs("GPISGraspOptimizer", self.device, tip_pose=tip_pose, target_pose=target_pose,
+                              compliance=compliance)
+            T = tip_pose.shape[1]
+            lrs = (1e-3, 1e-3 if self.optimize_target else 0.0, 0.2)  # tips, target, compliance (:348-355)
+            prm, cfg = _gpis_mode_setup(self, 0, T, friction_mu, lrs)
+            st = _GpisModeLoop(0, tip_pose.detach(), target_pose.detach(), compliance, gpis, self.device)
+            return _gpis_mode_run(self, 0, None, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step)
         tip_pose = tip_pose.clone().requires_grad_(True)
         self.loss_history = []
         compliance = compliance.clone().requires_grad_(True)
@@ -540,6 +700,8 @@ class GPISGraspOptimizer:
             optim = torch.optim.RMSprop([{"params": tip_pose, "lr": 1e-3}, {"params": compliance, "lr": 0.2}])
         E, T = tip_pose.shape[0], tip_pose.shape[1]
         best = _Best(torch.float64, E, T, self.device, tip=tip_pose, comp=compliance, target=target_pose)
+        if self.loop_events:
+            self.loop_events[0].record()
         for s in range(self.num_iters):
             optim.zero_grad()
             all_tip = tip_pose.view(-1, 3)
@@ -557,6 +719,8 @@ class GPISGraspOptimizer:
             l = c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0) + variance_cost
             l.sum().backward()
             self.loss_history.append(l.detach().sum())  # device scalar, no sync
+            if trace_rows:
+                self.loss_rows.append(l.detach().clone())
             if verbose:
                 print("Loss:", float(l.sum()), float(dist_cost.sum()), float(variance_cost.sum()))
             best.update(l, margin, normal, tip=tip_pose, comp=compliance, target=target_pose)
@@ -564,6 +728,8 @@ class GPISGraspOptimizer:
             with torch.no_grad():  # (:399-401)
                 tip_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
                 compliance.clamp_(min=40.0)
+        if self.loop_events:
+            self.loop_events[1].record()
         if verbose:
             print(best.margin, best.normal)
         self.best_loss = best.value
@@ -575,8 +741,12 @@ class KinGPISGraspOptimizer:
 
     def __init__(self, robot_urdf, ee_link_names, ee_link_offsets=EE_OFFSETS, palm_offset=WRIST_OFFSET, num_iters=1000,
                  optimize_target=False, ref_q=None, tip_bounding_box=(FINGERTIP_LB, FINGERTIP_UB), mass=0.1,
-                 com=(0.0, 0.0, 0.0), gravity=True, uncertainty=10.0, device="cuda"):
+                 com=(0.0, 0.0, 0.0), gravity=True, uncertainty=10.0, device="cuda", seed=0):
+        """``seed``: key of the fused loop's on-device Kabsch noise (as KinGraspOptimizer's)."""
         self.device = torch.device(device)
+        self._seed = int(seed)
+        self.loop_events = None  # optional (start, end) CUDA events recorded around the iterations, eager or fused
+        self._keep_loop_state = False  # tests: keep the fused loop's device state in ``_loop_state`` after the call
         self.ref_q = torch.tensor(list(ref_q)).to(self.device)
         self.robot_model = DifferentiableRobotModel(robot_urdf, device=device)
         self.num_iters = num_iters
@@ -593,7 +763,18 @@ class KinGPISGraspOptimizer:
                                                           offsets=self.ee_link_offsets, recursive=True)[0]
         return (tips.view(-1, 3) + self.palm_offset).view(-1, 3)
 
-    def optimize(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose=True, kabsch_noise=None):
+    def optimize(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose=True, kabsch_noise=None,
+                 fused=False, trace_rows=False, split_step=False):
+        """``fused`` / ``trace_rows`` / ``split_step``: as GPISGraspOptimizer.optimize; the fused step also clamps the
+        targets (optimised or not, :505-507) and computes the next iteration's fingertips, so the loop has one FK
+        launch in all (iteration 0's)."""
+        self.loss_rows = []
+        if fused:
+            self.loss_history = []
+            _gpis_mode_inputs("KinGPISGraspOptimizer", self.device, joint_angles=joint_angles, target_pose=target_pose,
+                              compliance=compliance)
+            return self._optimize_fused(joint_angles, target_pose, compliance, friction_mu, gpis, verbose, kabsch_noise,
+                                        trace_rows, split_step)
         joint_angles = joint_angles.clone().requires_grad_(True)
         self.loss_history = []
         compliance = compliance.clone().requires_grad_(True)
@@ -605,6 +786,8 @@ class KinGPISGraspOptimizer:
             optim = torch.optim.RMSprop([{"params": joint_angles, "lr": 1e-2}, {"params": compliance, "lr": 0.2}])
         E, T = target_pose.shape[0], target_pose.shape[1]
         best = _Best(torch.float64, E, T, self.device, q=joint_angles, comp=compliance, target=target_pose)
+        if self.loop_events:
+            self.loop_events[0].record()
         for s in range(self.num_iters):
             optim.zero_grad()
             all_tip = self.forward_kinematics(joint_angles)
@@ -624,6 +807,8 @@ class KinGPISGraspOptimizer:
                  variance_cost.max(dim=1)[0])
             l.sum().backward()
             self.loss_history.append(l.detach().sum())  # device scalar, no sync
+            if trace_rows:
+                self.loss_rows.append(l.detach().clone())
             if verbose:
                 print("Loss:", float(l.sum()), variance_cost.detach())
             best.update(l, margin, normal, q=joint_angles, comp=compliance, target=target_pose)
@@ -631,7 +816,31 @@ class KinGPISGraspOptimizer:
             with torch.no_grad():  # (:503-505)
                 compliance.clamp_(min=40.0)
                 target_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
+        if self.loop_events:
+            self.loop_events[1].record()
         if verbose:
             print(best.margin, best.normal)
         self.best_loss = best.value
         return best.params["q"], best.params["comp"], best.params["target"], best.flag()
+
+    def _optimize_fused(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose, kabsch_noise,
+                        trace_rows, split_step):
+        lib = N.load()
+        dev = self.device
+        E, T = target_pose.shape[0], target_pose.shape[1]
+        # q, target, compliance (:454-460)
+        lrs = (2e-3, 1e-3, 0.2) if self.optimize_target else (1e-2, 0.0, 0.2)
+        prm, cfg = _gpis_mode_setup(self, 1, T, friction_mu, lrs)
+        for i, v in enumerate(self.ref_q.to(torch.float64).tolist()):
+            prm.ref_q[i] = v
+        off = self.palm_offset.to(torch.float64).cpu().tolist()
+        for i in range(3):
+            prm.palm_offset[i] = off[i]
+        chain = self.robot_model._descriptor(self.ee_link_names, self.ee_link_offsets)
+        st = _GpisModeLoop(1, joint_angles.detach(), target_pose.detach(), compliance, gpis, dev)
+        # iteration 0's fingertips: double(FK_f32(float(q))) + palm offset (:462); later ones: cdx_gpis_mode_step
+        tips32 = torch.empty(E, T, 3, dtype=torch.float32, device=dev)
+        N.check(lib.cdx_fk_forward(chain, N.ptr(st.pose.float().contiguous()), E, N.ptr(tips32), None, N.stream_ptr(dev)),
+                "cdx_fk_forward")
+        st.tips.copy_(tips32.double() + self.palm_offset.to(torch.float64))
+        return _gpis_mode_run(self, 1, chain, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step)

@@ -420,6 +420,88 @@ int cdx_kin_iteration(const cdx_chain* chain, const cdx_kin_params* p, const cdx
                       const float* tsqdist, const int32_t* tsign, const float* tclst, const double* noise,
                       uint64_t seed, int32_t iteration, cdx_stream_t stream);
 
+/* ------------------------------------------------- GPIS / KinGPIS optimiser iteration ------
+ * The fused loop of GPISGraspOptimizer (optimize_pregrasp.py:322-406, mode 0: the fingertips are the parameters)
+ * and KinGPISGraspOptimizer (:408-511, mode 1: the joint angles are, tips = FK(q) + palm_offset), one lane per
+ * candidate, after the iteration's GPIS queries: cdx_gpis_mean over [tips; targets] (mean, ∇mean, normal) and
+ * cdx_gpis_std over the tips (std, ∇std; the reference's variance of the targets, :364 / :465, is never used).
+ *
+ * Dtypes: every array is f64 — the reference runs both modes in double.  Mode 1's FK is the float32 chain of
+ * cdx_fk_forward / cdx_fk_backward: tips = double(FK_f32(float(q))) + palm_offset, and the fingertip gradient is
+ * rounded to float32, walked back through the chain in float32 and widened again (robot_model._FK).
+ *
+ * cdx_gpis_mode_cost: loss [E], the force-closure margins into margin[iteration & 1], the fingertip normals copied
+ *   into normal_slot[iteration & 1] (when set), and the gradients of the loss
+ *     mode 0 (:374-383)  −25·reward + 1000·Σ|mean| + 10·Σ tmean + 10·‖mean tip − mean target‖
+ *                        − Σ min(fn·softmin(fn), 1) + uncertainty·Σ std
+ *     mode 1 (:473-486)  −5·reward + (the same four terms) + 20·‖q − ref_q‖ + max_t uncertainty·log(100·std_t)
+ *   into g_pose (tips / q), g_target, g_comp and (mode 1, nullable) g_tip, with torch autograd's rules: sign(0) = 0,
+ *   a zero norm gives a zero gradient, clamp(max = 1) passes the gradient where it does not clamp, the max feeds its
+ *   first maximal fingertip, normals are detached.  noise [E*9] is force_eq_reward's rand_like draw, or NULL for the
+ *   on-device draw keyed by (seed, row) of cdx_force_eq_*.
+ * cdx_gpis_mode_step: in this order
+ *   1. the best-iterate update (:389-397 / :495-503): per candidate, loss < opt_value in f64 copies the pose, target
+ *      and compliance the loss was computed on (a non-finite loss never does); opt_margin / opt_normal are the WHOLE
+ *      batch's margin / normal of the last iteration in which ANY candidate improved, committed one launch late from
+ *      the alternating slots through any[3] (zeroed before iteration 0) and by a `finalize` call after the last
+ *      iteration (iteration = the iteration count; only commits) — the protocol of cdx_kin_step;
+ *   2. RMSprop in f64, torch's single-tensor order (:348-355 / :454-460): sq = α·sq + (1 − α)·g², p −= lr·g/(√sq + eps);
+ *      one lr per group (pose, target, compliance), lr 0 freezes a group;
+ *   3. the clamps — mode 0: tips into [box_lb, box_ub] per fingertip, comp ≥ comp_min (:399-401); mode 1:
+ *      comp ≥ comp_min and the TARGETS into the box, optimised or not (:505-507);
+ *   4. mode 1 with `tips` set: the next iteration's fingertips, so that the loop needs no FK launch (iteration 0's
+ *      come from one cdx_fk_forward).
+ * cdx_gpis_mode_iteration: cost then step on the state in `buf`, in ONE launch for four fingertips (bit-identical
+ *   to the two calls), else the two launches.
+ * One cdx_gpis_mode_buffers (its slots, moments, best iterate and any[3]) belongs to one loop: two loops never share
+ * one, and the caller zeroes v_* / any and sets opt_value to +inf before iteration 0.  chain: mode 1 only (NULL for
+ * mode 0).  Runtime n_tips ≤ CDX_MAX_TIPS, n_dofs ≤ CDX_MAX_DOFS.  E = 0 is a no-op. */
+typedef struct {
+  int32_t mode;                  /* 0 GPIS (fingertip space), 1 KinGPIS (joint space) */
+  int32_t _pad;
+  cdx_force_eq fe;               /* force_eq_reward constants */
+  double uncertainty;            /* variance-cost weight (:383 / :480) */
+  double ref_q[CDX_MAX_DOFS];    /* mode 1: ref_cost = 20·‖q − ref_q‖ */
+  double palm_offset[3];         /* mode 1: tips = FK(q) + palm_offset */
+} cdx_gpis_mode_params;
+
+typedef struct {
+  double lr[3];                  /* pose, target, compliance */
+  double alpha, eps;             /* RMSprop */
+  double box_lb[CDX_MAX_TIPS * 3];
+  double box_ub[CDX_MAX_TIPS * 3];
+  double comp_min;
+} cdx_gpis_mode_opt;
+
+typedef struct {                 /* device pointers, candidate-major, all f64 */
+  double *pose, *target, *comp;  /* parameters, in place: pose = tips [E*T*3] (mode 0) or q [E*D] (mode 1) */
+  double* tips;                  /* mode 1: this iteration's fingertips [E*T*3]; the step writes the next ones */
+  const double *mean, *gmean, *normal, *std, *gstd; /* GPIS at the fingertips: [E*T], [E*T*3], … */
+  const double *tmean, *tgmean;  /* GPIS mean / ∇mean at the targets */
+  double *g_pose, *g_target, *g_comp;
+  double* g_tip;                 /* mode 1: gradient w.r.t. the fingertips (nullable) */
+  double *v_pose, *v_target, *v_comp; /* RMSprop square averages */
+  double* loss;                  /* [E] */
+  double* margin[2];             /* [E*T] slots (iteration s writes s & 1) */
+  double* normal_slot[2];        /* [E*T*3] slots */
+  double* opt_value;             /* [E], +inf before iteration 0 */
+  double *opt_margin, *opt_normal;
+  double *opt_pose, *opt_target, *opt_comp;
+  uint32_t* any;                 /* [3] */
+} cdx_gpis_mode_buffers;
+
+int cdx_gpis_mode_cost(const cdx_chain* chain, const cdx_gpis_mode_params* p, const cdx_gpis_mode_buffers* buf,
+                       int64_t E, int32_t n_tips, const double* noise, uint64_t seed, int32_t iteration,
+                       cdx_stream_t stream);
+int cdx_gpis_mode_step(const cdx_chain* chain, const cdx_gpis_mode_params* p, const cdx_gpis_mode_opt* opt,
+                       const cdx_gpis_mode_buffers* buf, int64_t E, int32_t n_tips, int32_t iteration,
+                       int32_t finalize, cdx_stream_t stream);
+int cdx_gpis_mode_iteration(const cdx_chain* chain, const cdx_gpis_mode_params* p, const cdx_gpis_mode_opt* opt,
+                            const cdx_gpis_mode_buffers* buf, int64_t E, int32_t n_tips, const double* noise,
+                            uint64_t seed, int32_t iteration, cdx_stream_t stream);
+/* sizeof of the three structs above (cdx_abi_sizes keeps its thirteen). */
+void cdx_gpis_mode_abi_sizes(size_t* out3);
+
 /* ------------------------------------------------------------ collision loss -------
  * Replaces ProbabilisticGraspOptimizer.compute_collision_loss (optimize_pregrasp.py:671-701):
  * anchor links by f32 FK (:674-676), palm transform R(euler XYZ)·a + palm_pos (:677-678), then

@@ -1,0 +1,419 @@
+"""The GPIS-mode optimiser iteration (csrc/cdx_gpis_mode.h: cdx_gpis_mode_cost / cdx_gpis_mode_step) on the CPU: the
+host build of the per-candidate code (libcdx_host.so: cdxh_gpis_mode_cost / cdxh_gpis_mode_step) against the two
+reference loops written in torch-CPU float64 from the oracle's pieces (OracleGPIS.pred / compute_normal,
+force_eq_reward, the oracle FK, torch.optim.RMSprop), the gradient rules on hand-made rows, and the C ABI's argument
+checks.  No GPU."""
+import ctypes as C
+
+import numpy as np
+import pytest
+import torch
+
+from compliancedex_amd import _native as N
+from compliancedex_amd.force_eq import force_eq_descriptor
+from compliancedex_amd.optimizer import FINGERTIP_LB, FINGERTIP_UB
+from tests import _host
+from tests._helpers import oracle_chain, oracle_gpis_at, product_chain, rel_err
+
+E, T, ITERS = 5, 4, 6
+TOL = {0: 1e-6, 1: 1e-5}  # GPIS in tip space; KinGPIS through the float32 FK (test_gpu_parity.py)
+UNCERTAINTY = {0: 20.0, 1: 10.0}
+INIT_TIP = np.array([[0.05, 0.05, 0.02], [0.06, -0.0, -0.01], [0.03, -0.04, 0.0], [-0.07, -0.01, 0.02]])
+# the bounds as the optimisers hold them: float32 tensors
+BOX_LB = np.asarray(FINGERTIP_LB, np.float32).astype(np.float64)
+BOX_UB = np.asarray(FINGERTIP_UB, np.float32).astype(np.float64)
+
+
+def _lib():
+    h = _host.host()
+    P = C.c_void_p
+    h.cdxh_gpis_mode_cost.restype = C.c_int
+    h.cdxh_gpis_mode_cost.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxGpisModeParams),
+                                      C.POINTER(N.CdxGpisModeBuffers), C.c_int64, C.c_int32, P, C.c_uint64, C.c_int32]
+    h.cdxh_gpis_mode_step.restype = C.c_int
+    h.cdxh_gpis_mode_step.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxGpisModeParams),
+                                      C.POINTER(N.CdxGpisModeOpt), C.POINTER(N.CdxGpisModeBuffers), C.c_int64,
+                                      C.c_int32, C.c_int32, C.c_int32]
+    return h
+
+
+@pytest.fixture(scope="module")
+def gpis():
+    """A 60-point box GPIS (workloads.box_arrays, cut): 14 external, 26 surface, 20 internal points."""
+    from compliancedex_amd.workloads import box_arrays
+    from oracle.cdx_oracle import OracleGPIS
+    X1, y, noise = box_arrays(n_surface=26)
+    return OracleGPIS.fit(X1[:60], y[:60], noise[:60], bias=1.0)
+
+
+@pytest.fixture(scope="module")
+def hand():
+    ochain, c = oracle_chain("allegro")
+    cfg = c["config"]
+    desc = product_chain("allegro").descriptor(cfg["ee_link_name"], cfg["ee_link_offset"])
+    ref_q = np.asarray(cfg["ref_q"], np.float32).astype(np.float64)  # (the optimiser's ref_q tensor is float32)
+    tips0 = _host.fk_forward(desc, ref_q[None].astype(np.float32))[0].reshape(T, 3).astype(np.float64)
+    palm = np.array([0.0, 0.0, 0.03]) - tips0.mean(0)  # the reference pose's fingertips around the box
+    return dict(ochain=ochain, links=cfg["ee_link_name"], offsets=cfg["ee_link_offset"], desc=desc, ref_q=ref_q,
+                palm=palm, D=desc.n_dofs)
+
+
+def _inputs(mode, hand, seed=50, n=E):
+    rng = np.random.default_rng(seed)
+    tips = np.array([0.0, 0.0, 0.03]) + 0.6 * INIT_TIP + 0.005 * rng.standard_normal((n, T, 3))
+    target = np.array([0.0, 0.0, 0.03]) + 0.003 * rng.standard_normal((n, T, 3))
+    target[0, 0, 2] = 0.01  # below the box (z ≥ 0.015): mode 1 clamps it, mode 0 leaves the targets alone
+    comp = np.tile([60.0, 60.0, 60.0, 80.0], (n, 1)) + rng.uniform(0, 5, (n, T))
+    q = hand["ref_q"] + 0.05 * rng.standard_normal((n, hand["D"]))
+    noise = rng.uniform(0, 1, (ITERS, n, 3, 3))
+    return (q if mode == 1 else tips), target, comp, noise
+
+
+def _params(mode, hand, mu=1.0):
+    prm = N.CdxGpisModeParams()
+    prm.mode = mode
+    prm.fe = force_eq_descriptor(T, mu, 0.1, 10.0, 2.0, (0.0, 0.0, 0.0))
+    prm.uncertainty = UNCERTAINTY[mode]
+    if mode == 1:
+        for i, v in enumerate(hand["ref_q"]):
+            prm.ref_q[i] = v
+        for i in range(3):
+            prm.palm_offset[i] = hand["palm"][i]
+    return prm
+
+
+def _opt(lrs):
+    cfg = N.CdxGpisModeOpt()
+    cfg.lr[0], cfg.lr[1], cfg.lr[2] = lrs
+    cfg.alpha, cfg.eps, cfg.comp_min = 0.99, 1e-8, 40.0
+    for i in range(3 * T):
+        cfg.box_lb[i], cfg.box_ub[i] = BOX_LB[i], BOX_UB[i]
+    return cfg
+
+
+def _lrs(mode, optimize_target):
+    if mode == 0:
+        return (1e-3, 1e-3 if optimize_target else 0.0, 0.2)
+    return (2e-3, 1e-3, 0.2) if optimize_target else (1e-2, 0.0, 0.2)
+
+
+class HostLoop:
+    """The loop state of cdx_gpis_mode_* in numpy arrays, and the host entry points on it."""
+
+    def __init__(self, mode, hand, pose, target, comp):
+        n = target.shape[0]
+        self.mode, self.n, self.hand = mode, n, hand
+        self.chain = hand["desc"] if mode == 1 else None
+        z = lambda *s: np.zeros(s)  # noqa: E731
+        a = dict(pose=pose.copy(), target=target.copy(), comp=comp.copy(), tips=z(n, T, 3), mean=z(n * T),
+                 gmean=z(n * T, 3), normal=z(n * T, 3), std=z(n * T), gstd=z(n * T, 3), tmean=z(n * T),
+                 tgmean=z(n * T, 3), g_pose=np.zeros_like(pose), g_target=z(n, T, 3), g_comp=z(n, T), g_tip=z(n, T, 3),
+                 v_pose=np.zeros_like(pose), v_target=z(n, T, 3), v_comp=z(n, T), loss=z(n),
+                 opt_value=np.full(n, np.inf), opt_margin=z(n, T), opt_normal=z(n * T, 3), opt_pose=pose.copy(),
+                 opt_target=target.copy(), opt_comp=comp.copy(), any=np.zeros(3, np.uint32))
+        self.a = a
+        self.margin = [z(n, T), z(n, T)]
+        self.nslot = [z(n * T, 3), z(n * T, 3)]
+        b = N.CdxGpisModeBuffers()
+        for k, v in a.items():
+            setattr(b, k, v.ctypes.data)
+        for i in range(2):
+            b.margin[i], b.normal_slot[i] = self.margin[i].ctypes.data, self.nslot[i].ctypes.data
+        self.b = b
+        if mode == 1:
+            self.fk()
+
+    def fk(self):
+        pos = _host.fk_forward(self.chain, self.a["pose"].astype(np.float32))[0]
+        self.a["tips"][:] = pos.reshape(self.n, T, 3).astype(np.float64) + self.hand["palm"]
+
+    def points(self):
+        return self.a["tips"] if self.mode == 1 else self.a["pose"]
+
+    def set_gpis(self, g):
+        """The oracle's per-point data at the current fingertips and targets (∇std by autograd).  (A non-finite point
+        is queried at 0: the oracle's batched solve would spread it over the batch; such a row's data is the test's.)"""
+        at = oracle_gpis_at(g, np.nan_to_num(self.points().reshape(-1, 3)), True)
+        tt = oracle_gpis_at(g, np.nan_to_num(self.a["target"].reshape(-1, 3)), False)
+        for k in ("mean", "gmean", "normal", "std", "gstd"):
+            self.a[k][:] = at[k].reshape(self.a[k].shape)
+        self.a["tmean"][:] = tt["mean"].reshape(-1)
+        self.a["tgmean"][:] = tt["gmean"]
+
+    def cost(self, prm, noise, s, seed=0):
+        nz = None if noise is None else np.ascontiguousarray(noise.reshape(self.n, 9))
+        rc = _lib().cdxh_gpis_mode_cost(self.chain, prm, self.b, self.n, T, None if nz is None else nz.ctypes.data,
+                                        seed, s)
+        assert rc == 0
+        return self.a["loss"].copy()
+
+    def step(self, prm, cfg, s, finalize=0):
+        assert _lib().cdxh_gpis_mode_step(self.chain, prm, cfg, self.b, self.n, T, s, finalize) == 0
+
+
+def _ref_loss(mode, g, hand, pose, target, comp, noise, mu=1.0):
+    """One iteration's per-candidate loss of the two eager loops (optimizers.py / optimize_pregrasp.py:362-383,
+    :462-486) on torch-CPU float64 tensors; returns (l, margin, tips)."""
+    from oracle.cdx_oracle import force_eq_reward
+    n = target.shape[0]
+    if mode == 1:
+        fk = hand["ochain"].forward_kinematics(pose, hand["links"], hand["offsets"])[0]
+        tips = (fk.view(-1, 3) + torch.from_numpy(hand["palm"])).view(n, T, 3)
+    else:
+        tips = pose
+    dist, var = g.pred(tips.reshape(-1, 3))
+    tar_dist, _ = g.pred(target.reshape(-1, 3))
+    normal = g.compute_normal(tips.reshape(-1, 3))
+    reward, margin, fnorm, _ = force_eq_reward(tips, target, comp, mu, normal.view(n, T, 3), noise, mass=0.1,
+                                               gravity=10.0, COM=(0.0, 0.0, 0.0))
+    center = (tips.mean(dim=1) - target.mean(dim=1)).norm(dim=1) * 10.0
+    dist_cost = 1000 * torch.abs(dist).view(n, T).sum(dim=1)
+    tar_cost = 10 * tar_dist.view(n, T).sum(dim=1)
+    force = -(fnorm * torch.nn.functional.softmin(fnorm, dim=1)).clamp(max=1.0).sum(dim=1)
+    if mode == 0:
+        l = -reward * 25.0 + dist_cost + tar_cost + center + force + UNCERTAINTY[0] * var.view(n, T).sum(dim=1)
+    else:
+        ref = (pose - torch.from_numpy(hand["ref_q"])).norm(dim=1) * 20.0
+        vc = UNCERTAINTY[1] * torch.log(100 * var).view(n, T)
+        l = -reward * 5.0 + dist_cost + tar_cost + center + force + ref + vc.max(dim=1)[0]
+    return l, margin, tips
+
+
+def _ref_loop(mode, g, hand, pose0, target0, comp0, noise, optimize_target):
+    pose = torch.from_numpy(pose0.copy()).requires_grad_(True)
+    comp = torch.from_numpy(comp0.copy()).requires_grad_(True)
+    target = torch.from_numpy(target0.copy())
+    lrs = _lrs(mode, optimize_target)
+    groups = [{"params": pose, "lr": lrs[0]}, {"params": comp, "lr": lrs[2]}]
+    if optimize_target:
+        target.requires_grad_(True)
+        groups.insert(1, {"params": target, "lr": lrs[1]})
+    optim = torch.optim.RMSprop(groups)
+    lb, ub = torch.from_numpy(BOX_LB).view(T, 3), torch.from_numpy(BOX_UB).view(T, 3)
+    n = target.shape[0]
+    opt_value = torch.full((n,), float("inf"), dtype=torch.float64)
+    best = dict(pose=pose.detach().clone(), target=target.detach().clone(), comp=comp.detach().clone(), margin=None)
+    losses, grads = [], []
+    for s in range(ITERS):
+        optim.zero_grad()
+        l, margin, _ = _ref_loss(mode, g, hand, pose, target, comp, torch.from_numpy(noise[s]))
+        l.sum().backward()
+        losses.append(l.detach().numpy().copy())
+        grads.append((pose.grad.numpy().copy(), target.grad.numpy().copy() if optimize_target else None,
+                      comp.grad.numpy().copy()))
+        with torch.no_grad():
+            flag = l < opt_value
+            if flag.any():
+                best["margin"] = margin.detach().clone()
+                opt_value[flag] = l[flag]
+                for k, v in (("pose", pose), ("target", target), ("comp", comp)):
+                    best[k][flag] = v[flag]
+        optim.step()
+        with torch.no_grad():
+            comp.clamp_(min=40.0)
+            (pose if mode == 0 else target).clamp_(min=lb, max=ub)
+    final = dict(pose=pose.detach().numpy(), target=target.detach().numpy(), comp=comp.detach().numpy())
+    return losses, grads, final, {k: v.numpy() for k, v in best.items()}, opt_value.numpy()
+
+
+@pytest.mark.parametrize("optimize_target", [True, False])
+@pytest.mark.parametrize("mode", [0, 1])
+def test_host_loop_vs_autograd(mode, optimize_target, gpis, hand):
+    """E = 5, T = 4, 6 iterations with replayed noise: per-iteration per-candidate loss, the gradients, the final
+    parameters, the best iterates, opt_value and opt_margin of the host build against the torch loop, at 1e-6 (GPIS)
+    / 1e-5 (KinGPIS, through the float32 FK)."""
+    pose0, target0, comp0, noise = _inputs(mode, hand)
+    losses, grads, final, best, opt_value = _ref_loop(mode, gpis, hand, pose0, target0, comp0, noise, optimize_target)
+    h = HostLoop(mode, hand, pose0, target0, comp0)
+    prm, cfg = _params(mode, hand), _opt(_lrs(mode, optimize_target))
+    tol = TOL[mode]
+    for s in range(ITERS):
+        h.set_gpis(gpis)
+        l = h.cost(prm, noise[s], s)
+        assert np.isfinite(l).all()
+        assert rel_err(l, losses[s]) < tol, (s, l, losses[s])
+        assert rel_err(h.a["g_pose"], grads[s][0]) < tol, s
+        assert rel_err(h.a["g_comp"], grads[s][2]) < tol, s
+        if optimize_target:
+            assert rel_err(h.a["g_target"], grads[s][1]) < tol, s
+        h.step(prm, cfg, s)
+    h.step(prm, cfg, ITERS, finalize=1)
+    for k in ("pose", "target", "comp"):
+        assert rel_err(h.a[k], final[k]) < tol, k
+        assert rel_err(h.a["opt_" + k], best[k]) < tol, k
+    assert rel_err(h.a["opt_value"], opt_value) < tol
+    assert rel_err(h.a["opt_margin"], best["margin"]) < tol
+    if mode == 1 and not optimize_target:  # the targets are clamped although they are not optimised (:505-507)
+        assert np.array_equal(h.a["target"], np.clip(target0, BOX_LB.reshape(T, 3), BOX_UB.reshape(T, 3)))
+        assert not np.array_equal(h.a["target"], target0)
+
+
+def _one_row(mode, hand, gpis, edit=None, n=1, seed=3):
+    """cdxh_gpis_mode_cost on hand-made rows: ``edit(h)`` changes the loop state after the oracle's GPIS data is in."""
+    pose0, target0, comp0, noise = _inputs(mode, hand, seed=seed, n=n)
+    h = HostLoop(mode, hand, pose0, target0, comp0)
+    h.set_gpis(gpis)
+    if edit:
+        edit(h)
+    h.cost(_params(mode, hand), noise[0], 0)
+    return h
+
+
+def test_zero_mean_has_zero_distance_gradient(gpis, hand):
+    """|mean| at mean = 0: sign(0) = 0, so ∇mean does not reach the fingertip gradient."""
+    def edit(scale):
+        def f(h):
+            h.a["mean"][:] = 0.0
+            h.a["gmean"][:] *= scale
+        return f
+    a, b = _one_row(0, hand, gpis, edit(1.0)), _one_row(0, hand, gpis, edit(-3.0))
+    assert np.array_equal(a.a["g_pose"], b.a["g_pose"]) and np.isfinite(a.a["g_pose"]).all()
+    c = _one_row(0, hand, gpis)  # (and with the real means the gradient does depend on ∇mean)
+    assert not np.array_equal(a.a["g_pose"], c.a["g_pose"])
+
+
+def test_coincident_centres_have_zero_centre_gradient(gpis, hand):
+    """‖mean tip − mean target‖ = 0: torch's norm backward gives 0, not 0/0."""
+    def edit(h):
+        t = h.a["pose"][0]
+        h.a["target"][0] = t[[1, 0, 2, 3]]  # the same four points, the same sums in the same order
+        h.set_gpis(gpis)
+    h = _one_row(0, hand, gpis, edit)
+    assert np.isfinite(h.a["loss"]).all()
+    for k in ("g_pose", "g_target", "g_comp"):
+        assert np.isfinite(h.a[k]).all(), k
+    # against autograd on the same row
+    pose, target, comp = (torch.from_numpy(h.a[k].copy()).requires_grad_(True) for k in ("pose", "target", "comp"))
+    _, _, _, noise = _inputs(0, hand, seed=3, n=1)
+    l, _, _ = _ref_loss(0, gpis, hand, pose, target, comp, torch.from_numpy(noise[0]))
+    l.sum().backward()
+    assert rel_err(h.a["loss"], l.detach().numpy()) < 1e-6
+    assert rel_err(h.a["g_pose"], pose.grad.numpy()) < 1e-6 and rel_err(h.a["g_target"], target.grad.numpy()) < 1e-6
+
+
+def test_clamped_force_term_passes_no_gradient(gpis, hand):
+    """clamp(fn·softmin(fn), max = 1): stiff springs push terms over the clamp; the gradients still equal autograd's
+    (which passes nothing through a clamped term)."""
+    from oracle.cdx_oracle import force_eq_reward
+
+    def edit(h):
+        h.a["comp"][:] = [[4000.0, 100.0, 100.0, 100.0]]
+    h = _one_row(0, hand, gpis, edit)
+    pose, target, comp = (torch.from_numpy(h.a[k].copy()).requires_grad_(True) for k in ("pose", "target", "comp"))
+    _, _, _, noise = _inputs(0, hand, seed=3, n=1)
+    nz = torch.from_numpy(noise[0])
+    with torch.no_grad():
+        nrm = gpis.compute_normal(pose.reshape(-1, 3)).view(1, T, 3)
+        fn = force_eq_reward(pose, target, comp, 1.0, nrm, nz, mass=0.1, gravity=10.0, COM=(0.0, 0.0, 0.0))[2]
+        v = fn * torch.nn.functional.softmin(fn, dim=1)
+    assert bool((v > 1.0).any()) and bool((v < 1.0).any()), v  # the row has clamped and unclamped terms
+    l, _, _ = _ref_loss(0, gpis, hand, pose, target, comp, nz)
+    l.sum().backward()
+    assert rel_err(h.a["loss"], l.detach().numpy()) < 1e-6
+    for k, t in (("g_pose", pose), ("g_target", target), ("g_comp", comp)):
+        assert rel_err(h.a[k], t.grad.numpy()) < 1e-6, k
+
+
+def test_kingpis_max_feeds_the_first_maximal_fingertip(gpis, hand):
+    """max_t uncertainty·log(100·std_t) with two equal maxima (fingertips 1 and 2): ∇std of fingertip 1 reaches the
+    fingertip gradient, ∇std of fingertip 2 (and of the others) does not."""
+    def edit(which, scale):
+        def f(h):
+            s = h.a["std"].reshape(1, T)
+            s[0] = [0.5 * s.max(), 2.0 * s.max(), 2.0 * s.max(), 0.5 * s.max()]
+            s[0, 2] = s[0, 1]
+            h.a["gstd"].reshape(1, T, 3)[0, which] *= scale
+        return f
+    base = _one_row(1, hand, gpis, edit(0, 1.0))
+    for which in (0, 2, 3):
+        assert np.array_equal(_one_row(1, hand, gpis, edit(which, 5.0)).a["g_tip"], base.a["g_tip"]), which
+    moved = _one_row(1, hand, gpis, edit(1, 5.0)).a["g_tip"]
+    assert not np.array_equal(moved[0, 1], base.a["g_tip"][0, 1])
+    assert np.array_equal(moved[0, [0, 2, 3]], base.a["g_tip"][0, [0, 2, 3]])
+
+
+def test_deep_chain_gradient_vs_autograd(gpis):
+    """The arm + hand chain (iiwa7_allegro: fingertips deeper than 8 levels, where the FK backward is the closed form
+    without per-level state): one KinGPIS iteration's loss and gradients against autograd through the oracle FK."""
+    from compliancedex_amd.workloads import CONFIG4_OFFSETS
+    ochain, c = oracle_chain("iiwa7_allegro")
+    links = c["config"]["ee_link_name"]
+    desc = product_chain("iiwa7_allegro").descriptor(links, CONFIG4_OFFSETS)
+    D = desc.n_dofs
+    tips0 = _host.fk_forward(desc, np.zeros((1, D), np.float32))[0].reshape(T, 3).astype(np.float64)
+    deep = dict(ochain=ochain, links=links, offsets=CONFIG4_OFFSETS, desc=desc, ref_q=np.zeros(D),
+                palm=np.array([0.0, 0.0, 0.03]) - tips0.mean(0), D=D)
+    h = _one_row(1, deep, gpis, n=3)
+    q0, target0, comp0, noise = _inputs(1, deep, seed=3, n=3)
+    q, target, comp = (torch.from_numpy(a.copy()).requires_grad_(True) for a in (q0, target0, comp0))
+    l, _, _ = _ref_loss(1, gpis, deep, q, target, comp, torch.from_numpy(noise[0]))
+    l.sum().backward()
+    assert np.isfinite(h.a["loss"]).all() and rel_err(h.a["loss"], l.detach().numpy()) < TOL[1]
+    for k, t in (("g_pose", q), ("g_target", target), ("g_comp", comp)):
+        assert rel_err(h.a[k], t.grad.numpy()) < TOL[1], k
+
+
+@pytest.mark.parametrize("mode", [0, 1])
+def test_nan_row_stays_in_its_row(mode, gpis, hand):
+    """A non-finite candidate: the other rows' outputs are bit-identical to a run without it, and it never becomes a
+    best iterate (l < opt_value is false)."""
+    pose0, target0, comp0, noise = _inputs(mode, hand, seed=9, n=3)
+    runs = []
+    for poison in (False, True):
+        h = HostLoop(mode, hand, pose0, target0, comp0)
+        prm, cfg = _params(mode, hand), _opt(_lrs(mode, True))
+        for s in range(3):
+            h.set_gpis(gpis)
+            if poison:
+                for k in ("mean", "gmean", "std"):
+                    h.a[k].reshape(3, -1)[1] = np.nan
+            h.cost(prm, noise[s], s)
+            h.step(prm, cfg, s)
+        h.step(prm, cfg, 3, finalize=1)
+        runs.append(h)
+    clean, bad = runs
+    keep = [0, 2]
+    for k in ("pose", "target", "comp", "g_pose", "g_target", "g_comp", "v_pose", "v_target", "v_comp", "loss",
+              "opt_value", "opt_pose", "opt_target", "opt_comp", "opt_margin"):
+        assert np.array_equal(clean.a[k][keep], bad.a[k][keep]), k
+    assert np.isinf(bad.a["opt_value"][1]) and np.isnan(bad.a["loss"][1])
+    assert np.array_equal(bad.a["opt_pose"][1], pose0[1]) and np.array_equal(bad.a["opt_comp"][1], comp0[1])
+    assert np.isfinite(clean.a["opt_value"]).all()
+
+
+def test_bad_arguments_are_rejected_without_launch(hand):
+    """cdx_gpis_mode_* (libcdx.so, no device touched) and the host entry points: negative E, fingertip counts outside
+    1..CDX_MAX_TIPS, NULL required pointers, mode 1 without a chain or with too many DOFs → CDX_EINVAL; E = 0 is a
+    no-op success."""
+    lib = N.load()
+    h = _lib()
+    prm, cfg, buf = _params(0, hand), _opt((1e-3, 0.0, 0.2)), N.CdxGpisModeBuffers()
+    calls = {
+        "cost": lambda L, ch, p, b, n, t: L("cost")(ch, p, b, n, t, None, 0, 0, *dev(L)),
+        "step": lambda L, ch, p, b, n, t: L("step")(ch, p, cfg, b, n, t, 0, 0, *dev(L)),
+        "iteration": lambda L, ch, p, b, n, t: L("iteration")(ch, p, cfg, b, n, t, None, 0, 0, *dev(L)),
+    }
+    device = lambda name: getattr(lib, "cdx_gpis_mode_" + name)  # noqa: E731
+    hostfn = lambda name: getattr(h, "cdxh_gpis_mode_" + name)  # noqa: E731
+    dev = lambda L: (None,) if L is device else ()  # noqa: E731  (the stream argument)
+    big = N.CdxChain()
+    C.memmove(C.byref(big), C.byref(hand["desc"]), C.sizeof(big))
+    big.n_dofs = N.MAX_DOFS + 1
+    prm1 = _params(1, hand)
+    for L, names in ((device, ("cost", "step", "iteration")), (hostfn, ("cost", "step"))):
+        for name in names:
+            f = calls[name]
+            assert f(L, None, prm, buf, -1, T) == -1, name            # negative E
+            assert f(L, None, prm, buf, 4, 0) == -1, name             # fingertip count
+            assert f(L, None, prm, buf, 4, N.MAX_TIPS + 1) == -1, name
+            assert f(L, None, None, buf, 4, T) == -1, name            # no parameters
+            assert f(L, None, prm, None, 4, T) == -1, name            # no buffers
+            assert f(L, None, prm, buf, 4, T) == -1, name             # NULL required pointers
+            assert f(L, None, prm1, buf, 4, T) == -1, name            # mode 1 without a chain
+            assert f(L, big, prm1, buf, 4, T) == -1, name             # a chain with too many DOFs
+            assert f(L, None, prm, buf, 0, T) == 0, name              # E = 0: nothing to do
+    assert lib.cdx_gpis_mode_step(None, prm, None, buf, 4, T, 0, 0, None) == -1   # no optimiser settings
+    assert lib.cdx_gpis_mode_iteration(None, prm, None, buf, 4, T, None, 0, 0, None) == -1
+    sizes = (C.c_size_t * 3)()
+    lib.cdx_gpis_mode_abi_sizes(sizes)
+    assert list(sizes) == [C.sizeof(N.CdxGpisModeParams), C.sizeof(N.CdxGpisModeOpt), C.sizeof(N.CdxGpisModeBuffers)]

@@ -1,0 +1,272 @@
+"""The fused GPIS / KinGPIS optimiser loops (optimize(..., fused=True): cdx_gpis_mean over [tips; targets],
+cdx_gpis_std over the tips, cdx_gpis_mode_iteration) on the GPU: against the reference's recorded runs, against the
+eager autograd loops past a wave boundary, one launch against two, the best-iterate rule, the on-device noise, a
+runtime fingertip count and the caller's tensors."""
+import numpy as np
+import pytest
+import torch
+
+from tests._helpers import golden, rel_err
+
+pytestmark = pytest.mark.gpu
+
+DEV = "cuda"
+TOL = {"gpis": 1e-6, "kingpis": 1e-5}  # tip space / through the float32 FK (test_other_optimisers_vs_reference)
+INIT_TIP = np.array([[0.05, 0.05, 0.02], [0.06, -0.0, -0.01], [0.03, -0.04, 0.0], [-0.07, -0.01, 0.02]])
+MEAN_TILE = 32  # queries per workgroup of cdx_gpis_mean (optimizers._MEAN_TILE)
+_CACHE = {}
+
+
+def _banana():
+    if "gpis" not in _CACHE:
+        from compliancedex_amd.workloads import stored_gpis
+        _CACHE["gpis"] = stored_gpis("banana", DEV)
+    return _CACHE["gpis"]
+
+
+def _make(mode, iters, optimize_target=True, T=4, seed=0):
+    from compliancedex_amd import GPISGraspOptimizer, KinGPISGraspOptimizer
+    from compliancedex_amd.optimizer import FINGERTIP_LB, FINGERTIP_UB
+    from compliancedex_amd.urdf import load_robot
+    bbox = [FINGERTIP_LB[:3 * T], FINGERTIP_UB[:3 * T]]
+    if mode == "gpis":
+        return GPISGraspOptimizer(bbox, num_iters=iters, optimize_target=optimize_target, seed=seed)
+    cfg = load_robot("allegro")["config"]
+    palm3 = golden("mode_kingpis.npz")["palm3"].tolist()
+    return KinGPISGraspOptimizer("allegro", list(cfg["ee_link_name"])[:T], list(cfg["ee_link_offset"])[:T],
+                                 palm_offset=palm3, num_iters=iters, optimize_target=optimize_target,
+                                 ref_q=cfg["ref_q"], tip_bounding_box=bbox, seed=seed)
+
+
+def _inputs(mode, E, T=4, seed=50):
+    """make_golden.gen_modes's recipe: tips = centre + init_tip + 0.005·randn, targets = centre + 0.003·randn,
+    q = ref_q + 0.05·randn, compliances (10, 10, 10, 20).  From E = 64 on candidate 3 is non-finite (a NaN compliance:
+    its loss, gradients and — after the first step — parameters are NaN in both paths)."""
+    from compliancedex_amd.urdf import load_robot
+    rng = np.random.default_rng(seed)
+    center = golden("mode_gpis.npz")["center"]
+    tips = center + INIT_TIP + 0.005 * rng.standard_normal((E, 4, 3))
+    target = np.tile(center, (E, 4, 1)) + 0.003 * rng.standard_normal((E, 4, 3))
+    comp = np.tile([10.0, 10.0, 10.0, 20.0], (E, 1))
+    if E >= 64:
+        comp[3, 1] = np.nan
+    q = np.asarray(load_robot("allegro")["config"]["ref_q"], dtype=np.float64) + 0.05 * rng.standard_normal((E, 16))
+    dev = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)  # noqa: E731
+    pose = dev(q) if mode == "kingpis" else dev(tips[:, :T])
+    return pose, dev(target[:, :T]), dev(comp[:, :T])
+
+
+def _noise(E, iters, seed=5):
+    g = torch.Generator(device=DEV).manual_seed(seed)
+    return [torch.rand(E, 3, 3, generator=g, device=DEV, dtype=torch.float64) for _ in range(iters)]
+
+
+def _run(mode, E, iters, optimize_target=True, T=4, noise=True, seed=0, **kw):
+    """One optimize call → (loss_rows [iters, E], the three returned tensors, flag, best_loss, last loop state), as
+    numpy; cached by its arguments (the eager and fused E = 67 runs serve several tests)."""
+    key = (mode, E, iters, optimize_target, T, noise, seed, tuple(sorted(kw.items())))
+    if key not in _CACHE:
+        o = _make(mode, iters, optimize_target, T, seed)
+        o._keep_loop_state = True
+        pose, target, comp = _inputs(mode, E, T)
+        out = o.optimize(pose, target, comp, 1, _banana(), verbose=False,
+                         kabsch_noise=_noise(E, iters) if noise else None, trace_rows=True, **kw)
+        rows = torch.stack(o.loss_rows).cpu().numpy()
+        st = getattr(o, "_loop_state", None)
+        state = None if st is None else dict(opt_margin=st.opt_margin.cpu().numpy(),
+                                             margin=[m.cpu().numpy() for m in st.margin])
+        _CACHE[key] = (rows, [x.detach().cpu().numpy() for x in out[:3]], bool(out[3]), o.best_loss.cpu().numpy(), state,
+                       torch.stack(o.loss_history).cpu().numpy())
+    return _CACHE[key]
+
+
+def _same_bits(a, b):
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+@pytest.mark.parametrize("mode", ["gpis", "kingpis"])
+def test_fused_vs_reference(mode):
+    """mode_gpis.npz / mode_kingpis.npz (the reference's own run, E = 6, 12 iterations, its Kabsch noise replayed)
+    through the fused loop: the assertions and tolerances of test_other_optimisers_vs_reference."""
+    d = golden(f"mode_{mode}.npz")
+    assert not bool(d["f32"])
+    iters = int(d["iters"])
+    o = _make(mode, iters)
+    dt = torch.float64
+    pose = torch.from_numpy(d["q" if mode == "kingpis" else "tips"]).to(DEV, dt)
+    target, comp = (torch.from_numpy(d[k]).to(DEV, dt) for k in ("target", "comp"))
+    noise = [torch.from_numpy(n).to(DEV) for n in d["noise"]]
+    out = o.optimize(pose, target, comp, 1, _banana(), verbose=False, kabsch_noise=noise, fused=True)
+    trace = torch.stack(o.loss_history).cpu().numpy()
+    tol = TOL[mode]
+    print("trace err", np.abs(trace - d["loss_trace"]).max() / np.abs(d["loss_trace"]).max())
+    assert np.abs(trace - d["loss_trace"]).max() <= tol * np.abs(d["loss_trace"]).max(), (trace, d["loss_trace"])
+    for i in range(3):
+        err = rel_err(out[i].detach().double().cpu(), d[f"out{i}"])
+        print("out", i, err)
+        assert err < tol, i
+    assert bool(out[3]) == bool(d["flag"])
+
+
+def _compare_paths(mode, E, iters, optimize_target, T=4):
+    ra, oa, fa, ba, _, _ = _run(mode, E, iters, optimize_target, T, fused=True)
+    rb, ob, fb, bb, _, _ = _run(mode, E, iters, optimize_target, T, fused=False)
+    tol = TOL[mode]
+    assert ra.shape == rb.shape == (iters, E)
+    for s in range(iters):  # every candidate: finite rows within tol of the largest, non-finite rows identical
+        fin = np.isfinite(rb[s])
+        assert np.array_equal(np.isfinite(ra[s]), fin), s
+        assert np.array_equal(np.isnan(ra[s]), np.isnan(rb[s])) and np.array_equal(ra[s][~fin], rb[s][~fin],
+                                                                                   equal_nan=True), s
+        # candidate 3, and from iteration 1 on at most the candidates sharing its workgroup of cdx_gpis_mean
+        # (MEAN_TILE queries = MEAN_TILE / T candidates: with N not a multiple of 256 the kernel stages zero-weight padding
+        # points relative to a query of the workgroup, so a NaN query reaches them — in both paths alike)
+        assert fin.sum() >= E - -(-MEAN_TILE // T) and (E < 64 or not fin[3]), s
+        err = np.abs(ra[s][fin] - rb[s][fin]).max() / np.abs(rb[s][fin]).max()
+        print(mode, optimize_target, "iteration", s, "loss err", err, "finite", int(fin.sum()))
+        assert err <= tol, (s, err)
+    for i, (x, y) in enumerate(zip(oa, ob)):
+        err = rel_err(x, y)
+        print(mode, optimize_target, "out", i, err)
+        assert err < tol, i
+    assert fa == fb
+    fin = np.isfinite(bb)
+    assert np.array_equal(np.isfinite(ba), fin) and np.array_equal(ba[~fin], bb[~fin])
+    assert rel_err(ba[fin], bb[fin]) < tol
+
+
+@pytest.mark.parametrize("optimize_target", [True, False])
+@pytest.mark.parametrize("mode", ["gpis", "kingpis"])
+def test_fused_equals_eager_past_a_wave_boundary(mode, optimize_target):
+    """E = 67 (one full wave and a 3-lane tail), 8 iterations, replayed noise: per-candidate per-iteration losses and
+    the returned tensors of the fused loop against the eager autograd loop, 1e-6 (GPIS) / 1e-5 (KinGPIS)."""
+    _compare_paths(mode, 67, 8, optimize_target)
+
+
+@pytest.mark.parametrize("E", [67, 64])
+@pytest.mark.parametrize("mode", ["gpis", "kingpis"])
+def test_one_launch_equals_two(mode, E):
+    """cdx_gpis_mode_iteration (one launch, four fingertips) against cdx_gpis_mode_cost + cdx_gpis_mode_step
+    (split_step=True): bit-identical per-candidate losses, outputs and best losses."""
+    one = _run(mode, E, 8, fused=True)
+    two = _run(mode, E, 8, fused=True, split_step=True)
+    assert _same_bits(one[0], two[0])
+    for x, y in zip(one[1], two[1]):
+        assert _same_bits(x, y)
+    assert one[2] == two[2] and _same_bits(one[3], two[3])
+    assert np.isfinite(one[0]).sum() >= 8 * (E - MEAN_TILE // 4) and np.isnan(one[0][:, 3]).all()
+
+
+@pytest.mark.parametrize("mode", ["gpis", "kingpis"])
+def test_best_iterate_rule(mode):
+    """best_loss is exactly the per-candidate minimum of the loss rows (a non-finite loss never wins), loss_history
+    their per-iteration sums, and `finalize` commits the margin of an improvement made in the LAST iteration: a
+    1-iteration run returns that iteration's margin."""
+    rows, _, _, best, _, hist = _run(mode, 67, 8, fused=True)
+    want = np.where(np.isnan(rows), np.inf, rows).min(axis=0)
+    assert np.array_equal(best, want)
+    assert rel_err(hist, rows.sum(axis=1)) < 1e-12
+    rows1, _, flag1, best1, st, _ = _run(mode, 67, 1, fused=True)
+    assert np.isfinite(rows1[0]).any()  # some candidate improved on +inf
+    assert np.array_equal(st["opt_margin"], st["margin"][0], equal_nan=True)
+    assert np.nanmax(np.abs(st["margin"][0])) > 0
+    assert flag1 == bool((st["margin"][0] > 0).all())
+    assert np.array_equal(best1, np.where(np.isnan(rows1[0]), np.inf, rows1[0]))
+
+
+@pytest.mark.parametrize("mode", ["gpis", "kingpis"])
+def test_on_device_noise_is_keyed_by_the_seed(mode):
+    """kabsch_noise=None: the Kabsch noise is drawn on the device from (seed, row); two optimisers with the same
+    seed agree to the bit, another seed draws other noise."""
+    a = _run(mode, 67, 4, noise=False, seed=11, fused=True)
+    b_ = _make(mode, 4, seed=11)
+    out = b_.optimize(*_inputs(mode, 67), 1, _banana(), verbose=False, kabsch_noise=None, trace_rows=True, fused=True)
+    rows = torch.stack(b_.loss_rows).cpu().numpy()
+    assert _same_bits(a[0], rows)
+    for x, y in zip(a[1], out[:3]):
+        assert _same_bits(x, y.cpu().numpy())
+    assert _same_bits(a[3], b_.best_loss.cpu().numpy())
+    c = _run(mode, 67, 4, noise=False, seed=12, fused=True)
+    assert not _same_bits(a[0], c[0])
+
+
+@pytest.mark.parametrize("mode", ["gpis", "kingpis"])
+def test_three_fingertips(mode):
+    """A runtime fingertip count (three of the Allegro fingertip links: the two-launch path): fused against eager."""
+    _compare_paths(mode, 67, 4, True, T=3)
+
+
+@pytest.mark.parametrize("optimize_target", [True, False])
+@pytest.mark.parametrize("mode", ["gpis", "kingpis"])
+def test_callers_tensors_are_unchanged(mode, optimize_target):
+    """The fused loop works on copies — also of KinGPIS's targets, which it clamps into the box although they are
+    not optimised (the eager loop clamps the caller's tensor in place there, as the reference does)."""
+    o = _make(mode, 3, optimize_target)
+    o._keep_loop_state = True
+    pose, target, comp = _inputs(mode, 67)
+    target[20, 0, 2] = 0.0  # below the box (z ≥ 0.015); (a candidate outside the NaN candidate's cdx_gpis_mean workgroup)
+    keep = [x.clone() for x in (pose, target, comp)]
+    out = o.optimize(pose, target, comp, 1, _banana(), verbose=False, kabsch_noise=_noise(67, 3), fused=True)
+    for x, y in zip((pose, target, comp), keep):
+        assert _same_bits(x.cpu().numpy(), y.cpu().numpy()) and not x.requires_grad  # (bits: candidate 3 holds a NaN)
+    if mode == "kingpis":  # the loop's own copy was clamped (the bounds are float32 tensors)
+        z = float(o._loop_state.target[20, 0, 2])
+        assert z >= float(np.float32(0.015)) and (optimize_target or z == float(np.float32(0.015)))
+    for x in out[:3]:
+        assert all(x.data_ptr() != y.data_ptr() for y in (pose, target, comp))
+
+
+@pytest.mark.parametrize("kernel", ["rbf", "joint"])
+@pytest.mark.parametrize("mode", ["gpis", "kingpis"])
+def test_other_gpis_kernels(mode, kernel):
+    """The fused loop reads the GPIS only through native_state(): an RBF and a joint (0.3·RBF + 0.7·TPS) surface
+    fitted on the small box (workloads.box_arrays), E = 6, 4 iterations, fused against eager at the same tolerances."""
+    from compliancedex_amd import GPIS
+    from compliancedex_amd.workloads import box_arrays
+    X1, y, nz = box_arrays(n_surface=100)
+    g = GPIS(0.08, 1.0, kernel=kernel)
+    g.fit(torch.from_numpy(X1).to(DEV), torch.from_numpy(y).to(DEV), noise=torch.from_numpy(nz).to(DEV))
+    g.bias = torch.tensor(1.0, dtype=torch.float64, device=DEV)
+    res = []
+    for fused in (True, False):
+        o = _make(mode, 4)
+        out = o.optimize(*_inputs(mode, 6), 1, g, verbose=False, kabsch_noise=_noise(6, 4), trace_rows=True, fused=fused)
+        res.append((torch.stack(o.loss_rows).cpu().numpy(), [x.detach().cpu().numpy() for x in out[:3]]))
+    (ra, oa), (rb, ob) = res
+    assert np.isfinite(rb).all() and rel_err(ra, rb) < TOL[mode]
+    for x, y_ in zip(oa, ob):
+        assert rel_err(x, y_) < TOL[mode]
+
+
+def test_deep_chain_fused_equals_eager():
+    """KinGPIS on the arm + hand chain (iiwa7_allegro, 23 DOFs, fingertips deeper than 8 levels: the kernel's deep-chain
+    instantiation, whose FK backward is the closed form without per-level state), config 4's inputs at E = 6: fused
+    against eager (cdx_fk_backward through autograd) at the KinGPIS tolerance."""
+    from compliancedex_amd import KinGPISGraspOptimizer
+    from compliancedex_amd.optimizer import FINGERTIP_LB, FINGERTIP_UB
+    from compliancedex_amd.workloads import config4_kin_inputs
+    links, offs, palm, q, target, comp = config4_kin_inputs(6, device=DEV)
+    res = []
+    for fused in (True, False):
+        o = KinGPISGraspOptimizer("iiwa7_allegro", links, offs, palm_offset=palm.astype(np.float64).tolist(), num_iters=4,
+                                  optimize_target=True, ref_q=[0.0] * 23, tip_bounding_box=[FINGERTIP_LB, FINGERTIP_UB])
+        args = [torch.from_numpy(np.ascontiguousarray(a)).to(DEV).double() for a in (q, target, comp)]
+        out = o.optimize(*args, 1, _banana(), verbose=False, kabsch_noise=_noise(6, 4), trace_rows=True, fused=fused)
+        res.append((torch.stack(o.loss_rows).cpu().numpy(), [x.detach().cpu().numpy() for x in out[:3]]))
+    (ra, oa), (rb, ob) = res
+    assert np.isfinite(rb).all() and rel_err(ra, rb) < TOL["kingpis"], rel_err(ra, rb)
+    for x, y in zip(oa, ob):
+        assert rel_err(x, y) < TOL["kingpis"]
+
+
+def test_fused_needs_float64_device_tensors():
+    o = _make("gpis", 1)
+    pose, target, comp = _inputs("gpis", 4)
+    with pytest.raises(ValueError, match="float64"):
+        o.optimize(pose.float(), target, comp, 1, _banana(), verbose=False, fused=True)
+    with pytest.raises(RuntimeError, match="no CPU path"):
+        o.optimize(pose.cpu(), target, comp, 1, _banana(), verbose=False, fused=True)
+    k = _make("kingpis", 1)
+    q, target, comp = _inputs("kingpis", 4)
+    with pytest.raises(ValueError, match="float64"):
+        k.optimize(q, target, comp.float(), 1, _banana(), verbose=False, fused=True)
