@@ -21,6 +21,7 @@ ARCH = os.environ.get("CDX_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["cdx_gpis.hip", "cdx_screen.hip", "cdx_fit.hip", "cdx_closure.hip", "cdx_sdf.hip", "cdx_optim.hip", "cdx_exchange.hip", "cdx_kin.hip",
                "cdx_gpis_mode.hip"]
+FP_CONTRACT_OFF = ("cdx_sdf.hip", "cdx_closure.hip", "cdx_kin.hip", "cdx_gpis_mode.hip")  # see build_device
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 
 
@@ -40,8 +41,9 @@ def _deps():
     return [os.path.join(CSRC, f) for f in os.listdir(CSRC)] + [os.path.join(REPO, "include", "cdx.h")]
 
 
-# Tuning switches compiled into the product library.
-DEFAULT_DEFINES = ("CDX_FAST_SQRT", "CDX_STD_SCHED", "CDX_MEAN_RSQ32")
+# -D switches of the product library: none, the sources compile to the product as they stand.  The name stays for
+# the diagnostic builds of tools/, which add theirs to it (DESIGN.md §2a lists every macro the sources test).
+DEFAULT_DEFINES = ()
 
 
 def source_digest(defines=DEFAULT_DEFINES):
@@ -93,7 +95,7 @@ def build_device(force=False, defines=DEFAULT_DEFINES, out_name="libcdx.so"):
         # no FMA contraction in the per-candidate code (FK, Kabsch, costs) and TorchSDF: the
         # device then rounds like the reference's CPU float ops and like libcdx_host.so (the
         # collision cost's 1/d near the floor amplifies a contracted f32 FK to 1e-4)
-        if src in ("cdx_sdf.hip", "cdx_closure.hip", "cdx_kin.hip", "cdx_gpis_mode.hip"):
+        if src in FP_CONTRACT_OFF:
             flags.append("-ffp-contract=off")
         cmds.append([HIPCC, *flags, "-c", os.path.join(CSRC, src), "-o", obj])
         objs.append(obj)

@@ -264,11 +264,6 @@ __global__ __launch_bounds__(64) void closure_level_kernel(cdx_problem P, int64_
                                                            GpisView gv, double* __restrict__ lvl,
                                                            int32_t* __restrict__ flip,
                                                            const double* __restrict__ krot) {
-#if defined(CDX_LEVEL_PRIO)
-  // latency-bound dependent chains: issue first whenever ready, so that the GPIS mean's part B on
-  // the side stream (CDX_MEAN_SPLIT) fills the issue slots the chains leave without stretching them
-  __builtin_amdgcn_s_setprio(CDX_LEVEL_PRIO);
-#endif
   const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   const int K = P.n_levels;
   if (t >= K * E) return;
@@ -367,10 +362,7 @@ __global__ __launch_bounds__(64) void closure_kabsch_kernel(cdx_problem P, int64
 // w_k·(l_k + uncertainty·log(100·std)) and, through the all-tip interpolation a = target + c·(tip −
 // target), c·g and g − c·g of g = w_k·uncertainty/std·∇std into the tip and target gradients; ∇std
 // summed from the pass's pieces here when folded (once per distinct level, by that fingertip's lane).
-#if !defined(CDX_COMBINE_BLOCK)
-#define CDX_COMBINE_BLOCK 64
-#endif
-constexpr int COMBINE_BLOCK = CDX_COMBINE_BLOCK;  // 64: E = 4096 spreads over 256 workgroups, one per CU
+constexpr int COMBINE_BLOCK = 64;  // E = 4096 spreads over 256 workgroups, one per CU
 template <int GS, int MAXD, bool VL = false>
 __global__ __launch_bounds__(COMBINE_BLOCK) void closure_combine_kernel(
     cdx_problem P, int64_t E, const double* __restrict__ q, const double* __restrict__ palm_pos,
@@ -447,17 +439,8 @@ __global__ __launch_bounds__(COMBINE_BLOCK) void closure_combine_kernel(
   if (live) {
     // the chain read in place from the kernel-argument segment (P is the first argument, at offset 0)
     const cdx_chain& kc = (*(const cdx_problem*)(__builtin_amdgcn_kernarg_segment_ptr())).chain;
-#if defined(CDX_COMBINE_FK_BWD1)  // (A/B: the stored-rotations backward walk)
-    cdx::fk_tip_bwd<MAXD>(kc, f, cdx::QRowD{q + ec * D}, gtl, [&](int d, float v) { gcon[d][tid] += v; }, tl);
-#elif defined(CDX_COMBINE_FK_BWD3R)  // (A/B: round 5 — one unrolled walk in registers for the hands, two walks for deep
-                                     // chains)
-    if constexpr (MAXD <= 8)
-      cdx::fk_tip_bwd3<MAXD>(kc, f, cdx::QRowD{q + ec * D}, gtl, [&](int d, float v) { gcon[d][tid] += v; }, tl);
-    else
-      cdx::fk_tip_bwd2<MAXD>(kc, f, cdx::QRowD{q + ec * D}, gtl, [&](int d, float v) { gcon[d][tid] += v; }, tl);
-#elif !defined(CDX_COMBINE_DIAG_NOFK)  // (timing-only diagnostic build without the FK backward: outputs wrong)
-    // one rolled walk, the joints' axes and origins in LDS, then the per-joint products (fk_tip_bwd3's arithmetic;
-    // deep chains no longer walk twice)
+#if !defined(CDX_COMBINE_DIAG_NOFK)  // (timing-only diagnostic build without the FK backward: outputs wrong)
+    // one rolled walk, the joints' axes and origins in LDS, then the per-joint products
     __shared__ float s_cst[6 * MAXD * COMBINE_BLOCK];
     float R[9], t[3];
     cdx::fk_tip_walk3s(kc, f, cdx::QRowD{q + ec * D}, R, t,
@@ -586,9 +569,6 @@ bool fork_mean() {
 constexpr int64_t SCREEN_MIN_ROWS = 4096;
 
 bool screen_on(const cdx_problem* p, int64_t E) {
-#if defined(CDX_GRAD_EXPLICIT)
-  return false;  // the screened path keeps V for the ∇std pass, which this build does not allocate
-#endif
   static const bool off = cdx::ab_env("CDX_NO_SCREEN") != nullptr;
   const int64_t Ms = (int64_t)p->n_query_levels * E * p->chain.n_tips;
   return !off && p->gpis.screen && p->gpis.screen_delta > 0 && p->chain.n_tips <= CDX_MAX_TIPS &&
@@ -629,11 +609,7 @@ ClosureWs closure_ws_layout(const cdx_problem* p, int64_t E, char* base) {
   w.refine_ws = scr ? take(cdx::gpis_refine_ws_bytes(p->gpis, Ms)) : nullptr;
   w.lvl = (double*)take((size_t)p->n_levels * E * level_record_width(p->chain.n_tips) * sizeof(double));
   w.krot = scr ? (double*)take((size_t)p->n_levels * E * cdx::ForceEq<0>::KABSCH_RECORD * sizeof(double)) : nullptr;
-#if !defined(CDX_GRAD_EXPLICIT)
   w.V = (double*)take(cdx::gpis_v_bytes(p->gpis, Ms));
-#else
-  w.V = nullptr;
-#endif
   w.bytes = off;
   return w;
 }

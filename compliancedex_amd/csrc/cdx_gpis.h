@@ -13,7 +13,7 @@ namespace cdx {
 // a clamped r² ≥ 1e-200 never needs); r² = 0 returns 1e-100, harmless in every use here
 // (k(1e-100) = k(0) to 1e-200, and ∂k/∂x carries a factor (x − x_j) = 0).
 CDX_HD double sqrt_r2(double x) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(CDX_FAST_SQRT)
+#if defined(__HIP_DEVICE_COMPILE__)
   x = fmax(x, 1e-200);
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;
@@ -30,12 +30,9 @@ CDX_HD double sqrt_r2(double x) {
 }
 
 // sqrt_r2 without its final Newton correction (≤ 1 ulp from the rounded root): the whitened
-// pass's on-chip K* generation (CDX_GEN_SQRT_FULL keeps the full sequence there).
-CDX_HD double sqrt_r2_f32seed(double x);
+// pass's on-chip K* generation.
 CDX_HD double sqrt_r2_gen(double x) {
-#if defined(__HIP_DEVICE_COMPILE__) && defined(CDX_GEN_RSQ32)  // A/B: the f32-seeded root (≈ 2⁻⁴⁵) in K* too
-  return sqrt_r2_f32seed(x);
-#elif defined(__HIP_DEVICE_COMPILE__) && defined(CDX_FAST_SQRT) && !defined(CDX_GEN_SQRT_FULL)
+#if defined(__HIP_DEVICE_COMPILE__)
   x = fmax(x, 1e-200);
   const double y = __builtin_amdgcn_rsq(x);
   double g = x * y, h = 0.5 * y;
@@ -51,7 +48,7 @@ CDX_HD double sqrt_r2_gen(double x) {
 
 // sqrt(x) from an f32 reciprocal-root seed and one f64 Newton step (relative error ≈ 2⁻⁴⁵, 1e-14; against
 // ≤ 1 ulp for sqrt_r2_gen): the f32 transcendental and the two conversions replace v_rsq_f64 and the
-// Goldschmidt refinement — the GPIS mean's per-pair root (CDX_MEAN_RSQ32 builds).
+// Goldschmidt refinement — the GPIS mean's per-pair root.
 CDX_HD double sqrt_r2_f32seed(double x) {
 #if defined(__HIP_DEVICE_COMPILE__)
   const float xf = fmaxf((float)x, 1e-30f);

@@ -41,11 +41,7 @@ namespace {
 // 32 queries × 8 lanes per workgroup since the moment form (fewer VALU ops per pair, so the
 // staging and barriers per pair matter more): 0.095 ms against 0.101 for 16 × 16 and 64 × 4 at
 // 53 248 queries (profiles/r02zd_mean_layout_ab.txt).
-#ifndef CDX_MEAN_Q  // A/B switches (tools/mean_variants.sh); MEAN_Q · MEAN_SPLIT = 256
-#define CDX_MEAN_Q 32
-#define CDX_MEAN_SPLIT 8
-#endif
-constexpr int MEAN_Q = CDX_MEAN_Q, MEAN_SPLIT = CDX_MEAN_SPLIT, MEAN_BLOCK = MEAN_Q * MEAN_SPLIT;
+constexpr int MEAN_Q = 32, MEAN_SPLIT = 8, MEAN_BLOCK = MEAN_Q * MEAN_SPLIT;
 static_assert(MEAN_BLOCK == 256, "the mean kernel's moment reduction assumes 4 waves");
 
 // TPS mean in moment form.  With k = 2r³ − 3Rr² + R³ and ∇k = 6(r − R)(x − x_n):
@@ -55,8 +51,8 @@ static_assert(MEAN_BLOCK == 256, "the mean kernel's moment reduction assumes 4 w
 // (p̃ = x_n − c, x̃ = x − c, c = the first inducing point, so both stay at the object's scale):
 //   Σ α r² = |x̃|² S0 − 2 x̃·S1 + S2,   Σ α (x − x_n) = x̃ S0 − S1.
 // Per pair only r, αr, Σ (αr) r² and Σ (αr) d remain: 17 f64 ops + v_rsq against 23 + v_rsq (r
-// without the root's final Newton correction, ≤ 1 ulp, as the whitened pass's K* generation).  The product
-// build (CDX_MEAN_RSQ32) seeds the root in f32 and takes one f64 Newton step (2⁻⁴⁵ relative, 3 DP ops fewer
+// without the root's final Newton correction, ≤ 1 ulp, as the whitened pass's K* generation).  The root
+// is seeded in f32 and takes one f64 Newton step (2⁻⁴⁵ relative, 3 DP ops fewer
 // per pair): the mean is DP-issue-bound beside the refine pass, and the closure runs ≈ 10 µs faster (4
 // interleaved A/Bs, profiles/r04cde_ab_*.jsonl, r04g_ab_roots.jsonl) while the mean moves by ≤ 6e-13 relative —
 // below its own distance from the reference's f64 autograd (1.3e-12 on the banana state, 2.3e-13 on the
@@ -85,21 +81,12 @@ __device__ __forceinline__ void mean_tps_moments(const cdx_gpis& g, int64_t M, i
     }
     sp[tid] = v;
     __syncthreads();
-#ifndef CDX_MEAN_UNROLL
-#define CDX_MEAN_UNROLL 4
-#endif
-#pragma unroll CDX_MEAN_UNROLL
+#pragma unroll 4
     for (int jj = split; jj < MEAN_BLOCK; jj += MEAN_SPLIT) {
       const dbl4 p = sp[jj];
       const double dx = x0 - p.x, dy = x1 - p.y, dz = x2 - p.z;
       const double r2 = dx * dx + dy * dy + dz * dz;
-#if defined(CDX_MEAN_RSQ32)  // (product build) f32 seed + one f64 Newton step (≈ 2⁻⁴⁵ relative), see below
-      const double ar = p.w * cdx::sqrt_r2_f32seed(r2);
-#elif !defined(CDX_MEAN_FULLSQRT)  // the root without its final Newton correction (≤ 1 ulp), as the K* generation
-      const double ar = p.w * cdx::sqrt_r2_gen(r2);
-#else
-      const double ar = p.w * cdx::sqrt_r2(r2);
-#endif
+      const double ar = p.w * cdx::sqrt_r2_f32seed(r2);  // f32 seed + one f64 Newton step (≈ 2⁻⁴⁵ relative)
       a3 += ar * r2;
       h0 += ar * dx;
       h1 += ar * dy;
@@ -151,123 +138,6 @@ __device__ __forceinline__ void mean_tps_moments(const cdx_gpis& g, int64_t M, i
   }
 }
 
-// Register-blocked TPS moment form (A/B switch CDX_MEAN_QPT > 1, off): each thread carries MQ_QPT queries, so
-// one LDS read of a staged point serves MQ_QPT pairs; MQ_SPLIT lanes share a query group's points.  Same staging,
-// moments and epilogue as mean_tps_moments.  Measured slower in the closure (round 5, profiles/r05i_*: the
-// mean 85 → 92 µs at 4 queries per thread, 90 µs at 2): the loop is f64-VALU-bound, not LDS-bound, and the
-// extra accumulators cost occupancy.
-#ifndef CDX_MEAN_QPT
-#define CDX_MEAN_QPT 1
-#endif
-#ifndef CDX_MEAN_QSPLIT
-#define CDX_MEAN_QSPLIT 16
-#endif
-constexpr int MQ_QPT = CDX_MEAN_QPT, MQ_SPLIT = CDX_MEAN_QSPLIT;
-constexpr int MQ_PER_WG = (MEAN_BLOCK / MQ_SPLIT) * MQ_QPT;  // queries per workgroup
-__global__ __launch_bounds__(MEAN_BLOCK) void gpis_mean_tps_blocked_kernel(cdx_gpis g, const double* __restrict__ X,
-                                                                           int64_t M, double* __restrict__ mean,
-                                                                           double* __restrict__ gmean,
-                                                                           double* __restrict__ normal) {
-  __shared__ dbl4 sp[MEAN_BLOCK];
-  const int tid = threadIdx.x;
-  const int split = tid % MQ_SPLIT;
-  const int64_t m0 = ((int64_t)blockIdx.x * (MEAN_BLOCK / MQ_SPLIT) + tid / MQ_SPLIT) * MQ_QPT;
-  double xq[MQ_QPT][3];
-#pragma unroll
-  for (int q = 0; q < MQ_QPT; ++q) {
-    const int64_t m = m0 + q;
-    for (int i = 0; i < 3; ++i) xq[q][i] = m < M ? X[3 * m + i] : 0.0;
-  }
-  const double c0 = g.X1[0], c1 = g.X1[1], c2 = g.X1[2];
-  double a3[MQ_QPT], h0[MQ_QPT], h1[MQ_QPT], h2[MQ_QPT];
-#pragma unroll
-  for (int q = 0; q < MQ_QPT; ++q) a3[q] = h0[q] = h1[q] = h2[q] = 0.0;
-  double s0 = 0, s1x = 0, s1y = 0, s1z = 0, s2 = 0;
-  for (int j0 = 0; j0 < g.N; j0 += MEAN_BLOCK) {
-    const int j = j0 + tid;
-    __syncthreads();
-    dbl4 v;
-    if (j < g.N) {
-      v.x = g.X1[3 * j]; v.y = g.X1[3 * j + 1]; v.z = g.X1[3 * j + 2]; v.w = g.alpha[j];
-      const double px = v.x - c0, py = v.y - c1, pz = v.z - c2;
-      s0 += v.w;
-      s1x += v.w * px; s1y += v.w * py; s1z += v.w * pz;
-      s2 += v.w * (px * px + py * py + pz * pz);
-    } else {
-      v.x = xq[0][0] + 1.0; v.y = v.z = 0.0; v.w = 0.0;  // any finite point; α = 0
-    }
-    sp[tid] = v;
-    __syncthreads();
-#pragma unroll 2
-    for (int jj = split; jj < MEAN_BLOCK; jj += MQ_SPLIT) {
-      const dbl4 p = sp[jj];
-#pragma unroll
-      for (int q = 0; q < MQ_QPT; ++q) {
-        const double dx = xq[q][0] - p.x, dy = xq[q][1] - p.y, dz = xq[q][2] - p.z;
-        const double r2 = dx * dx + dy * dy + dz * dz;
-#if defined(CDX_MEAN_RSQ32)
-        const double ar = p.w * cdx::sqrt_r2_f32seed(r2);
-#else
-        const double ar = p.w * cdx::sqrt_r2_gen(r2);
-#endif
-        a3[q] += ar * r2;
-        h0[q] += ar * dx;
-        h1[q] += ar * dy;
-        h2[q] += ar * dz;
-      }
-    }
-  }
-#pragma unroll
-  for (int q = 0; q < MQ_QPT; ++q)
-#pragma unroll
-    for (int w = 1; w < MQ_SPLIT; w <<= 1) {
-      a3[q] += __shfl_xor(a3[q], w);
-      h0[q] += __shfl_xor(h0[q], w);
-      h1[q] += __shfl_xor(h1[q], w);
-      h2[q] += __shfl_xor(h2[q], w);
-    }
-#pragma unroll
-  for (int w = 1; w < 64; w <<= 1) {
-    s0 += __shfl_xor(s0, w);
-    s1x += __shfl_xor(s1x, w);
-    s1y += __shfl_xor(s1y, w);
-    s1z += __shfl_xor(s1z, w);
-    s2 += __shfl_xor(s2, w);
-  }
-  __syncthreads();
-  double* red = reinterpret_cast<double*>(sp);
-  const int wave = tid >> 6;
-  if ((tid & 63) == 0) {
-    red[wave * 5 + 0] = s0; red[wave * 5 + 1] = s1x; red[wave * 5 + 2] = s1y; red[wave * 5 + 3] = s1z;
-    red[wave * 5 + 4] = s2;
-  }
-  __syncthreads();
-  s0 = s1x = s1y = s1z = s2 = 0;
-#pragma unroll
-  for (int w = 0; w < MEAN_BLOCK / 64; ++w) {
-    s0 += red[w * 5 + 0]; s1x += red[w * 5 + 1]; s1y += red[w * 5 + 2]; s1z += red[w * 5 + 3];
-    s2 += red[w * 5 + 4];
-  }
-  if (split != 0) return;
-  const double R = g.R;
-#pragma unroll
-  for (int q = 0; q < MQ_QPT; ++q) {
-    const int64_t m = m0 + q;
-    if (m >= M) break;
-    const double qx = xq[q][0] - c0, qy = xq[q][1] - c1, qz = xq[q][2] - c2;
-    const double sr2 = (qx * qx + qy * qy + qz * qz) * s0 - 2.0 * (qx * s1x + qy * s1y + qz * s1z) + s2;
-    mean[m] = 2.0 * a3[q] - 3.0 * R * sr2 + R * R * R * s0 + g.bias;
-    const double gx = 6.0 * h0[q] - 6.0 * R * (qx * s0 - s1x);
-    const double gy = 6.0 * h1[q] - 6.0 * R * (qy * s0 - s1y);
-    const double gz = 6.0 * h2[q] - 6.0 * R * (qz * s0 - s1z);
-    if (gmean) { gmean[3 * m] = gx; gmean[3 * m + 1] = gy; gmean[3 * m + 2] = gz; }
-    if (normal) {
-      const double nn = sqrt(gx * gx + gy * gy + gz * gz) + 1e-8;
-      normal[3 * m] = gx / nn; normal[3 * m + 1] = gy / nn; normal[3 * m + 2] = gz / nn;
-    }
-  }
-}
-
 template <int KT>
 __global__ __launch_bounds__(MEAN_BLOCK) void gpis_mean_kernel(cdx_gpis g, const double* __restrict__ X, int64_t M,
                                                                double* __restrict__ mean, double* __restrict__ gmean,
@@ -280,12 +150,10 @@ __global__ __launch_bounds__(MEAN_BLOCK) void gpis_mean_kernel(cdx_gpis g, const
   if (m < M) { x0 = X[3 * m]; x1 = X[3 * m + 1]; x2 = X[3 * m + 2]; }
   const double R = g.R, inv_s2 = 1.0 / (g.sigma * g.sigma);
   double acc = 0, g0 = 0, g1 = 0, g2 = 0;
-#ifndef CDX_MEAN_DIRECT  // A/B switch: the per-pair k / ∇k form for TPS too
   if constexpr (KT == CDX_KERNEL_TPS) {
     mean_tps_moments(g, M, m, x0, x1, x2, mean, gmean, normal, sp);
     return;
   }
-#endif
   for (int j0 = 0; j0 < g.N; j0 += MEAN_BLOCK) {
     const int j = j0 + tid;
     __syncthreads();
@@ -375,76 +243,29 @@ typedef double dbl2v __attribute__((ext_vector_type(2)));
 //   cut into gridDim.x equal pieces of the concatenated K-sequence of all (query tile, stripe)
 //   pairs: a piece's segments that cover a whole stripe finish their epilogue in place, a stripe
 //   cut by piece boundaries leaves partial V tiles in rl.slots (slot 0: the piece's first segment,
-//   1: its last) that gpis_var_merge sums in piece order.  (CDX_MERGE_FUSED instead lets the last of a
-//   unit's pieces to finish — a per-unit arrival counter — sum them, in the same order: bit-identical,
-//   but 1.22 vs 1.11 ms per closure, profiles/r03f_merge_fused_ab.jsonl: the agent-scope release
-//   fence each cut piece needs writes back its XCD's whole L2.)
+//   1: its last) that gpis_var_merge sums in piece order.
 enum { MODE_GRAD = 0, MODE_VAR = 1, MODE_GRADV = 2, MODE_VARL = 3 };
 
-// Streaming V (A/B switches): CDX_NT_VSTORE stores V rows and the refine's partial tiles non-temporally,
-// CDX_NT_VLOAD loads the ∇std pass's V rows non-temporally — streamed once, they then do not evict the
-// L⁻ᵀ / L⁻¹ stripes each XCD's L2 re-reads for every query tile.
-template <class T>
-__device__ __forceinline__ void v_store(T* p, T v) {
-#if defined(CDX_NT_VSTORE)
-  __builtin_nontemporal_store(v, p);
-#else
-  *p = v;
-#endif
-}
 // A wave's 64×64 sub-tile of V (acc[i][j][r] = D[row (l>>4) + 4r][col (l&15) + 16j] in block (i, j)) to
-// row-major dst (leading dimension ld, even column offset): with CDX_VSTORE_X4 the lane pairs (l, l^1)
-// trade one value per two rows (two xor-1 shuffles) so each stores two adjacent columns of two rows as
-// 16-byte stores — half the store instructions of the plain 8-byte-per-lane form, same bytes and values.
+// row-major dst (leading dimension ld).
 template <class ACC>
 __device__ __forceinline__ void store_v_tile(double* dst, int64_t ld, const ACC& acc, int lane) {
-#if defined(CDX_VSTORE_X4)
-  const bool even = (lane & 1) == 0;
-  const int c0 = (lane & 15) & ~1;
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const double a0 = acc[i][j][0], a1 = acc[i][j][1], a2 = acc[i][j][2], a3 = acc[i][j][3];
-      const double x0 = __shfl_xor(even ? a1 : a0, 1), x1 = __shfl_xor(even ? a3 : a2, 1);
-      // even lane: rows r = 0, 2 (own value, partner's); odd lane: rows r = 1, 3 (partner's, own value)
-      const int ra = even ? 0 : 1, rb = even ? 2 : 3;
-      const double2 va = even ? make_double2(a0, x0) : make_double2(x0, a1);
-      const double2 vb = even ? make_double2(a2, x1) : make_double2(x1, a3);
-      double* base = dst + (int64_t)(16 * i + (lane >> 4)) * ld + 16 * j + c0;
-      v_store(reinterpret_cast<double2*>(base + (int64_t)(4 * ra) * ld), va);
-      v_store(reinterpret_cast<double2*>(base + (int64_t)(4 * rb) * ld), vb);
-    }
-#else
 #pragma unroll
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       double* vr = dst + (int64_t)(16 * i + (lane >> 4) + 4 * r) * ld + (lane & 15);
 #pragma unroll
-      for (int j = 0; j < 4; ++j) v_store(vr + 16 * j, acc[i][j][r]);
+      for (int j = 0; j < 4; ++j) vr[16 * j] = acc[i][j][r];
     }
-#endif
-}
-
-template <class T>
-__device__ __forceinline__ T v_load(const T* p) {
-#if defined(CDX_NT_VLOAD)
-  return __builtin_nontemporal_load(p);
-#else
-  return *p;
-#endif
 }
 
 constexpr int RC_MAX_NT = 16;  // stripes with host unit costs (N_pad ≤ 4096); beyond: equal K-step cuts
-static_assert(RC_MAX_NT == cdx::GC_MAX_NT, "the ∇std pass's stripe costs travel in RefineList::uc");
 struct RefineList {
   const int* rows;    // query index per list position (null: the identity)
   const int* extra;   // device count of positions past the G primary ones (nullable: 0)
   int G;
   double* slots;      // [gridDim.x][2][ST_BM][ST_BN] partial V tiles of cut stripes
-  int* cnt;           // [Nt][mt_cap] arrival counters of cut units (zero between launches)
-  int mt_cap;         // query tiles the list can hold
   int64_t* cuts;      // [gridDim.x + 1] piece bounds in the K-sequence (written by the refine kernel)
   int n_uc;           // stripes with unit costs below (= N_pad/256), 0: equal K-step cuts
   int64_t uc[RC_MAX_NT];  // cost of one (stripe, query tile) unit per stripe (var_unit_cost, host)
@@ -457,19 +278,6 @@ __device__ inline int64_t refine_rows(const RefineList& rl) {
   if (rl.gate && !cdx::screen_failed(rl.gate)) return 0;
   return (int64_t)rl.G + (rl.extra ? *rl.extra : 0);
 }
-
-// Whitened pass A operand: K* generated on chip per stripe (default), or read from a buffer
-// gpis_kstar_kernel wrote (CDX_VAR_KLOAD).  On chip, each K* entry is regenerated by every stripe
-// that needs its row (Σ_nt K-steps = 4.4× the unique ones at N = 2000) and its ≈ 16 f64 VALU ops
-// share the DP pipe with the f64 MFMA.  Measured (profiles/r01zi_var_kload_ab.jsonl): the buffer
-// makes the std kernel 3 % faster (1.185 → 1.152 ms) but the closure 3 % slower (2.35 → 2.27 M
-// evals/s): the 268 MB K* write plus its re-reads slow the K* kernel, mean and ∇std passes more.
-#if defined(CDX_VAR_KLOAD)
-constexpr bool VAR_KLOAD = true;
-#else
-constexpr bool VAR_KLOAD = false;
-#endif
-
 
 // K-range [lo, hi) of stripe nt in the triangular modes.
 __device__ __host__ inline void stripe_k_range(int mode, int nt, int N, int& lo, int& hi) {
@@ -531,16 +339,12 @@ __device__ inline int refine_piece(int b, int G, int pieces) {
 // Cost-balanced cuts of the refine sequence.  A K-step's time is not uniform: in the last 16–20 K-steps
 // of a unit (the stripe's diagonal block) the waves past their own columns skip their MFMAs, so the
 // light stripes' short units are cheaper per K-step.  Measured per piece (CDX_DIAG_WGTIME build,
-// tools/refine_pieces.py, profiles/r03v_refine_pieces.json): time ≈ 2.8 µs per K-step + 0.27 µs per
+// tools/refine_pieces.py, profiles/r03zd_refine_pieces.json): time ≈ 2.8 µs per K-step + 0.27 µs per
 // 16-column MFMA block of the busiest SIMD (8 in a full step); equal K-step cuts left the heavy-stripe
 // pieces 366 µs against 295 µs for the light ones (end times 292 … 385 µs).  The cuts balance
 // RC_FIX + RC_BLK·blocks per K-step instead (integer costs: the same cuts on every workgroup and in the
-// merge); CDX_REFINE_UNIFORM builds the equal-K-step cuts for the A/B.
-#if defined(CDX_REFINE_UNIFORM)
-constexpr int RC_FIX = 1, RC_BLK = 0;
-#else
+// merge).
 constexpr int RC_FIX = 21, RC_BLK = 2;
-#endif
 // MFMA blocks (16 columns × one wave) of the busiest SIMD in K-step s of a stripe-nt unit: wave cwave c
 // (columns 64c … 64c+63 of the stripe, shifted by vsh) issues 4 blocks up to its diagonal block, then
 // 3, 2, 1, 0 (gpis_std_kernel's VAR step variants); SIMDs hold the column waves (c, 3 − c).
@@ -666,7 +470,7 @@ __device__ inline void refine_merge_unit(const cdx_gpis& g, const RefineList& rl
       sq[rr] = 0.0;
 #pragma unroll
       for (int c = 0; c < 4; ++c) {
-        v_store(dst + c, v[rr][c]);
+        dst[c] = v[rr][c];
         sq[rr] = fma(v[rr][c], v[rr][c], sq[rr]);
       }
     }
@@ -703,7 +507,7 @@ __global__ __launch_bounds__(ST_THREADS, 2) void gpis_std_kernel(cdx_gpis g, con
   constexpr bool LIST = MODE == MODE_VARL;
   constexpr bool VAR = MODE == MODE_VAR || LIST;
   constexpr bool TRI = MODE != MODE_GRAD;
-  constexpr bool GEN = MODE == MODE_GRAD || (VAR && !VAR_KLOAD);  // A tile generated on chip (else loaded from vin)
+  constexpr bool GEN = MODE != MODE_GRADV;  // A tile generated on chip (GRADV: V rows loaded from vin)
   __shared__ __attribute__((aligned(16))) double smem[ST_SMEM];
   double* xq = smem + ST_NBUF * (ST_TILE + ST_BTILE);
   double* xs = xq + ST_BM * 3;  // [2][ST_XS]: X1 rows of the stage generated next
@@ -768,9 +572,9 @@ __global__ __launch_bounds__(ST_THREADS, 2) void gpis_std_kernel(cdx_gpis g, con
       av[i] = (!VAR || n0 != 0 || ac + i * BSTR >= vsh) ? src[i * (BSTR / 2)] : dbl2v{0.0, 0.0};
 #endif
     }
-    if (!GEN) {  // GRADV: V at shifted columns; VAR: K* rows
+    if (!GEN) {  // GRADV: V at shifted columns
 #pragma unroll
-      for (int i = 0; i < GEN_PER; ++i) kv[i] = v_load(vrow + kb + gk + i + (VAR ? 0 : vsh));
+      for (int i = 0; i < GEN_PER; ++i) kv[i] = *(vrow + kb + gk + i + vsh);
     }
   };
   auto gen = [&](const double* x1, int i) {  // K* entry (gm, gk + i) from the X1 rows at x1
@@ -864,7 +668,6 @@ __global__ __launch_bounds__(ST_THREADS, 2) void gpis_std_kernel(cdx_gpis g, con
           if (kk == 8) gen(x1, 3);
         }
         if (kk == 8) stage_write(wb);
-#if defined(CDX_STD_SCHED)
         if constexpr (JHI > JLO) {
           __builtin_amdgcn_sched_group_barrier(0x100, 8, 0);  // next fragments first
 #pragma unroll
@@ -873,7 +676,6 @@ __global__ __launch_bounds__(ST_THREADS, 2) void gpis_std_kernel(cdx_gpis g, con
             __builtin_amdgcn_sched_group_barrier(0x002, 4, 0);  // then up to four VALU
           }
         }
-#endif
       }
     };
     kstep(jlo_s, jhi_s);
@@ -894,21 +696,15 @@ __global__ __launch_bounds__(ST_THREADS, 2) void gpis_std_kernel(cdx_gpis g, con
   int s = 0;
   if constexpr (VAR) {
     for (const int e = min(nK, max(0, 1 - d0)); s < e; ++s) step(s, I0{}, I4{});
-#if !defined(CDX_STD_NODIAG)
     if (s < nK && s + d0 == 1) step(s++, I1{}, I4{});
     if (s < nK && s + d0 == 2) step(s++, I2{}, I4{});
     if (s < nK && s + d0 == 3) step(s++, I3{}, I4{});
-#else
-    for (const int e = min(nK, max(0, 4 - d0)); s < e; ++s) step(s, I0{}, I4{});
-#endif
     for (; s < nK; ++s) step(s, I0{}, I0{});
   } else if constexpr (MODE == MODE_GRADV) {
     for (const int e = min(nK, max(0, -d0)); s < e; ++s) step(s, I0{}, I0{});
-#if !defined(CDX_STD_NODIAG)
     if (s < nK && s + d0 == 0) step(s++, I0{}, I1{});
     if (s < nK && s + d0 == 1) step(s++, I0{}, I2{});
     if (s < nK && s + d0 == 2) step(s++, I0{}, I3{});
-#endif
     for (; s < nK; ++s) step(s, I0{}, I4{});
   } else {
     for (; s < nK; ++s) step(s, I0{}, I4{});
@@ -1103,7 +899,6 @@ __global__ __launch_bounds__(ST_THREADS, 2) void gpis_std_kernel(cdx_gpis g, con
       if (pc == pieces - 1) rl.cuts[pieces] = q1;
     }
     bool first = true;
-    __shared__ int s_last;
 #if defined(CDX_DIAG_WGTIME)
     int n_seg = 0;
 #endif
@@ -1118,25 +913,6 @@ __global__ __launch_bounds__(ST_THREADS, 2) void gpis_std_kernel(cdx_gpis g, con
       if (!first) __syncthreads();  // the previous segment's epilogue used the stage buffers
       first = false;
       tile(mt, nt, kbeg, kend, full ? nt : 2 * pc + (q == q0 ? 0 : 1), full);
-#if defined(CDX_MERGE_FUSED)
-      if (!full) {
-        // release this piece's partial tile, count the arrival; the unit's last piece merges it
-        __threadfence();
-        __syncthreads();
-        if (tid == 0) {
-          const int n = refine_piece_of(S1 - 1, rl.cuts, pieces) - refine_piece_of(S0, rl.cuts, pieces) + 1;
-          int* c = rl.cnt + (int64_t)nt * rl.mt_cap + mt;
-          const int old = atomicAdd(c, 1);
-          s_last = old == n - 1;
-          if (old == n - 1) *c = 0;  // ready for the next launch
-        }
-        __syncthreads();
-        if (s_last) {
-          __threadfence();  // acquire: the other pieces' tiles
-          refine_merge_unit(g, rl, M_pad, partial, vout, nt, mt, S0, S1, pieces, tid);
-        }
-      }
-#endif
       q = e;
 #if defined(CDX_DIAG_WGTIME)
       ++n_seg;
@@ -1159,9 +935,7 @@ __global__ __launch_bounds__(ST_THREADS, 2) void gpis_std_kernel(cdx_gpis g, con
     const int p = t / Mt, mt = t - p * Mt;
     int W = 0;
     for (int nt = 0; nt < Nt; ++nt) W += gradv_ksteps(nt, g.N);
-    // cost-balanced cuts from the launcher's per-stripe costs (carried in rl.uc, RC_MAX_NT = GC_MAX_NT)
-    const int q0 = cdx::gradv_cut(p, parts, W, g.N, Nt, rl.uc, rl.n_uc),
-              q1 = cdx::gradv_cut(p + 1, parts, W, g.N, Nt, rl.uc, rl.n_uc);
+    const int q0 = cdx::gradv_cut(p, parts, W), q1 = cdx::gradv_cut(p + 1, parts, W);
     bool first = true;
     for (int nt = 0, s0 = 0; nt < Nt; ++nt) {
       const int s1 = s0 + gradv_ksteps(nt, g.N);
@@ -1215,38 +989,6 @@ __global__ __launch_bounds__(ST_THREADS, 2) void gpis_std_kernel(cdx_gpis g, con
   }
   // B rows ≥ N are zero: stop at the last live K-step; L⁻ᵀ (VAR) also stops at the tile's diagonal
   tile(mt, nt, 0, VAR ? min(g.N, nt * ST_BN + ST_BN - vsh) : g.N, nt);
-}
-
-
-
-// K*[m][j] = k(x_m, x_j) for j < N, 0 for N ≤ j < N_pad: the whitened pass's A operand
-// ([M][N_pad], row-major).  Each 256-thread block covers KS_ROWS query rows: a thread keeps one
-// inducing point per column step and writes KS_ROWS rows (coalesced along j); X1 is read once
-// per block.  Write-bound: 8·N_pad bytes per query.
-constexpr int KS_ROWS = 16;
-template <int KT>
-__global__ __launch_bounds__(256) void gpis_kstar_kernel(cdx_gpis g, const double* __restrict__ X, int64_t M,
-                                                         double* __restrict__ out) {
-  __shared__ double xq[3 * KS_ROWS];
-  const int64_t m0 = (int64_t)blockIdx.x * KS_ROWS;
-  const int Np = g.N_pad, N = g.N;
-  if (threadIdx.x < 3 * KS_ROWS) {
-    const int64_t m = min(m0 + threadIdx.x / 3, M - 1);
-    xq[threadIdx.x] = X[3 * m + threadIdx.x % 3];
-  }
-  __syncthreads();
-  const double R = g.R, inv_s2 = 1.0 / (g.sigma * g.sigma);
-  const int nr = (int)min((int64_t)KS_ROWS, M - m0);
-  for (int j = threadIdx.x; j < Np; j += 256) {
-    const bool live = j < N;
-    const double px = live ? g.X1[3 * j] : 0.0, py = live ? g.X1[3 * j + 1] : 0.0, pz = live ? g.X1[3 * j + 2] : 0.0;
-    for (int r = 0; r < nr; ++r) {
-      const double dx = xq[3 * r] - px, dy = xq[3 * r + 1] - py, dz = xq[3 * r + 2] - pz;
-      double k, kd;
-      gpis_k<KT>(dx * dx + dy * dy + dz * dz, R, inv_s2, k, kd);
-      out[(m0 + r) * Np + j] = live ? k : 0.0;
-    }
-  }
 }
 
 // std = sqrt|k0 − Σ_t V²-partials|; var_out keeps the signed k0 − ‖L⁻¹k‖² for the ∇std scale.
@@ -1348,7 +1090,6 @@ __global__ __launch_bounds__(256) void gpis_var_splitk_finalize(cdx_gpis g, cons
   }
 }
 
-#if !defined(CDX_MERGE_FUSED)
 // The cut units merged by a separate kernel after the refine pass — workgroup p finishes the unit
 // whose K-range ends inside piece p after starting in an earlier one.
 __global__ __launch_bounds__(MERGE_THREADS) void gpis_var_merge(cdx_gpis g, RefineList rl, int64_t M_pad,
@@ -1366,8 +1107,6 @@ __global__ __launch_bounds__(MERGE_THREADS) void gpis_var_merge(cdx_gpis g, Refi
   if (!(S0 < q0 && S1 <= q1)) return;
   refine_merge_unit(g, rl, M_pad, partial, vout, nt, mt, S0, S1, rc.pieces, threadIdx.x);
 }
-
-#endif
 
 // Partial slots a ∇std launch wrote, in increasing order (host-computed, passed by value).
 constexpr int GRAD_MAX_SLOTS = 512;
@@ -1435,8 +1174,8 @@ static int var_chunk(const cdx_gpis& g, int64_t M) {
   return c;
 }
 
-// Chunk/stripe partials, then (VAR_KLOAD) the K* buffer at a 256-byte aligned offset.
-static size_t var_partial_bytes(const cdx_gpis& g, int64_t M) {
+// Chunk/stripe partials.
+size_t gpis_var_ws_bytes(const cdx_gpis& g, int64_t M) {
   const int c = var_chunk(g, M);
   size_t b;
   if (c > 0) {
@@ -1446,10 +1185,6 @@ static size_t var_partial_bytes(const cdx_gpis& g, int64_t M) {
     b = (size_t)(g.N_pad / ST_BN) * (size_t)round_up(M, ST_BM) * sizeof(double);
   }
   return (b + 255) / 256 * 256;
-}
-
-size_t gpis_var_ws_bytes(const cdx_gpis& g, int64_t M) {
-  return var_partial_bytes(g, M) + (VAR_KLOAD ? (size_t)M * g.N_pad * sizeof(double) : 0);
 }
 
 // Pieces per query tile of the ∇std pass: one round of workgroups over the 256 CUs when the query
@@ -1476,18 +1211,12 @@ static void var_launch_kt(const cdx_gpis& g, const double* X, int64_t M, double*
   // Σ V² needs the K-summed V: a split-K launch (few query tiles) stores per-chunk V tiles and a
   // second kernel sums them in a fixed order (no atomics: deterministic).
   const int chunk = var_chunk(g, M);
-  double* kstar = nullptr;
-  if (VAR_KLOAD) {
-    kstar = reinterpret_cast<double*>(reinterpret_cast<char*>(partial) + var_partial_bytes(g, M));
-    hipLaunchKernelGGL(gpis_kstar_kernel<KT>, dim3((unsigned)((M + KS_ROWS - 1) / KS_ROWS)), dim3(256), 0, s, g, X, M,
-                       kstar);
-  }
   if (chunk > 0) {
     int units = 0;
     for (int nt = 0; nt < n_tiles; ++nt) units += (var_ksteps(nt, g.N, g.N_pad) + chunk - 1) / chunk;
     prof_mark(PROF_GPIS_STD, true, s);
     hipLaunchKernelGGL((gpis_std_kernel<KT, MODE_VAR>), dim3((unsigned)(Mt * units)), dim3(ST_THREADS), 0, s,
-                       g, X, M, partial, M_pad, Mt, n_tiles, nullptr, kstar, nullptr, chunk, RefineList{});
+                       g, X, M, partial, M_pad, Mt, n_tiles, nullptr, nullptr, nullptr, chunk, RefineList{});
     hipLaunchKernelGGL(gpis_var_splitk_finalize<KT>, dim3((unsigned)M), dim3(256), 0, s, g, partial, M_pad, chunk,
                        vout, std_out, var_out);
     prof_mark(PROF_GPIS_STD, false, s);
@@ -1498,7 +1227,7 @@ static void var_launch_kt(const cdx_gpis& g, const double* X, int64_t M, double*
   }
   prof_mark(PROF_GPIS_STD, true, s);
   hipLaunchKernelGGL((gpis_std_kernel<KT, MODE_VAR>), dim3((unsigned)(Mt * n_tiles)), dim3(ST_THREADS), 0, s,
-                     g, X, M, partial, M_pad, Mt, n_tiles, vout, kstar, nullptr, 0, RefineList{});
+                     g, X, M, partial, M_pad, Mt, n_tiles, vout, nullptr, nullptr, 0, RefineList{});
   prof_mark(PROF_GPIS_STD, false, s);
   if (vs && 256 % vs->T == 0) {
     hipLaunchKernelGGL(gpis_var_finalize_select<KT>, dim3((unsigned)((M + 255) / 256)), dim3(256), 0, s, g, partial,
@@ -1521,21 +1250,11 @@ static void grad_launch_kt(const cdx_gpis& g, const double* X, int64_t M, const 
   slots.n = 0;
   if (vin) {
     const int parts = gradv_parts(g, Mt);
-    // cost-balanced pieces (gradv_cut): per-stripe costs to the kernel through the list's cost table
-    GradCosts gc;
-    RefineList rl{};
-#if defined(CDX_GRAD_COSTCUT)  // off: 0.295 vs 0.286 ms for the ∇std pass (profiles/r03w_cuts_ab.jsonl)
-    if (n_tiles <= GC_MAX_NT && n_tiles <= RC_MAX_NT) {
-      gc.n = rl.n_uc = n_tiles;
-      for (int nt = 0; nt < n_tiles; ++nt) gc.uc[nt] = rl.uc[nt] = gradv_unit_cost(nt, g.N);
-    }
-#endif
     // slot p + nt per (piece, stripe) segment the kernel runs (same cut as gpis_std_kernel<GRADV>)
     int W = 0;
     for (int nt = 0; nt < n_tiles; ++nt) W += gradv_ksteps(nt, g.N);
     for (int p = 0; p < parts; ++p) {
-      const int q0 = gradv_cut(p, parts, W, g.N, n_tiles, gc.uc, gc.n),
-                q1 = gradv_cut(p + 1, parts, W, g.N, n_tiles, gc.uc, gc.n);
+      const int q0 = gradv_cut(p, parts, W), q1 = gradv_cut(p + 1, parts, W);
       for (int nt = 0, s0 = 0; nt < n_tiles; ++nt) {
         const int s1 = s0 + gradv_ksteps(nt, g.N);
         if (std::max(q0, s0) < std::min(q1, s1) && slots.n < GRAD_MAX_SLOTS) slots.t[slots.n++] = (unsigned short)(p + nt);
@@ -1543,7 +1262,7 @@ static void grad_launch_kt(const cdx_gpis& g, const double* X, int64_t M, const 
       }
     }
     hipLaunchKernelGGL((gpis_std_kernel<KT, MODE_GRADV>), dim3((unsigned)(Mt * parts)), dim3(ST_THREADS), 0,
-                       s, g, X, M, partial, M_pad, Mt, n_tiles, nullptr, vin, vrow ? vrow : sel, parts, rl);
+                       s, g, X, M, partial, M_pad, Mt, n_tiles, nullptr, vin, vrow ? vrow : sel, parts, RefineList{});
     if (fold) {  // the consumer sums the pieces itself (same slots in the same order as the list above)
       prof_mark(PROF_GPIS_GRAD, false, s);
       fold->partial = partial;
@@ -1552,14 +1271,11 @@ static void grad_launch_kt(const cdx_gpis& g, const double* X, int64_t M, const 
       fold->W = W;
       fold->Nt = n_tiles;
       fold->N = g.N;
-      fold->gc = gc;
       fold->n_slots = 0;
-#if !defined(CDX_FOLD_CUTS)  // (A/B: the consumer walks the cuts itself)
       if (slots.n <= GF_MAX_SLOTS) {
         fold->n_slots = slots.n;
         for (int i = 0; i < slots.n; ++i) fold->slot[i] = slots.t[i];
       }
-#endif
       return;
     }
   } else {
@@ -1615,25 +1331,22 @@ int gpis_grad_launch(const cdx_gpis& g, const double* X, int64_t M, const int64_
 // Pieces of the refine pass: one per CU.
 constexpr int REFINE_PIECES = 256;
 
-// [stripe partials][cut-unit partial tiles][arrival counters]
+// [stripe partials][cut-unit partial tiles][the repair pass's arrival counter][piece bounds]
 static size_t refine_part_bytes(const cdx_gpis& g, int64_t Mcap) {
   return ((size_t)(g.N_pad / ST_BN) * (size_t)round_up(Mcap, ST_BM) * sizeof(double) + 255) / 256 * 256;
 }
 static size_t refine_slot_bytes() { return (size_t)REFINE_PIECES * 2 * ST_BM * ST_BN * sizeof(double); }
-// (+1: the repair pass's workgroup arrival counter, after the cut-unit counters)
-static size_t refine_cnt_bytes(const cdx_gpis& g, int64_t Mcap) {
-  return ((size_t)(g.N_pad / ST_BN) * (size_t)(round_up(Mcap, ST_BM) / ST_BM) * sizeof(int) + sizeof(int) + 255) / 256 * 256;
-}
+static size_t refine_cnt_bytes() { return 256; }  // (one int, the next region 256-byte aligned)
 
 static size_t refine_cuts_bytes() { return ((REFINE_PIECES + 1) * sizeof(int64_t) + 255) / 256 * 256; }
 
 size_t gpis_refine_ws_bytes(const cdx_gpis& g, int64_t Mcap) {
-  return refine_part_bytes(g, Mcap) + refine_slot_bytes() + refine_cnt_bytes(g, Mcap) + refine_cuts_bytes();
+  return refine_part_bytes(g, Mcap) + refine_slot_bytes() + refine_cnt_bytes() + refine_cuts_bytes();
 }
 
 int gpis_refine_reset(const cdx_gpis& g, int64_t Mcap, void* ws, hipStream_t s) {
   char* c = static_cast<char*>(ws) + refine_part_bytes(g, Mcap) + refine_slot_bytes();
-  return hipMemsetAsync(c, 0, refine_cnt_bytes(g, Mcap), s) == hipSuccess ? CDX_OK : CDX_ELAUNCH;
+  return hipMemsetAsync(c, 0, refine_cnt_bytes(), s) == hipSuccess ? CDX_OK : CDX_ELAUNCH;
 }
 
 template <int KT>
@@ -1644,10 +1357,8 @@ static void refine_launch_kt(const cdx_gpis& g, const double* X, int64_t Mcap, c
                      M_pad, 0, g.N_pad / ST_BN, vout, nullptr, nullptr, 0, rl);
   if (prof) prof_mark(PROF_GPIS_STD, false, s);
   if (after) (void)hipEventRecord(after, s);
-#if !defined(CDX_MERGE_FUSED)
   if (!rl.rs.on)  // (the repair pass runs whole units: nothing to merge)
     hipLaunchKernelGGL(gpis_var_merge, dim3(REFINE_PIECES), dim3(MERGE_THREADS), 0, s, g, rl, M_pad, partial, vout);
-#endif
 }
 
 int gpis_refine_launch(const cdx_gpis& g, const double* X, const int* rows, const int* extra, int G, int64_t Mcap,
@@ -1658,13 +1369,12 @@ int gpis_refine_launch(const cdx_gpis& g, const double* X, const int* rows, cons
   const int64_t M_pad = round_up(Mcap, ST_BM);
   double* partial = static_cast<double*>(ws);
   char* slots = static_cast<char*>(ws) + refine_part_bytes(g, Mcap);
-  RefineList rl{rows, extra, G, reinterpret_cast<double*>(slots), reinterpret_cast<int*>(slots + refine_slot_bytes()),
-                (int)(M_pad / ST_BM),
-                reinterpret_cast<int64_t*>(slots + refine_slot_bytes() + refine_cnt_bytes(g, Mcap)), 0, {}, gate, {}};
+  RefineList rl{rows, extra, G, reinterpret_cast<double*>(slots),
+                reinterpret_cast<int64_t*>(slots + refine_slot_bytes() + refine_cnt_bytes()), 0, {}, gate, {}};
   if (repair) {
     rl.rs = *repair;
     rl.rs.on = true;
-    rl.rs.done = rl.cnt + (size_t)(g.N_pad / ST_BN) * (size_t)(M_pad / ST_BM);
+    rl.rs.done = reinterpret_cast<int*>(slots + refine_slot_bytes());
   }
   const int Nt = g.N_pad / ST_BN;
   if (Nt <= RC_MAX_NT) {
@@ -1695,12 +1405,7 @@ int cdx_gpis_mean(const cdx_gpis* g, const double* X, int64_t M, double* mean, d
   cdx::prof_mark(cdx::PROF_GPIS_MEAN, true, s);
   switch (g->kernel) {
     case CDX_KERNEL_TPS:
-#if !defined(CDX_MEAN_DIRECT) && CDX_MEAN_QPT > 1
-      hipLaunchKernelGGL(gpis_mean_tps_blocked_kernel, dim3((unsigned)((M + MQ_PER_WG - 1) / MQ_PER_WG)), dim3(MEAN_BLOCK), 0, s,
-                         *g, X, M, mean, grad_mean, normal);
-#else
       hipLaunchKernelGGL(gpis_mean_kernel<CDX_KERNEL_TPS>, grid, dim3(MEAN_BLOCK), 0, s, *g, X, M, mean, grad_mean, normal);
-#endif
       break;
     case CDX_KERNEL_RBF: hipLaunchKernelGGL(gpis_mean_kernel<CDX_KERNEL_RBF>, grid, dim3(MEAN_BLOCK), 0, s, *g, X, M, mean, grad_mean, normal); break;
     default: hipLaunchKernelGGL(gpis_mean_kernel<CDX_KERNEL_JOINT>, grid, dim3(MEAN_BLOCK), 0, s, *g, X, M, mean, grad_mean, normal); break;

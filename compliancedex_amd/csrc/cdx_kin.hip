@@ -20,12 +20,6 @@
 
 namespace {
 
-#if defined(CDX_KIN_FE_F32)  // (A/B: the reward in the reference's float32 — 0.338 → 0.330 ms per Kin iteration, but its
-using FeReal = float;        // SVD backward then divides by S_k² − S_j² = 0 on near-repeated singular values, a NaN the
-#else                        // f64 path does not produce there: profiles/r06g_kin_fe_f32_ab.jsonl)
-using FeReal = double;
-#endif
-
 __device__ __forceinline__ uint64_t kin_mix(uint64_t x) {
   x += 0x9E3779B97F4A7C15ull;
   x = (x ^ (x >> 30)) * 0xBF58476D1CE4E5B9ull;
@@ -255,13 +249,9 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
     cdx_kin_opt_buffers sb, int it) {
   constexpr int NT = 4;
   if constexpr (STEP && FK) KIN_PHASE(0);
-#if !defined(CDX_KIN_FK_BWD1)
   __shared__ float s_fk[CDX_MAX_DOFS][64];  // per-DOF FK gradient contributions (then, with STEP, the summed ones)
-#endif
-#if !defined(CDX_KIN_FK_BWD1) && !defined(CDX_KIN_FK_BWD2)
   // the FK walk's slots (fk_tip_walk3s) behind the final pose; with STEP, the whole FK-walk cache image (FKS_BLOCK)
   __shared__ float s_jst[fks_slots(MAXD) * 64];
-#endif
   __shared__ float s_qn[64 / NT][CDX_MAX_DOFS];  // STEP: the candidates' joint rows (cache check), then the updated rows
   // STEP: the step's operands, prefetched (DOFs f + 4u of the candidate's row, this lane's target / compliance)
   constexpr int PF_DOFS = CDX_MAX_DOFS / NT;
@@ -314,7 +304,6 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
   } else {
     for (int i = 0; i < 9; ++i) nz[i] = (double)(kin_mix(seed ^ kin_mix((uint64_t)(e * 9 + i))) >> 11) * 0x1.0p-53;
   }
-#if !defined(CDX_KIN_FK_BWD1) && !defined(CDX_KIN_FK_BWD2)
   // STEP (Kin): the previous iteration's FK-walk cache of this workgroup and the candidates' current joint rows, into
   // LDS by DMA now — they land while the reward runs; the FK backward checks them and skips the chain walk
   const bool fks = STEP && FK && it > 0 && sb.fk_state != nullptr;
@@ -337,7 +326,6 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
       __builtin_amdgcn_global_load_lds(qb + (in ? 4 * u : 0), (lds_ptr)(&s_qn[0][0] + 256 * c), 16, 0, 0);
     }
   }
-#endif
   if constexpr (STEP && FK) KIN_PHASE(1);
   cdx::ForceEqParams fp;
   fp.cos_mu = (double)p.fe.cos_mu;
@@ -345,19 +333,8 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
   for (int i = 0; i < 3; ++i) fp.com[i] = (double)p.fe.com[i];
   fp.dummy_target_z = (double)p.fe.dummy_target_z;
   fp.dummy_comp = (double)p.fe.dummy_comp;
-  cdx::ForceEq<NT, -1, FeReal> fe;
-#if defined(CDX_KIN_FE_F32)
-  FeReal cpf[NT];
-#pragma unroll
-  for (int k = 0; k < NT; ++k) cpf[k] = (FeReal)cp[k];
-  {
-    FeReal tpf[NT][3], tgf[NT * 3], nrf[NT][3];  // (the reference's float32 values: exact)
-#pragma unroll
-    for (int k = 0; k < NT; ++k)
-      for (int i = 0; i < 3; ++i) { tpf[k][i] = (FeReal)tp[k][i]; tgf[3 * k + i] = (FeReal)tg[3 * k + i]; nrf[k][i] = (FeReal)nr[k][i]; }
-    fe.forward(fp, NT, tpf, tgf, cpf, nrf, nz);
-  }
-#elif !defined(CDX_KIN_DIAG_NOFE)
+  cdx::ForceEq<NT, -1, double> fe;
+#if !defined(CDX_KIN_DIAG_NOFE)
   fe.forward(fp, NT, tp, tg, cp, nr, nz);
 #endif
   if constexpr (STEP && FK) KIN_PHASE(2);
@@ -380,13 +357,7 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
     dcost += sd[k];
     tcost += ts[k] * std_[k];
   }
-#if defined(CDX_KIN_FE_F32)
-  double fn[NT];
-#pragma unroll
-  for (int k = 0; k < NT; ++k) fn[k] = (double)fe.fn[k];
-#else
   const double* fn = fe.fn;
-#endif
   double zmax = -fn[0];
   for (int k = 1; k < NT; ++k) zmax = -fn[k] > zmax ? -fn[k] : zmax;
   double ez[NT], esum = 0.0;
@@ -426,23 +397,7 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
     gsm_dot += g_sm[k] * sm[k];
   }
   for (int k = 0; k < NT; ++k) g_fn[k] += -(sm[k] * (g_sm[k] - gsm_dot));
-#if defined(CDX_KIN_FE_F32)
-  {
-    FeReal g_fnf[NT], gtf[NT][3], ggf[NT][3], gcf[NT];
-#pragma unroll
-    for (int k = 0; k < NT; ++k) {
-      g_fnf[k] = (FeReal)g_fn[k];
-      gcf[k] = FeReal(0);
-      for (int i = 0; i < 3; ++i) gtf[k][i] = ggf[k][i] = FeReal(0);
-    }
-    fe.backward(FeReal(-5.0), g_fnf, cpf, gtf, ggf, gcf);
-#pragma unroll
-    for (int k = 0; k < NT; ++k) {
-      for (int i = 0; i < 3; ++i) { gt[k][i] += (double)gtf[k][i]; gg[k][i] += (double)ggf[k][i]; }
-      gc[k] += (double)gcf[k];
-    }
-  }
-#elif !defined(CDX_KIN_DIAG_NOFE)
+#if !defined(CDX_KIN_DIAG_NOFE)
   fe.backward(-5.0, g_fn, cp, gt, gg, gc);
 #endif
   if constexpr (STEP && FK) KIN_PHASE(4);
@@ -455,17 +410,10 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
       gco = gc[k];
     }
   if constexpr (FK) {
-#if defined(CDX_KIN_FK_BWD1)  // (A/B: the stored-rotations backward walk, per-DOF sums in a register array)
-    float fk_g[CDX_MAX_DOFS];
-    for (int i = 0; i < D; ++i) fk_g[i] = 0.f;
-    const float gpos[3] = {(float)gto[0], (float)gto[1], (float)gto[2]};
-#if !defined(CDX_KIN_DIAG_NOFK)  // (timing-only diagnostic builds: outputs wrong)
-    cdx::fk_tip_bwd<MAXD>(chain, f, q + e * D, gpos, cdx::GqAdd{fk_g});
-#endif
-#else  // the closed-form backward (fk_tip_bwd2), per-DOF sums in LDS (a register array indexed by DOF spilled)
+    // the closed-form backward, per-DOF sums in LDS (a register array indexed by DOF spilled)
     for (int i = 0; i < D; ++i) s_fk[i][threadIdx.x] = 0.f;
     const float gpos[3] = {(float)gto[0], (float)gto[1], (float)gto[2]};
-#if !defined(CDX_KIN_DIAG_NOFK)
+#if !defined(CDX_KIN_DIAG_NOFK)  // (timing-only diagnostic builds: outputs wrong)
     // the chain read in place from the kernel-argument segment (it is the first argument, at offset 0): indexed by a
     // per-lane body index, the by-value copy went to scratch (≈ 2 KB per lane) in the deep-chain instantiation
     const cdx_chain& kc = *(const cdx_chain*)(__builtin_amdgcn_kernarg_segment_ptr());
@@ -499,9 +447,7 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
           for (int i = 0; i < 3; ++i) pf_nm[i] = nm[3 * r + i];
         }
     }
-#if defined(CDX_KIN_FK_BWD2)  // (A/B: two walks, no per-level state)
-    cdx::fk_tip_bwd2<MAXD>(kc, f, q + e * D, gpos, [&](int d, float v) { s_fk[d][threadIdx.x] += v; });
-#else  // one walk, each joint's world axis and origin kept in LDS
+    // one walk, each joint's world axis and origin kept in LDS
     auto gacc = [&](int d, float v) { s_fk[d][threadIdx.x] += v; };
     // the joints' slots in s_jst, in the cache's layout (fks_at)
     auto jput = [&](int l, int i, float v) { s_jst[fks_at(12 + 6 * l + i, threadIdx.x)] = v; };
@@ -537,12 +483,7 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
       cdx::fk_tip_bwd3_grad(kc, f, R, t, gpos, gacc, jget);
     }
 #endif
-#endif
     if constexpr (STEP && FK) KIN_PHASE(14);
-    float* fk_g = nullptr;
-    (void)fk_g;
-#endif
-#if !defined(CDX_KIN_FK_BWD1)
     if constexpr (STEP) {
       // the same sums, DOF by DOF; a lane's own DOFs f + 4u take their joint angle from the step's prefetch (the
       // loop below re-reads q per DOF behind the previous DOF's g_q store, which q may alias: one load latency each)
@@ -563,22 +504,15 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
           }
         }
     } else
-#endif
     for (int i = 0; i < D; ++i) {
-#if defined(CDX_KIN_FK_BWD1)
-      float s = fk_g[i];
-#else
       float s = s_fk[i][threadIdx.x];
-#endif
       s += __shfl_xor(s, 1);
       s += __shfl_xor(s, 2);
       if ((i & 3) == f) {
         const double d = (double)q[e * D + i] - (double)p.ref_q[i];
         const float gq = qn > 0 ? (float)(10.0 * d / qn) : 0.f;
         if (on) g_q[e * D + i] = gq + s;
-#if !defined(CDX_KIN_FK_BWD1)
         if constexpr (STEP) s_fk[i][threadIdx.x] = gq + s;  // (this lane's own slot: the step below reads it)
-#endif
       }
     }
   }
@@ -589,7 +523,6 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
     g_comp[r] = (float)gco;
     for (int i = 0; i < 3; ++i) g_target[3 * r + i] = (float)ggo[i];
   }
-#if !defined(CDX_KIN_FK_BWD1)
   if constexpr (STEP && FK) {
     // ---- cdx_kin_step's iteration `it` (kin_step_kernel, rule 0, T = 4): the previous iteration's margin / normal
     // commit, the best iterate, Adam, the next fingertip
@@ -676,7 +609,6 @@ __global__ __launch_bounds__(64) void kin_cost4_kernel(
     }
     KIN_PHASE(7);
   }
-#endif
   if constexpr (STEP && !FK) {
     // ---- cdx_kin_step's iteration `it` for the SDF optimiser (kin_step_kernel, rule 1, T = 4): the previous
     // iteration's margin / normal commit, the best iterate, RMSprop on this lane's fingertip / target / compliance,
@@ -757,17 +689,10 @@ extern "C" int cdx_kin_cost(const cdx_chain* chain, const cdx_kin_params* p, int
   hipLaunchKernelGGL((kin_cost4_kernel<MAXD, FK>), dim3((unsigned)((4 * E + 63) / 64)), dim3(64), 0, s, c, *p, E, q, tip, \
                      target, comp, sign1, n1, sqdist, sign2, n2, clst, tsqdist, tsign, tclst, noise, seed, loss, margin,   \
                      normal, g_q, g_target, g_comp, g_tip, cdx_kin_opt{}, cdx_kin_opt_buffers{}, 0)
-#if defined(CDX_KIN_1LANE)  // A/B: one lane per candidate for four fingertips too (round 4)
-  if (!chain && T == 4) CDX_KIN_LAUNCH(4, 8, false);
-  else if (!chain) CDX_KIN_LAUNCH(0, 8, false);
-  else if (T == 4 && shallow) CDX_KIN_LAUNCH(4, 8, true);
-  else if (T == 4) CDX_KIN_LAUNCH(4, CDX_MAX_DEPTH, true);
-#else
   if (!chain && T == 4) CDX_KIN4_LAUNCH(8, false);
   else if (!chain) CDX_KIN_LAUNCH(0, 8, false);
   else if (T == 4 && shallow) CDX_KIN4_LAUNCH(8, true);
   else if (T == 4) CDX_KIN4_LAUNCH(CDX_MAX_DEPTH, true);
-#endif
   else if (shallow) CDX_KIN_LAUNCH(0, 8, true);
   else CDX_KIN_LAUNCH(0, CDX_MAX_DEPTH, true);
 #undef CDX_KIN_LAUNCH

@@ -46,54 +46,24 @@ typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 using cdx::SC_BK;
 using cdx::SC_BN;
 constexpr int SC_BM = 256;                 // query rows per workgroup
-#ifndef CDX_SC_WAVES
-#define CDX_SC_WAVES 8
-#endif
-// 8 waves (two per SIMD): 2 (rows) × 4 (columns), 128 × 64 outputs each; 4 waves (one per SIMD,
-// accumulators in AGPRs): 2 × 2, 128 × 128 outputs each (half the fragment reads per MFMA);
-// 16 waves (four per SIMD, ≤ 128 registers): 4 × 4, 64 × 64 outputs each
-constexpr int SC_W = CDX_SC_WAVES;
-static_assert(SC_W == 8 || SC_W == 4 || SC_W == 16, "4, 8 or 16 waves per workgroup");
+// 8 waves (two per SIMD): 2 (rows) × 4 (columns), 128 × 64 outputs each
+constexpr int SC_W = 8;
 constexpr int SC_THREADS = 64 * SC_W;
-constexpr int SC_WC = SC_W == 4 ? 128 : 64;   // columns per wave
-constexpr int SC_WR = SC_W == 16 ? 64 : 128;  // rows per wave
-constexpr int SC_NJ = SC_WC / 32;             // 32-column accumulator blocks per wave
-constexpr int SC_NI = SC_WR / 32;             // 32-row accumulator blocks per wave
-constexpr int SC_GKH = SC_W == 4 ? 2 : 1;     // k-halves generated per thread per sub-step
-// 16 waves: each thread generates one (sub-step, k-half) chunk of the next stage
+constexpr int SC_WC = 64;                  // columns per wave
+constexpr int SC_WR = 128;                 // rows per wave
+constexpr int SC_NJ = SC_WC / 32;          // 32-column accumulator blocks per wave
+constexpr int SC_NI = SC_WR / 32;          // 32-row accumulator blocks per wave
 constexpr int SC_REG = 4 * 256;            // 16-byte LDS units of one 16-K sub-step: [slice][khalf][256]
-#ifndef CDX_SC_SUB
-#define CDX_SC_SUB 2
-#endif
-constexpr int SC_SUB = CDX_SC_SUB;         // 16-K sub-steps per stage (one barrier per stage)
-#ifndef CDX_SC_RING
-#define CDX_SC_RING (CDX_SC_SUB == 1 ? 3 : 2)
-#endif
-constexpr int SC_RING = CDX_SC_RING;       // B stages in LDS: DMA'd SC_RING − 1 stages ahead
-static_assert(SC_RING == 2 || SC_RING == 3, "B ring of 2 or 3 stages");
-constexpr int SC_NDMA = 16 * SC_SUB / SC_W;  // 1-KB DMAs per wave per stage
-static_assert(SC_SUB == 1 || SC_SUB == 2, "stage = 16 or 32 K rows");
-#ifndef CDX_SC_PP
-#define CDX_SC_PP 0
-#endif
-#ifndef CDX_SC_EPI_REG  // epilogue from the accumulator registers (1, default) or through an LDS image (0)
-#define CDX_SC_EPI_REG 1
-#endif
-// Ping-pong: the two waves of a SIMD (waves w, w+4) multiply in alternate half-stages; in the
-// other half each generates one 16-K sub-step of the next stage's A and DMAs its B.
-constexpr bool SC_PP = CDX_SC_PP;
-static_assert(!SC_PP || (SC_W == 8 && SC_SUB == 2 && SC_RING == 2), "ping-pong: 8 waves, 32-K stages, B ring of 2");
-// Epilogue image of one row half of the tile: fp32 rows of pitch SC_LDE ≡ 4 (mod 32), the e-th
-// 64-column share of a row rotated by 16·e dwords (sc_tcol): the accumulators' ds_write_b128 (8
-// consecutive rows per lane group) and the summing threads' ds_read_b128 (4 shares × 4 rows per
-// lane group) are both conflict-free.  Then the stripe's (cscale, csum) pairs, pair c at c + (c >> 6).
-constexpr int SC_LDE = 260;
-constexpr int SC_EPI_CF = 128 * SC_LDE * 4;
-constexpr int SC_EPI = SC_EPI_CF + (SC_BN + SC_BN / 64) * 16;
-// LDS: A stages (generated, 2 buffers) | B stages (LDS-DMA ring); after the loop, the epilogue
+constexpr int SC_SUB = 2;                  // 16-K sub-steps per stage (one barrier per stage)
+constexpr int SC_RING = 2;                 // B stages in LDS: DMA'd one stage ahead
+constexpr int SC_NDMA = 4;                 // 1-KB DMAs per wave per stage
+static_assert(SC_NDMA * SC_W == 16 * SC_SUB, "the waves' DMAs cover a B stage");
+// LDS: A stages (generated, 2 buffers) | B stages (LDS-DMA ring); after the loop, the epilogue's
+// (cscale, csum) pairs and column-wave partials (12 KB) reuse the front
 constexpr int SC_A_OFF = 0, SC_B_OFF = 2 * SC_SUB * SC_REG * 16;
-constexpr int SC_SMEM = std::max(SC_B_OFF + SC_RING * SC_SUB * SC_REG * 16, SC_EPI);
+constexpr int SC_SMEM = SC_B_OFF + SC_RING * SC_SUB * SC_REG * 16;
 static_assert(SC_SMEM <= 160 * 1024, "screen stage buffers exceed the CU's LDS");
+static_assert(SC_BN * 16 + (SC_BN / SC_WC) * SC_BM * 8 <= SC_SMEM, "the epilogue's LDS use fits the stage buffers");
 
 // K-steps (16 rows of L⁻ᵀ) of stripe nt: rows [0, min(N, (nt+1)·256 − shift)) as in the fp64 pass.
 __device__ __host__ inline int sc_ksteps(int nt, int N, int Np) {
@@ -125,7 +95,7 @@ __device__ __forceinline__ void split2(float xa, float xb, unsigned& h0, unsigne
 // One workgroup per (query tile of 256 rows, stripe of 256 columns); stripes paired heavy+light per
 // XCD as in gpis_std_kernel<VAR>.  partial[nt][m] = Σ over the stripe's columns of (Ã·L⁻ᵀ + c)².
 template <int KT>
-__global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_gpis g, const double* __restrict__ X, int64_t M,
+__global__ __launch_bounds__(SC_THREADS, 2) void gpis_screen_kernel(cdx_gpis g, const double* __restrict__ X, int64_t M,
                                                                     double* __restrict__ partial, int64_t M_pad, int Mt,
                                                                     int Nt) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[SC_SMEM];
@@ -156,10 +126,9 @@ __global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_g
   const int nK = sc_ksteps(nt, N, Np);        // 16-K sub-steps
   const int nS = (nK + SC_SUB - 1) / SC_SUB;  // stages
 
-  // generation: thread → query row grow, k-halves gkh .. gkh + SC_GKH − 1 (wave-uniform), 8 entries each
+  // generation: thread → query row grow, k-half gkh (wave-uniform), 8 entries
   const int grow = tid & (SC_BM - 1);
-  const int gkh = SC_W == 4 ? 0 : __builtin_amdgcn_readfirstlane((tid >> 8) & 1);
-  const int gsub = SC_W == 16 ? __builtin_amdgcn_readfirstlane(tid >> 9) : 0;
+  const int gkh = __builtin_amdgcn_readfirstlane((tid >> 8) & 1);
   float qx, qy, qz;
   {
     const int64_t m = std::min(m0 + grow, M - 1);  // pad rows replicate a valid query
@@ -175,11 +144,9 @@ __global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_g
                      (float)(-0.5 / (g.sigma * g.sigma)));
   }
 
-  // wave → 128 × SC_WC output sub-tile; with 8 waves, waves w and w+4 share a SIMD and take
-  // complementary columns
-  // (16 waves: waves w, w+4, w+8, w+12 share a SIMD and take all four column quarters)
-  const int cwave = SC_W == 16 ? (((wave & 3) + (wave >> 2)) & 3) : SC_W == 8 ? (wave < 4 ? wave : 7 - wave) : (wave & 1);
-  const int wr = (SC_W == 16 ? (wave >> 2) : SC_W == 8 ? (wave >> 2) : (wave >> 1)) * SC_WR;
+  // wave → 128 × 64 output sub-tile; waves w and w+4 share a SIMD and take complementary columns
+  const int cwave = wave < 4 ? wave : 7 - wave;
+  const int wr = (wave >> 2) * SC_WR;
   const int wc = cwave * SC_WC;
   // B rows past this wave's last column are zero (upper-triangular L⁻ᵀ, shifted columns)
   const int kend_w = __builtin_amdgcn_readfirstlane(n0 + wc + SC_WC - shift);
@@ -194,11 +161,8 @@ __global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_g
 
   // Staging by LDS-DMA (global_load_lds: no VGPRs, no ds_write).  issue(st): every wave DMAs
   // SC_NDMA × 1 KB of B stage st (instruction u = wave + 8i: sub-step u>>4, slice/k-half region
-  // (u>>2)&3, columns 64·(u&3) + lane) into ring slot st % SC_RING, SC_RING − 1 stages ahead.
-  // 32-K stages (default): issue(s+1) during step s, `s_waitcnt vmcnt(0)` before the step's raw
-  // s_barrier.  16-K stages: issue(s+2) during step s and a counted `vmcnt(2)` keeps that step's DMAs
-  // in flight across the barrier (__syncthreads would wait vmcnt(0)); clamped stages past the
-  // stripe's end load into free slots, so every step issues the same count.
+  // (u>>2)&3, columns 64·(u&3) + lane) into ring slot st % SC_RING, one stage ahead:
+  // issue(s+1) during step s, `s_waitcnt vmcnt(0)` before the step's raw s_barrier.
   const char* Lb = static_cast<const char*>(sv.L);
   auto issue = [&](int st) {
     const int sc = std::min(st, nS - 1);
@@ -240,13 +204,6 @@ __global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_g
   auto write_a = [&](int buf, int sub, int kh) {
 #pragma unroll
     for (int i = 0; i < 2; ++i) sA4[(buf * SC_SUB + sub) * SC_REG + (i * 2 + kh) * 256 + grow] = ast[i];
-  };
-  auto gen_write = [&](int st, int buf, int sub) {
-#pragma unroll
-    for (int h = 0; h < SC_GKH; ++h) {
-      gen_a(st, sub, gkh + h);
-      write_a(buf, sub, gkh + h);
-    }
   };
   // one sub-step's 12·SC_NJ MFMAs: lane → (row/col l&31, k-half l>>5); B slices of the wave's column
   // blocks, A slice by slice (products of slice-index sum ≤ 1, smallest first); each MFMA takes the
@@ -290,24 +247,19 @@ __global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_g
     }
   };
 
-#if defined(CDX_SC_PRIO_YOUNG)  // A/B: static priority for the second-dispatched half (waves 4–7)
-  if (wave >= SC_W / 2) __builtin_amdgcn_s_setprio(1);
-#endif
-  // prologue: B stages 0 .. SC_RING−2 landed, A of stage 0 generated
+  // prologue: B stage 0 landed, A of stage 0 generated
 #pragma unroll
   for (int st = 0; st < SC_RING - 1; ++st) issue(st);
-  if constexpr (SC_W == 16) {
-    gen_a(0, gsub, gkh);
-    write_a(0, gsub, gkh);
-  } else {
 #pragma unroll
-    for (int u = 0; u < SC_SUB; ++u) gen_write(0, 0, u);
+  for (int u = 0; u < SC_SUB; ++u) {
+    gen_a(0, u, gkh);
+    write_a(0, u, gkh);
   }
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   __builtin_amdgcn_s_barrier();
 
-  // Step s multiplies stage s (A buffer s&1, B slot s % SC_RING) while stage s + SC_RING − 1 is DMA'd
+  // Step s multiplies stage s (A buffer s&1, B slot s % SC_RING) while B stage s+1 is DMA'd
   // and stage s+1's A is generated and written to the other A buffer, sub-step by sub-step.  NLIVE:
   // this wave's B columns are non-zero in the first NLIVE sub-steps of stage s; MORE: a stage s+1
   // exists.  Each (NLIVE, MORE) body is one straight-line block, so the generation's VALU work
@@ -315,29 +267,15 @@ __global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_g
   auto step = [&](int s, auto nlive_c, auto more_c) {
     constexpr int NLIVE = decltype(nlive_c)::value;
     constexpr bool MORE = decltype(more_c)::value;
-    if (SC_RING > 2 || s + 1 < nS) issue(s + SC_RING - 1);
+    if (s + 1 < nS) issue(s + 1);
 #pragma unroll
     for (int u = 0; u < SC_SUB; ++u) {
-      if constexpr (SC_W == 16) {
-        if (MORE && u == 0) gen_a(s + 1, gsub, gkh);
-        if (u < NLIVE) mfma_sub(s & 1, s % SC_RING, u, more_c);
-        if (MORE && u == 0) write_a((s + 1) & 1, gsub, gkh);
-      } else if (SC_GKH == 1) {
-        if (MORE) gen_a(s + 1, u, gkh);
-        if (u < NLIVE) mfma_sub(s & 1, s % SC_RING, u, more_c);
-        if (MORE) write_a((s + 1) & 1, u, gkh);
-      } else {
-        if (u < NLIVE) mfma_sub(s & 1, s % SC_RING, u, more_c);
-        if (MORE) gen_write(s + 1, (s + 1) & 1, u);
-      }
+      if (MORE) gen_a(s + 1, u, gkh);
+      if (u < NLIVE) mfma_sub(s & 1, s % SC_RING, u, more_c);
+      if (MORE) write_a((s + 1) & 1, u, gkh);
     }
-    // B stage s+1 landed (the newest stage's DMAs may stay in flight), A written
-    if constexpr (SC_RING == 2)
-      asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    else if constexpr (SC_NDMA == 2)
-      asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory");
-    else
-      asm volatile("s_waitcnt vmcnt(4) lgkmcnt(0)" ::: "memory");
+    // B stage s+1 landed, A written
+    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
 #if !defined(CDX_SC_DIAG_NOBAR)  // timing-only diagnostic build (races): outputs are wrong
     __builtin_amdgcn_s_barrier();
 #endif
@@ -345,67 +283,25 @@ __global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_g
   using T_ = std::true_type;
   using F_ = std::false_type;
   const int k_live = std::min(nK, std::max(0, (kend_w + SC_BK - 1) / SC_BK));  // live sub-steps (wave-uniform)
-  if constexpr (SC_PP) {
-    // Phase ph of stage s: waves 0–3 (ph 0) or 4–7 (ph 1) multiply stage s; the other half DMAs
-    // sub-step ph of B(s+1) (4 KB per wave) and generates sub-step ph of A(s+1) (both k-halves of
-    // its 256 rows).  Buffers: A(s+1) and B(s+1) go to the slots stage s−1 used, free since the
-    // barrier that ended stage s−1; B(s+1) has landed at the barrier that ends stage s.
-    const bool P = wave < 4;
-    for (int s = 0; s < nS; ++s) {
-      const bool more = s + 1 < nS;
-#pragma unroll
-      for (int ph = 0; ph < 2; ++ph) {
-        if (P == (ph == 0)) {
-          if (2 * s < k_live) mfma_sub(s & 1, s % SC_RING, 0, T_{});
-          if (2 * s + 1 < k_live) mfma_sub(s & 1, s % SC_RING, 1, T_{});
-        } else if (more) {
-          const int sc = s + 1, slot = sc % SC_RING;
-#pragma unroll
-          for (int i = 0; i < 4; ++i) {
-            const int r = (wave & 3) + 4 * i, col = 64 * (r & 3) + lane;
-            const char* src = Lb + (((int64_t)((sc * SC_SUB + ph) * 4 + (r >> 2))) * Np + n0 + col) * 16;
-            __builtin_amdgcn_global_load_lds(src, (__attribute__((address_space(3))) void*)(sB4 + (slot * SC_SUB + ph) * SC_REG + r * 64),
-                                             16, 0, 0);
-          }
-#pragma unroll
-          for (int kh = 0; kh < 2; ++kh) {
-            gen_a(sc, ph, kh);
-            write_a(sc & 1, ph, kh);
-          }
-        }
-        if (ph == 0)
-          asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        else
-          asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-        __builtin_amdgcn_s_barrier();
-      }
-    }
-  } else {
-    const int full = k_live / SC_SUB;
-    int s = 0;
-    for (; s < std::min(full, nS - 1); ++s) step(s, std::integral_constant<int, SC_SUB>{}, T_{});
-    if (SC_SUB == 2 && s < nS - 1 && s * SC_SUB < k_live) {
-      step(s, std::integral_constant<int, 1>{}, T_{});
-      ++s;
-    }
-    for (; s < nS - 1; ++s) step(s, std::integral_constant<int, 0>{}, T_{});
-    // last stage: its MFMAs only; then every DMA drained before the epilogue reuses the LDS
-#pragma unroll
-    for (int u = 0; u < SC_SUB; ++u)
-      if (s * SC_SUB + u < k_live) mfma_sub(s & 1, s % SC_RING, u, F_{});
+  const int full = k_live / SC_SUB;
+  int s = 0;
+  for (; s < std::min(full, nS - 1); ++s) step(s, std::integral_constant<int, SC_SUB>{}, T_{});
+  if (s < nS - 1 && s * SC_SUB < k_live) {
+    step(s, std::integral_constant<int, 1>{}, T_{});
+    ++s;
   }
+  for (; s < nS - 1; ++s) step(s, std::integral_constant<int, 0>{}, T_{});
+  // last stage: its MFMAs only; then every DMA drained before the epilogue reuses the LDS
+#pragma unroll
+  for (int u = 0; u < SC_SUB; ++u)
+    if (s * SC_SUB + u < k_live) mfma_sub(s & 1, s % SC_RING, u, F_{});
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
   __syncthreads();
 
   // Epilogue: per row Σ over the stripe's 256 columns of (Ṽ + c)² in f64.  The MFMAs compute Ṽᵀ (L⁻ᵀ
   // slice as the A operand, Ã as B), so reg r of lane l holds query row l&31, column (r&3) + 8(r>>2) +
-  // 4(l>>5).  Default (CDX_SC_EPI_REG=1): each lane sums its own columns straight from the accumulators
-  // into one f64 per row block (below; 0.175 vs 0.181 ms per screen in the closure, standalone 0.207–0.211
-  // vs 0.218 ms against 0.200–0.204 with no epilogue at all, profiles/r03u_screen_epilogue_ab.jsonl).
-  // CDX_SC_EPI_REG=0: the accumulators go through LDS one row half at a time (four consecutive columns
-  // per register quad, one ds_write_b128, rotated conflict-free image), then EP threads per row sum a
-  // share of its columns each, in column order, and combine by xor-shuffles.  Both stage the columns'
-  // (cscale, csum) in LDS once (read from global memory per thread, they cost a quarter of the kernel).
+  // 4(l>>5).  The columns' (cscale, csum) are staged in LDS once (read from global memory per thread,
+  // they cost a quarter of the kernel).
 #if defined(CDX_SC_DIAG_NOEPI)  // timing-only diagnostic build: outputs are wrong
   {
     float t = 0.f;
@@ -417,9 +313,8 @@ __global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_g
     return;
   }
 #endif
-#if CDX_SC_EPI_REG
-  // Register epilogue: each lane sums (Ṽ·cscale + csum)² over its own 32 columns of its rows straight
-  // from the accumulators (columns in (j, r) order, the (cscale, csum) pairs broadcast from LDS), the
+  // Each lane sums (Ṽ·cscale + csum)² over its own 32 columns of its rows straight from the
+  // accumulators (columns in (j, r) order, the (cscale, csum) pairs broadcast from LDS), the
   // two column halves of a lane pair combine by one xor-shuffle, and the column waves of a row through
   // LDS in column-wave order — no accumulator image in LDS and one barrier instead of three.
   {
@@ -452,49 +347,6 @@ __global__ __launch_bounds__(SC_THREADS, SC_W / 4) void gpis_screen_kernel(cdx_g
 #pragma unroll
       for (int c = 0; c < SC_BN / SC_WC; ++c) t += red[c * SC_BM + tid];
       partial[(int64_t)nt * M_pad + m0 + tid] = t;
-    }
-    return;
-  }
-#endif
-  float* T = reinterpret_cast<float*>(smem);
-  double2* CF = reinterpret_cast<double2*>(smem + SC_EPI_CF);
-  constexpr int EP = SC_W == 4 ? 2 : 4, ECOL = SC_BN / EP;  // threads per row, columns per thread
-  const int erow = tid / EP, epart = tid % EP;
-  auto tcol = [](int c) { return (c & ~63) + (((c & 63) + 16 * (c >> 6)) & 63); };
-  if (tid < SC_BN) CF[tid + (tid >> 6)] = make_double2(sv.cscale[n0 + tid], sv.csum[n0 + tid]);
-#pragma unroll
-  for (int ph = 0; ph < 2; ++ph) {
-    if (ph) __syncthreads();  // phase 0's readers are done with T
-    if ((wr >> 7) == ph) {
-#pragma unroll
-      for (int i = 0; i < SC_NI; ++i)
-#pragma unroll
-        for (int j = 0; j < SC_NJ; ++j)
-#pragma unroll
-          for (int q = 0; q < 4; ++q)
-            *reinterpret_cast<float4*>(T + ((wr & 127) + 32 * i + (lane & 31)) * SC_LDE + tcol(wc + 32 * j + 8 * q + 4 * (lane >> 5))) =
-                make_float4(acc[i][j][4 * q], acc[i][j][4 * q + 1], acc[i][j][4 * q + 2], acc[i][j][4 * q + 3]);
-    }
-    __syncthreads();
-    if (tid < 128 * EP) {  // 16 waves: the first 8 sum (the same column split and order)
-      const float* Tr = T + erow * SC_LDE;
-      double sum = 0.0;
-#pragma unroll 4
-      for (int c = 0; c < ECOL / 4; ++c) {
-        const int c0 = ECOL * epart + 4 * c;  // 4 columns inside one 64-column share
-        const float4 v = *reinterpret_cast<const float4*>(Tr + tcol(c0));
-        const double2* p = CF + c0 + (c0 >> 6);
-        const double2 p0 = p[0], p1 = p[1], p2 = p[2], p3 = p[3];
-        const double x0 = fma((double)v.x, p0.x, p0.y), x1 = fma((double)v.y, p1.x, p1.y),
-                     x2 = fma((double)v.z, p2.x, p2.y), x3 = fma((double)v.w, p3.x, p3.y);
-        sum = fma(x0, x0, sum);
-        sum = fma(x1, x1, sum);
-        sum = fma(x2, x2, sum);
-        sum = fma(x3, x3, sum);
-      }
-#pragma unroll
-      for (int w = 1; w < EP; w <<= 1) sum += __shfl_xor(sum, w);
-      if (epart == 0) partial[(int64_t)nt * M_pad + m0 + 128 * ph + erow] = sum;
     }
   }
 }

@@ -23,8 +23,7 @@
 //     needs, the faces' slab bounds per lane, and evaluates only the (lane, face) pairs a lane needs,
 //     packed 64 to a round (ballot/mbcnt into LDS, an LDS 64-bit minimum on (distance bits, face index)
 //     into the owner's best).  Runs and the shared top mask: config-4 forward 0.71 → 0.61 ms (points
-//     around the mesh) and 0.775 → 0.725 ms (far), CDX_SDF_NO_RUNS / CDX_SDF_NO_TMASK build the A/B
-//     (profiles/r05l_sdf_runs_tmask_ab.jsonl).
+//     around the mesh) and 0.775 → 0.725 ms (far) (profiles/r05l_sdf_runs_tmask_ab.jsonl).
 // A skip needs bound·(1 − α) − β > sqrt(best): α = 1e-4 + 1e-5·κ (κ = the worst face's 1/sinθ in the
 // node; α ≥ 1 or a NaN κ never skips) and β = (1e-4 + 1e-8·κ)·(|p| + |c| + 3R) exceed every rounding error
 // of point_face and of the bound (tests/test_sdf_bounds_cpu.py), so a skipped face's computed
@@ -333,36 +332,6 @@ __global__ __launch_bounds__(64) void sdf_node_kernel(const cdx::FaceRec* __rest
   out[blockIdx.x] = nd;
 }
 
-// Reference tile rule for one point over all faces (uniform face loads); writes outputs.
-__device__ void exact_point(cdx::F3 p, const float* __restrict__ faces, int64_t F, int64_t pi, float* out_dist,
-                            int32_t* out_sign, float* out_nrm, float* out_clst, int32_t* out_face, bool write) {
-  float best = 0.f;
-  int bsign = 0, bface = -1;
-  cdx::F3 bn = cdx::f3(0.f, 0.f, 0.f), bc = bn;
-  for (int64_t f0 = 0; f0 < F; f0 += SDF_TILE) {
-    const int nt = (int)min((int64_t)SDF_TILE, F - f0);
-    float tbest = 0.f;
-    int tsign = 0, tface = -1;
-    cdx::F3 tn = cdx::f3(0.f, 0.f, 0.f), tc = tn;
-    for (int s = 0; s < nt; ++s) {
-      const float* v = faces + 9 * (f0 + s);
-      cdx::F3 c, n;
-      int sg;
-      const float d = cdx::point_face(p, cdx::f3(v[0], v[1], v[2]), cdx::f3(v[3], v[4], v[5]),
-                                      cdx::f3(v[6], v[7], v[8]), c, n, sg);
-      if (s == 0 || tbest > d) { tbest = d; tsign = sg; tn = n; tc = c; tface = (int)(f0 + s); }
-    }
-    if (f0 == 0 || best > tbest) { best = tbest; bsign = tsign; bn = tn; bc = tc; bface = tface; }
-  }
-  if (!write) return;
-  out_dist[pi] = best;
-  out_sign[pi] = bsign;
-  out_nrm[3 * pi] = bn.x; out_nrm[3 * pi + 1] = bn.y; out_nrm[3 * pi + 2] = bn.z;
-  out_clst[3 * pi] = bc.x; out_clst[3 * pi + 1] = bc.y; out_clst[3 * pi + 2] = bc.z;
-  if (out_face) out_face[pi] = bface;
-}
-
-
 // The reference tile rule for lane b's point with the faces split over the wave's lanes (all 64 lanes call it):
 // per 512-face tile, the sequential rule `s == 0 || best > d` picks the tile's first face when its distance is NaN,
 // else the first minimum over the tile's non-NaN distances — a (distance, face) minimum over the lanes' partial
@@ -470,12 +439,7 @@ constexpr int REC_WORDS = sizeof(cdx::FaceRec) / 4;  // 40
 static_assert(REC_WORDS * CHUNK % (64 * 4) == 0, "a chunk's records load as whole dwordx4 per lane");
 constexpr int REC_V4 = REC_WORDS * CHUNK / (64 * 4);   // dwordx4 loads per lane per chunk (5)
 static_assert(sizeof(Slab) * CHUNK == 64 * 16, "a chunk's slabs load as one dwordx4 per lane");
-#if defined(CDX_SDF_CHUNKS_LDS)
-constexpr int NODES_LDS = 512;  // chunk nodes staged in LDS (F ≤ 16 384 faces): 2 waves per SIMD, slower (r05f)
-#else
-constexpr int NODES_LDS = 0;    // chunk nodes loaded per visited top node (the wave's share, one vector load)
-#endif
-constexpr int TOPS_LDS = 64;    // top nodes staged in LDS
+constexpr int TOPS_LDS = 64;    // top nodes staged in LDS (chunk nodes: loaded per visited top node, the wave's share)
 
 // (distance, face) as one unsigned 64-bit word whose order is the winner rule's: a non-negative float's
 // bits order as unsigned integers, ties then go to the smaller index.
@@ -487,13 +451,8 @@ __device__ inline unsigned long long pack_best(float d, int idx) {
 // the work — the greedy seed's tops / chunks / faces NW ways, then the chunks of every top node some lane
 // cannot rule out (wave w takes chunks w, w + NW, … of the top) — and share each point's packed best in LDS,
 // so a face one wave evaluates tightens the bounds the others test.  Grid: ⌈P/64⌉ workgroups of NW waves.
-#ifndef CDX_SDF_NW
-#define CDX_SDF_NW 4
-#endif
-constexpr int NW = CDX_SDF_NW;     // waves per point group
-#ifndef CDX_SDF_MINW
-#define CDX_SDF_MINW 5  // waves per SIMD the tree kernel is compiled for: 96 VGPRs, 30.7 KB LDS per group → 5 (1: 101 VGPRs, 4)
-#endif
+constexpr int NW = 4;              // waves per point group
+constexpr int SDF_MINW = 5;        // waves per SIMD the tree kernel is compiled for: 96 VGPRs, 30.7 KB LDS per group → 5
 constexpr int CPW = TOPB / NW;     // chunks of a top node per wave
 static_assert(TOPB % NW == 0 && CHUNK % NW == 0, "waves split a top's chunks and a chunk's faces evenly");
 #if defined(CDX_SDF_DIAG)
@@ -519,7 +478,7 @@ __device__ __forceinline__ void sdf_tree_body(
   __shared__ float4 s_slab[NW][2 * CHUNK];             // … and its face slabs
   __shared__ float4 s_run[NW][3 * RPC];               // … and its runs' nodes
   __shared__ unsigned long long s_tmask;              // top nodes some lane cannot rule out (T ≤ 64)
-  __shared__ float4 s_node[3 * (NODES_LDS + TOPS_LDS)];  // chunk nodes, then top nodes (when they fit)
+  __shared__ float4 s_node[3 * TOPS_LDS];             // the top nodes (when they fit)
   __shared__ float4 s_cn[NW][3 * CPW];                // per wave: its CPW chunk nodes of the current top node
   __shared__ unsigned long long s_best[64];           // the group's packed (distance, face) best per point
   __shared__ unsigned short s_pair[NW][128];           // per wave: pending (lane << 5 | face) pairs
@@ -529,37 +488,27 @@ __device__ __forceinline__ void sdf_tree_body(
   int (*s_sel)[64] = reinterpret_cast<int (*)[64]>(reinterpret_cast<float*>(&s_rec[0][0]) + NW * 64);
   const int lane = threadIdx.x & 63;
   const int w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  // the upper levels of the hierarchy in LDS: one coalesced copy per workgroup instead of a dependent load per
-  // node test (the tests then read LDS; a mesh with more nodes reads the rest from global memory)
-  const bool chunks_lds = C <= NODES_LDS, tops_lds = T <= TOPS_LDS;
+  // the top level of the hierarchy in LDS: one coalesced copy per workgroup instead of a dependent load per
+  // node test (the tests then read LDS; a mesh with more top nodes reads them from global memory)
+  const bool tops_lds = T <= TOPS_LDS;
   {
-    const float4* cs = reinterpret_cast<const float4*>(chunk);
     const float4* ts = reinterpret_cast<const float4*>(top);
-    if (chunks_lds)
-      for (int i = threadIdx.x; i < 3 * C; i += 64 * NW) s_node[i] = cs[i];
     if (tops_lds)
-      for (int i = threadIdx.x; i < 3 * T; i += 64 * NW) s_node[3 * NODES_LDS + i] = ts[i];
+      for (int i = threadIdx.x; i < 3 * T; i += 64 * NW) s_node[i] = ts[i];
     __syncthreads();
   }
-  // the wave's chunks of top node t are t·16 + w + NW·i, i < CPW: staged per wave (one vector load) unless all
-  // chunk nodes are in LDS; wave_chunk(t, i) then reads LDS either way
+  // the wave's chunks of top node t are t·16 + w + NW·i, i < CPW: staged per wave (one vector load);
+  // wave_chunk(t, i) then reads LDS
   auto stage_chunks = [&](int t) {
-    if (chunks_lds) return;
     if (lane < 3 * CPW) {
       const int c = t * TOPB + w + NW * (lane / 3);
       s_cn[w][lane] = c < C ? reinterpret_cast<const float4*>(chunk)[3 * c + lane % 3] : make_float4(0.f, 0.f, 0.f, 0.f);
     }
     __builtin_amdgcn_wave_barrier();
   };
-  auto wave_chunk = [&](int t, int i) {
-    if (chunks_lds) {
-      const int c = t * TOPB + w + NW * i;
-      return Node{s_node[3 * c], s_node[3 * c + 1], s_node[3 * c + 2]};
-    }
-    return Node{s_cn[w][3 * i], s_cn[w][3 * i + 1], s_cn[w][3 * i + 2]};
-  };
+  auto wave_chunk = [&](int i) { return Node{s_cn[w][3 * i], s_cn[w][3 * i + 1], s_cn[w][3 * i + 2]}; };
   auto top_node = [&](int t) {
-    if (tops_lds) return Node{s_node[3 * (NODES_LDS + t)], s_node[3 * (NODES_LDS + t) + 1], s_node[3 * (NODES_LDS + t) + 2]};
+    if (tops_lds) return Node{s_node[3 * t], s_node[3 * t + 1], s_node[3 * t + 2]};
     return load_node(top, t);
   };
   const int64_t j = grp * 64 + lane;
@@ -569,14 +518,6 @@ __device__ __forceinline__ void sdf_tree_body(
   const bool ok = fabsf(p0.x) <= PT_LIM && fabsf(p0.y) <= PT_LIM && fabsf(p0.z) <= PT_LIM;
   const unsigned long long badm = __ballot(!ok);  // same points in every wave: uniform over the workgroup
   if (badm) {
-#if defined(CDX_SDF_EXACT_GROUP)  // (A/B: the whole group by the tile rule, one point per lane of wave 0)
-    if (w == 0) {
-      exact_point(p0, faces, F, pi, out_dist, out_sign, out_nrm, out_clst, out_face, live0);
-      if (count && lane == 0)
-        atomicAdd(&g_sdf_stats[1], (unsigned long long)F * (unsigned long long)__popcll(__ballot(live0)));
-    }
-    return;
-#else
     // a non-finite or out-of-range point (an optimiser's diverged candidate) takes the reference's tile rule, its
     // faces split over the lanes of one wave (the waves take such points in turn); the group's other points walk
     // the tree as usual
@@ -605,7 +546,6 @@ __device__ __forceinline__ void sdf_tree_body(
     if (count && threadIdx.x == 0)  // (the brute-force pairs the tile rule stands for, NaN points included)
       atomicAdd(&g_sdf_stats[1], (unsigned long long)F * (unsigned long long)__popcll(badm & __ballot(live0)));
     if (!~badm) return;
-#endif
   }
   // the walk: a bad lane shadows the first good lane's point and writes nothing
   const int sh = __builtin_ctzll(~badm);
@@ -639,16 +579,9 @@ __device__ __forceinline__ void sdf_tree_body(
   {
     float cl = INFINITY;
     int cs = 0x7fffffff;
-    if (!chunks_lds) {  // (a per-lane top: each lane loads its own 4 nodes)
-      for (int i = 0; i < CPW; ++i) {
-        const int c = tsel * TOPB + w + NW * i;
-        if (c < C) sel_min(cl, cs, node_lb(p, load_node(chunk, c)), c);
-      }
-    } else {
-      for (int i = 0; i < CPW; ++i) {
-        const int c = tsel * TOPB + w + NW * i;
-        if (c < C) sel_min(cl, cs, node_lb(p, Node{s_node[3 * c], s_node[3 * c + 1], s_node[3 * c + 2]}), c);
-      }
+    for (int i = 0; i < CPW; ++i) {  // (a per-lane top: each lane loads its own 4 nodes)
+      const int c = tsel * TOPB + w + NW * i;
+      if (c < C) sel_min(cl, cs, node_lb(p, load_node(chunk, c)), c);
     }
     csel = merge(cl, cs);
     if (csel >= C) csel = tsel * TOPB;
@@ -679,11 +612,7 @@ __device__ __forceinline__ void sdf_tree_body(
   const cdx::FaceRec* rr = reinterpret_cast<const cdx::FaceRec*>(buf);
   // the top nodes some lane cannot rule out against the seeds, tested once per workgroup (waves split them) when
   // they fit one mask word; each is re-tested against the current best before its chunks are walked
-#if defined(CDX_SDF_NO_TMASK)
-  const bool shared_tops = false;
-#else
   const bool shared_tops = tops_lds && T <= 64;
-#endif
   if (shared_tops) {
     if (threadIdx.x == 0) s_tmask = 0ull;
     __syncthreads();
@@ -700,7 +629,7 @@ __device__ __forceinline__ void sdf_tree_body(
     for (int i = 0; i < CPW; ++i) {
       const int c = t * TOPB + w + NW * i;
       if (c >= C) break;
-      const Node cn = wave_chunk(t, i);
+      const Node cn = wave_chunk(i);
       const float sb = bsqrt(best_now());
       if (!__any(node_needed(p, cn, sb, pnorm))) continue;
       // the chunk's face slabs (one dwordx4 per lane) and records (5 per lane) in flight together, into the
@@ -708,17 +637,7 @@ __device__ __forceinline__ void sdf_tree_body(
       {
         static_assert(REC_V4 == 5, "five record loads per lane");
         const float4* rc = rec4 + (int64_t)c * (REC_WORDS * CHUNK / 4) + lane;
-#if defined(CDX_SDF_REG_STAGE)  // (A/B: through registers — 28 VGPRs in flight)
-        const float4 v0 = rc[0], v1 = rc[64], v2 = rc[128], v3 = rc[192], v4 = rc[256];
-        const float4 sv = reinterpret_cast<const float4*>(slab)[(int64_t)c * 2 * CHUNK + lane];
-        const float4 rv = lane < 3 * RPC ? reinterpret_cast<const float4*>(run)[(int64_t)c * 3 * RPC + lane]
-                                         : make_float4(0.f, 0.f, 0.f, 0.f);
-        __builtin_amdgcn_wave_barrier();
-        s_slab[w][lane] = sv;
-        if (lane < 3 * RPC) s_run[w][lane] = rv;
-        buf[lane] = v0; buf[lane + 64] = v1; buf[lane + 128] = v2; buf[lane + 192] = v3; buf[lane + 256] = v4;
-        __builtin_amdgcn_wave_barrier();
-#else  // LDS-DMA (global_load_lds_dwordx4: lane l's 16 bytes to base + 16·l, no VGPRs, no ds_write)
+        // LDS-DMA (global_load_lds_dwordx4: lane l's 16 bytes to base + 16·l, no VGPRs, no ds_write)
         typedef __attribute__((address_space(3))) void* lds_ptr;
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // (the previous chunk's LDS reads are done)
         __builtin_amdgcn_wave_barrier();
@@ -731,7 +650,6 @@ __device__ __forceinline__ void sdf_tree_body(
         for (int q = 0; q < REC_V4; ++q) __builtin_amdgcn_global_load_lds(rc + 64 * q, (lds_ptr)(buf + 64 * q), 16, 0, 0);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __builtin_amdgcn_wave_barrier();
-#endif
       }
       // the chunk's faces a lane cannot rule out: the runs first (their own nodes), then the slab bound of each
       // face of a run some lane needs, against the chunk's threshold (its margins)
@@ -742,10 +660,8 @@ __device__ __forceinline__ void sdf_tree_body(
 #pragma unroll
       for (int rr = 0; rr < RPC; ++rr) {
         if (rr * RUN >= nf) break;
-#if !defined(CDX_SDF_NO_RUNS)
         const Node rn = Node{s_run[w][3 * rr], s_run[w][3 * rr + 1], s_run[w][3 * rr + 2]};
         if (!__any(node_needed(p, rn, sb, pnorm))) continue;
-#endif
 #pragma unroll
         for (int kk = 0; kk < RUN; ++kk) {
           const int k = RUN * rr + kk;
@@ -834,7 +750,7 @@ __device__ __forceinline__ void sdf_tree_body(
   if (out_face) out_face[pi] = bidx;
 }
 
-__global__ __launch_bounds__(64 * NW, CDX_SDF_MINW) void sdf_tree_kernel(
+__global__ __launch_bounds__(64 * NW, SDF_MINW) void sdf_tree_kernel(
     const float* __restrict__ points, int64_t P, const int* __restrict__ porder, const float* __restrict__ faces,
     int64_t F, const cdx::FaceRec* __restrict__ rec, const Slab* __restrict__ slab, const Node* __restrict__ chunk,
     const Node* __restrict__ top, const Node* __restrict__ run, int C, int T, const unsigned* __restrict__ ws,
@@ -878,7 +794,7 @@ struct SdfBatch {
 // later, an optimiser step away — start first and the light ones fill the tail.  Any permutation gives the same
 // outputs: every group writes only its own points.
 constexpr int SDF_SCHED_HDR = 4;
-__global__ __launch_bounds__(64 * NW, CDX_SDF_MINW) void sdf_tree_batch_kernel(SdfBatch b) {
+__global__ __launch_bounds__(64 * NW, SDF_MINW) void sdf_tree_batch_kernel(SdfBatch b) {
   // the descriptors read in place from the kernel-argument segment (indexed per workgroup, a by-value copy would go
   // to scratch)
   const SdfBatch& kb = *(const SdfBatch*)(__builtin_amdgcn_kernarg_segment_ptr());

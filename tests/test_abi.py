@@ -38,6 +38,27 @@ def test_shipped_library_ignores_ab_switches():
     assert "CDX_AB_SWITCHES" not in DEFAULT_DEFINES
 
 
+def test_build_macros_are_the_documented_ones():
+    """The product is a plain compile of csrc/ (no -D), and the only CDX_* macros a preprocessor conditional there
+    tests are the ones DESIGN.md §2a lists under "Build macros": CDX_AB_SWITCHES and the timing-only diagnostic
+    builds.  A measured-and-lost variant kept behind a new macro fails here."""
+    from compliancedex_amd.build import CSRC, DEFAULT_DEFINES
+    assert tuple(DEFAULT_DEFINES) == ()
+    used = set()
+    for name in os.listdir(CSRC):
+        for line in open(os.path.join(CSRC, name), encoding="utf-8"):
+            if re.match(r"\s*#\s*(if|ifdef|ifndef|elif)\b", line):
+                used |= set(re.findall(r"\bCDX_[A-Z0-9_]+", line))
+    design = open(os.path.join(REPO, "DESIGN.md"), encoding="utf-8").read()
+    section = design.split("### Build macros", 1)[1].split("\n#", 1)[0]
+    documented = set()
+    for row in section.splitlines():
+        if row.startswith("| `CDX_"):
+            documented |= set(re.findall(r"`(CDX_[A-Z0-9_]+)`", row.split("|")[1]))
+    assert "CDX_AB_SWITCHES" in documented
+    assert used == documented, (sorted(used - documented), sorted(documented - used))
+
+
 def test_bad_arguments_are_rejected_without_launch():
     import ctypes
     from compliancedex_amd import _native as N

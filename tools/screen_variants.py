@@ -13,16 +13,8 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-BASE = ("CDX_FAST_SQRT", "CDX_STD_SCHED")
+BASE = ()
 VARIANTS = {"base": BASE,
-            "sub1": BASE + ("CDX_SC_SUB=1",),  # 16-K stages (one barrier per 16 K rows)
-            "ring3": BASE + ("CDX_SC_RING=3",),  # 32-K stages, B DMA'd two stages ahead (160 KB LDS)
-            "prio_young": BASE + ("CDX_SC_PRIO_YOUNG",),  # s_setprio 1 for waves 4-7 before the loop
-            "pp": BASE + ("CDX_SC_PP=1",),  # ping-pong: the two waves of a SIMD multiply in alternate half-stages
-            "w4": BASE + ("CDX_SC_WAVES=4",),  # 4 waves of 128 x 128 (one per SIMD, AGPR accumulators)
-            "w4_sub1": BASE + ("CDX_SC_WAVES=4", "CDX_SC_SUB=1"),
-            "w16": BASE + ("CDX_SC_WAVES=16",),  # 16 waves of 64 x 64 (four per SIMD, <= 128 registers)
-            "w16_ring3": BASE + ("CDX_SC_WAVES=16", "CDX_SC_RING=3"),
             "diag_noread": BASE + ("CDX_SC_DIAG_NOREAD",),      # MFMAs on fragments read once per stage
             "diag_nobar": BASE + ("CDX_SC_DIAG_NOBAR",),        # no s_barrier in the loop (races)
             "diag_nodma": BASE + ("CDX_SC_DIAG_NODMA",),        # no B DMAs in the loop
@@ -31,9 +23,7 @@ VARIANTS = {"base": BASE,
             "diag_nogen_nomfma": BASE + ("CDX_SC_DIAG_NOGEN", "CDX_SC_DIAG_NOMFMA"),
             # MFMAs only: fragments from lane ids, no generation, no B DMA, no barrier
             "diag_mfma_only": BASE + ("CDX_SC_DIAG_NOREAD", "CDX_SC_DIAG_NOGEN", "CDX_SC_DIAG_NODMA", "CDX_SC_DIAG_NOBAR"),
-            "diag_noepi": BASE + ("CDX_SC_DIAG_NOEPI",),  # no epilogue (Σ (Ṽ + c)² through LDS)
-            "epireg": BASE + ("CDX_SC_EPI_REG=1",),  # epilogue summed from the accumulator registers
-            "epilds": BASE + ("CDX_SC_EPI_REG=0",),  # epilogue through the LDS image
+            "diag_noepi": BASE + ("CDX_SC_DIAG_NOEPI",),  # no epilogue (Σ (Ṽ + c)² from the accumulators)
             "diag_noread_nogen": BASE + ("CDX_SC_DIAG_NOREAD", "CDX_SC_DIAG_NOGEN"),
             "diag_noread_nodma": BASE + ("CDX_SC_DIAG_NOREAD", "CDX_SC_DIAG_NODMA")}
 # measured and dropped (profiles/r02j_screen_variants.jsonl): sched_group_barrier 1 MFMA : 6 VALU
@@ -57,7 +47,7 @@ def build():
         if src == "cdx_screen.hip":
             continue
         obj = os.path.join(tmp, src.replace(".hip", ".o"))
-        extra = ["-ffp-contract=off"] if src in ("cdx_sdf.hip", "cdx_closure.hip") else []
+        extra = ["-ffp-contract=off"] if src in B.FP_CONTRACT_OFF else []
         B._run([B.HIPCC, *_flags(B, BASE), *extra, "-c", os.path.join(B.CSRC, src), "-o", obj])
         common.append(obj)
     for name, defs in VARIANTS.items():

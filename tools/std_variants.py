@@ -15,26 +15,19 @@ import sys
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, REPO)
-VARIANTS = {"wn4": ("CDX_FAST_SQRT", "CDX_STD_SCHED"),               # default build
-            "wn4_nosched": ("CDX_FAST_SQRT",),
-            "gensqrtfull": ("CDX_FAST_SQRT", "CDX_STD_SCHED", "CDX_GEN_SQRT_FULL"),  # full sqrt in K* generation
-            "kload": ("CDX_FAST_SQRT", "CDX_STD_SCHED", "CDX_VAR_KLOAD"),  # whitened pass reads a K* buffer
-            "nodiag": ("CDX_FAST_SQRT", "CDX_STD_SCHED", "CDX_STD_NODIAG"),  # no diagonal-block MFMA trimming
-            "old2buf": None,                                       # prebuilt older library, not rebuilt
-            "diag_nogen": ("CDX_FAST_SQRT", "CDX_STD_SCHED", "CDX_DIAG_NOGEN"),
-            "diag_nomfma": ("CDX_FAST_SQRT", "CDX_STD_SCHED", "CDX_DIAG_NOMFMA"),
-            "diag_nobload": ("CDX_FAST_SQRT", "CDX_STD_SCHED", "CDX_DIAG_NOBLOAD"),
-            "diag_wgtime": ("CDX_FAST_SQRT", "CDX_STD_SCHED", "CDX_DIAG_WGTIME"),
-            "diag_nobload_nogen": ("CDX_FAST_SQRT", "CDX_STD_SCHED", "CDX_DIAG_NOBLOAD", "CDX_DIAG_NOGEN")}
-if os.environ.get("CDX_VARIANTS"):  # e.g. CDX_VARIANTS=wn4,t4_nosched
+VARIANTS = {"wn4": (),                                             # default build
+            "diag_nogen": ("CDX_DIAG_NOGEN",),
+            "diag_nomfma": ("CDX_DIAG_NOMFMA",),
+            "diag_nobload": ("CDX_DIAG_NOBLOAD",),
+            "diag_wgtime": ("CDX_DIAG_WGTIME",),
+            "diag_nobload_nogen": ("CDX_DIAG_NOBLOAD", "CDX_DIAG_NOGEN")}
+if os.environ.get("CDX_VARIANTS"):  # e.g. CDX_VARIANTS=wn4,diag_nogen
     VARIANTS = {k: v for k, v in VARIANTS.items() if k in os.environ["CDX_VARIANTS"].split(",")}
 
 
 def build():
     from compliancedex_amd.build import build_device
     for name, defs in VARIANTS.items():
-        if defs is None:
-            continue
         build_device(force=True, defines=defs, out_name=f"libcdx_{name}.so")
 
 
