@@ -58,6 +58,9 @@ static_assert(MEAN_BLOCK == 256, "the mean kernel's moment reduction assumes 4 w
 // below its own distance from the reference's f64 autograd (1.3e-12 on the banana state, 2.3e-13 on the
 // synthetic one; tools/root_precision.py, profiles/r04g_root_precision.jsonl).
 // The moments are summed by the staging threads (one point each per block), then over the workgroup.
+// GRAD false (gpis_mean_only_kernel: a lattice field's mean, nobody reads ∇mean): the per-pair loop drops the three
+// Σ (αr) d accumulations; the mean's own operations and their order are the same, so it has the same bits.
+template <bool GRAD = true>
 __device__ __forceinline__ void mean_tps_moments(const cdx_gpis& g, int64_t M, int64_t m, double x0, double x1,
                                                  double x2, double* __restrict__ mean, double* __restrict__ gmean,
                                                  double* __restrict__ normal, dbl4* sp) {
@@ -88,17 +91,21 @@ __device__ __forceinline__ void mean_tps_moments(const cdx_gpis& g, int64_t M, i
       const double r2 = dx * dx + dy * dy + dz * dz;
       const double ar = p.w * cdx::sqrt_r2_f32seed(r2);  // f32 seed + one f64 Newton step (≈ 2⁻⁴⁵ relative)
       a3 += ar * r2;
-      h0 += ar * dx;
-      h1 += ar * dy;
-      h2 += ar * dz;
+      if constexpr (GRAD) {
+        h0 += ar * dx;
+        h1 += ar * dy;
+        h2 += ar * dz;
+      }
     }
   }
 #pragma unroll
   for (int w = 1; w < MEAN_SPLIT; w <<= 1) {
     a3 += __shfl_xor(a3, w);
-    h0 += __shfl_xor(h0, w);
-    h1 += __shfl_xor(h1, w);
-    h2 += __shfl_xor(h2, w);
+    if constexpr (GRAD) {
+      h0 += __shfl_xor(h0, w);
+      h1 += __shfl_xor(h1, w);
+      h2 += __shfl_xor(h2, w);
+    }
   }
   // workgroup sums of the five moments: wave reduction, then the four waves' partials through LDS
 #pragma unroll
@@ -128,6 +135,7 @@ __device__ __forceinline__ void mean_tps_moments(const cdx_gpis& g, int64_t M, i
   const double qx = x0 - c0, qy = x1 - c1, qz = x2 - c2;
   const double sr2 = (qx * qx + qy * qy + qz * qz) * s0 - 2.0 * (qx * s1x + qy * s1y + qz * s1z) + s2;
   mean[m] = 2.0 * a3 - 3.0 * R * sr2 + R * R * R * s0 + g.bias;
+  if constexpr (!GRAD) return;
   const double gx = 6.0 * h0 - 6.0 * R * (qx * s0 - s1x);
   const double gy = 6.0 * h1 - 6.0 * R * (qy * s0 - s1y);
   const double gz = 6.0 * h2 - 6.0 * R * (qz * s0 - s1z);
@@ -193,6 +201,16 @@ __global__ __launch_bounds__(MEAN_BLOCK) void gpis_mean_kernel(cdx_gpis g, const
     const double nn = sqrt(g0 * g0 + g1 * g1 + g2 * g2) + 1e-8;
     normal[3 * m] = g0 / nn; normal[3 * m + 1] = g1 / nn; normal[3 * m + 2] = g2 / nn;
   }
+}
+
+// TPS mean alone (cdx::gpis_mean_only_launch): gpis_mean_kernel<TPS> without the gradient sums.
+__global__ __launch_bounds__(MEAN_BLOCK) void gpis_mean_only_kernel(cdx_gpis g, const double* __restrict__ X, int64_t M,
+                                                                    double* __restrict__ mean) {
+  __shared__ dbl4 sp[MEAN_BLOCK];
+  const int64_t m = (int64_t)blockIdx.x * MEAN_Q + threadIdx.x / MEAN_SPLIT;
+  double x0 = 0, x1 = 0, x2 = 0;
+  if (m < M) { x0 = X[3 * m]; x1 = X[3 * m + 1]; x2 = X[3 * m + 2]; }
+  mean_tps_moments<false>(g, M, m, x0, x1, x2, mean, nullptr, nullptr, sp);
 }
 
 // ------------------------------------------------------------------ std (MFMA)
@@ -1388,6 +1406,17 @@ int gpis_refine_launch(const cdx_gpis& g, const double* X, const int* rows, cons
   }
   if (partial_out) *partial_out = partial;
   if (M_pad_out) *M_pad_out = M_pad;
+  return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;
+}
+
+int gpis_mean_only_launch(const cdx_gpis& g, const double* X, int64_t M, double* mean, hipStream_t s) {
+  if (g.kernel != CDX_KERNEL_TPS) return cdx_gpis_mean(&g, X, M, mean, nullptr, nullptr, reinterpret_cast<cdx_stream_t>(s));
+  if (!gpis_ok(&g) || M < 0 || (M > 0 && (!X || !mean))) return CDX_EINVAL;
+  if (M == 0) return CDX_OK;
+  prof_mark(PROF_GPIS_MEAN, true, s);
+  hipLaunchKernelGGL(gpis_mean_only_kernel, dim3((unsigned)((M + MEAN_Q - 1) / MEAN_Q)), dim3(MEAN_BLOCK), 0, s, g, X, M,
+                     mean);
+  prof_mark(PROF_GPIS_MEAN, false, s);
   return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;
 }
 

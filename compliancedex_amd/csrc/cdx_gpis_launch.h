@@ -6,6 +6,9 @@
 #include "cdx.h"
 
 namespace cdx {
+// The mean alone at M queries, for callers that read neither ∇mean nor the normal (cdx_gpis_field): the TPS kernel
+// without its gradient sums — the same bits as cdx_gpis_mean's mean; other kernels take cdx_gpis_mean.
+int gpis_mean_only_launch(const cdx_gpis& g, const double* X, int64_t M, double* mean, hipStream_t s);
 size_t gpis_var_ws_bytes(const cdx_gpis& g, int64_t M);
 size_t gpis_grad_ws_bytes(const cdx_gpis& g, int64_t M);
 // Bytes of the stored whitened vectors V = (L⁻¹K*ᵀ)ᵀ of M queries ([round_up(M, 128), N_pad] f64).

@@ -1,5 +1,5 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
-// cdx_sdf.h / cdx_gpis_mode.h.
+// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
@@ -8,6 +8,7 @@
 
 #include "cdx_collision.h"
 #include "cdx_cost.h"
+#include "cdx_field.h"
 #include "cdx_gpis_mode.h"
 #include "cdx_sdf.h"
 
@@ -34,6 +35,29 @@ struct HostGpis {
     return p;
   }
 };
+
+// GPIS.topcd (gpis.py:127-150) as a plain loop over the shared cell rule: the surface cells in C order of (i, j, k)
+// (the order of numpy's boolean-mask indexing, :147-149), at most `capacity` rows written.
+template <typename T>
+int64_t surface_extract(const T* mean, const T* normal, int steps, int flip_k, const double* px, const double* py,
+                        const double* pz, int64_t capacity, int64_t* cells, double* points, T* normals) {
+  int64_t n = 0;
+  for (int i = 1; i < steps - 1; ++i)
+    for (int j = 1; j < steps - 1; ++j)
+      for (int k = 1; k < steps - 1; ++k) {
+        if (!cdx::field_surface_cell(mean, steps, i, j, k, flip_k)) continue;
+        if (n < capacity) {
+          if (cells) cells[n] = ((int64_t)i * steps + j) * steps + k;
+          if (points) { points[3 * n] = px[j]; points[3 * n + 1] = py[i]; points[3 * n + 2] = pz[k]; }
+          if (normal && normals) {
+            const int64_t src = cdx::field_src(steps, i, j, k, flip_k);
+            for (int d = 0; d < 3; ++d) normals[3 * n + d] = normal[3 * src + d];
+          }
+        }
+        ++n;
+      }
+  return n;
+}
 
 }  // namespace
 
@@ -243,6 +267,22 @@ void cdxh_face_dist2(const float* points, const float* faces, int64_t n, float* 
     int sg;
     d_ref[i] = cdx::point_face(p, v1, v2, v3, c, nrm, sg);
   }
+}
+
+// Host build of cdx_gpis_surface_count + cdx_gpis_surface_place (same arguments, host pointers): returns the full
+// count of surface cells, or CDX_EINVAL.  tests/test_field_cpu.py checks it against the reference's topcd outputs.
+int64_t cdxh_surface_extract(const void* mean, const void* normal, int32_t dtype, int32_t steps, int32_t flip_k,
+                             const double* px, const double* py, const double* pz, int64_t capacity, int64_t* cells,
+                             double* points, void* normals) {
+  if (!mean || steps < 1 || steps > CDX_FIELD_MAX_STEPS || capacity < 0 || (points && (!px || !py || !pz)))
+    return CDX_EINVAL;
+  if (dtype == CDX_DTYPE_F32)
+    return surface_extract(static_cast<const float*>(mean), static_cast<const float*>(normal), steps, flip_k, px, py,
+                           pz, capacity, cells, points, static_cast<float*>(normals));
+  if (dtype == CDX_DTYPE_F64)
+    return surface_extract(static_cast<const double*>(mean), static_cast<const double*>(normal), steps, flip_k, px, py,
+                           pz, capacity, cells, points, static_cast<double*>(normals));
+  return CDX_EINVAL;
 }
 
 }  // extern "C"

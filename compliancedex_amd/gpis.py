@@ -2,8 +2,13 @@
 
 Same constructor, attributes (``R, X1, y1, E11, bias, sigma, noise``), state files and
 methods (``fit``, ``pred``, ``compute_normal``, ``compute_multinormals``,
-``save_state_data``, ``load_state_data``, ``get_visualization_data``).  Queries run on the
+``save_state_data``, ``load_state_data``, ``get_visualization_data``, ``topcd``).  Queries run on the
 gfx950 kernels (cdx_gpis_mean / cdx_gpis_std); there is no CPU path.
+
+Beyond the reference: ``field`` evaluates mean / std / normal on a whole lattice in one native call
+(``get_visualization_data(fused=True)`` is that plus one copy back), ``topcd`` compacts the surface cells on
+the device (cdx_gpis_surface_count / _place, the reference's triple Python loop), and ``surface`` chains the
+two without the lattice leaving the device.
 
 Differences in *how*, not *what*: ``fit`` builds R and E11 with cdx_gpis_fit, and L⁻¹ (E11 = LLᵀ),
 E11⁻¹ and α = L⁻ᵀL⁻¹y1 are factored once per state on the device by cdx_gpis_factor (blocked
@@ -361,8 +366,16 @@ class GPIS:
         weights = torch.hstack(weights)
         return torch.stack(normals, dim=1), weights / weights.sum()
 
-    def get_visualization_data(self, lb, ub, steps=100):
-        """Mean / std / normal on a steps³ grid (gpis.py:113-125)."""
+    def get_visualization_data(self, lb, ub, steps=100, fused=False):
+        """Mean / std / normal on a steps³ grid (gpis.py:113-125).  ``fused=True`` evaluates the whole grid with
+        one ``field`` call and one copy back instead of three kernel chains and three copies per slice."""
+        if fused:
+            with torch.no_grad():
+                m, v, nrm = self.field(lb, ub, steps)
+                out = torch.cat([m.reshape(-1), v.reshape(-1), nrm.reshape(-1)]).float().cpu().numpy()
+            n = steps ** 3
+            return (out[:n].reshape(steps, steps, steps), out[n:2 * n].reshape(steps, steps, steps),
+                    out[2 * n:].reshape(steps, steps, steps, 3), np.asarray(lb), np.asarray(ub))
         dev = self.X1.device
         grid = torch.stack(torch.meshgrid(torch.linspace(lb[0], ub[0], steps), torch.linspace(lb[1], ub[1], steps),
                                           torch.linspace(lb[2], ub[2], steps), indexing="xy"), dim=3).double().to(dev)
@@ -376,3 +389,112 @@ class GPIS:
                 m[i] = mean.view(steps, steps).cpu()
                 v[i] = var.view(steps, steps).cpu()
         return m.numpy(), v.numpy(), nrm.numpy(), np.asarray(lb), np.asarray(ub)
+
+    # ------------------------------------------------- lattice field / surface
+    @staticmethod
+    def _check_steps(steps):
+        steps = int(steps)
+        if not 1 <= steps <= N.FIELD_MAX_STEPS:
+            raise ValueError(f"steps must be in 1..{N.FIELD_MAX_STEPS}, got {steps}")
+        return steps
+
+    def _query_axes(self, lb, ub, steps):
+        """The reference's query axes (gpis.py:114-116): float32 linspace, then double; [3, steps] on the device."""
+        ax = torch.stack([torch.linspace(float(lb[d]), float(ub[d]), steps) for d in range(3)]).double()
+        return ax.to(self.X1.device).contiguous()
+
+    def _point_axes(self, lb, ub, steps):
+        """topcd's point axes (gpis.py:144-146): float64 numpy linspace; [3, steps] on the device."""
+        lb, ub = np.asarray(lb), np.asarray(ub)
+        ax = np.stack([np.linspace(lb[d], ub[d], steps) for d in range(3)]).astype(np.float64)
+        return torch.from_numpy(ax).to(self.X1.device).contiguous()
+
+    def field(self, lb, ub, steps=100, std=True, normal=True, chunk=0):
+        """(mean [s, s, s], std [s, s, s] or None, normal [s, s, s, 3] or None), f64 on the device, on the lattice
+        of ``get_visualization_data``: cell (i, j, k) at (x[j], y[i], z[k]).  One cdx_gpis_field call: the cells go
+        through the mean kernel (mean and normal in one pass) and the whitened std pass ``chunk`` at a time
+        (0: a default that keeps the workspace under 1 GiB), with no host sync."""
+        steps = self._check_steps(steps)
+        if chunk < 0:
+            raise ValueError("chunk must be >= 0")
+        st = self.native_state()
+        dev = self.X1.device
+        lib = N.load()
+        ax = self._query_axes(lb, ub, steps)
+        mean = torch.empty(steps, steps, steps, dtype=torch.float64, device=dev)
+        sd = torch.empty(steps, steps, steps, dtype=torch.float64, device=dev) if std else None
+        nrm = torch.empty(steps, steps, steps, 3, dtype=torch.float64, device=dev) if normal else None
+        ws = torch.empty(max(lib.cdx_gpis_field_workspace(st.desc, steps, chunk), 1), dtype=torch.uint8, device=dev)
+        N.check(lib.cdx_gpis_field(st.desc, N.ptr(ax[0]), N.ptr(ax[1]), N.ptr(ax[2]), steps, chunk, N.ptr(mean),
+                                   N.ptr(sd), N.ptr(nrm), N.ptr(ws), N.stream_ptr(dev)), "cdx_gpis_field")
+        return mean, sd, nrm
+
+    def _surface_count(self, mean, dtype, steps, flip):
+        """count + scan on the stream; (workspace, the total: ONE host read)."""
+        lib = N.load()
+        dev = mean.device
+        ws = torch.empty(max(lib.cdx_gpis_surface_workspace(steps), 1), dtype=torch.uint8, device=dev)
+        total = torch.zeros(1, dtype=torch.int64, device=dev)
+        N.check(lib.cdx_gpis_surface_count(N.ptr(mean), dtype, steps, flip, N.ptr(ws), N.ptr(total),
+                                           N.stream_ptr(dev)), "cdx_gpis_surface_count")
+        return ws, int(total.item())
+
+    def topcd(self, test_mean, test_normal, lb, ub, steps=100):
+        """Surface point cloud of a lattice field (gpis.py:127-150): (points float64 [n, 3], normals [n, 3]) as
+        numpy — the interior cells with mean < 0 that have a face neighbour with mean ≥ 0, in C order.  Tensor
+        inputs are read flipped along k as the reference does (:130-133, the points are not); numpy inputs are
+        not.  Count and ordered placement run on the device (cdx_gpis_surface_count / _place)."""
+        steps = self._check_steps(steps)
+        _require_cuda(self.X1, "GPIS state")
+        dev = self.X1.device
+        flip = 1 if torch.is_tensor(test_mean) else 0
+        if torch.is_tensor(test_normal) != bool(flip):
+            raise TypeError("topcd takes test_mean and test_normal both as tensors or both as numpy arrays")
+        mean = (test_mean.detach() if flip else torch.from_numpy(np.ascontiguousarray(test_mean))).to(dev)
+        nrm = (test_normal.detach() if flip else torch.from_numpy(np.ascontiguousarray(test_normal))).to(dev)
+        if mean.dtype not in (torch.float32, torch.float64):
+            mean = mean.double()
+        nrm = nrm.to(mean.dtype).contiguous()
+        mean = mean.contiguous()
+        if tuple(mean.shape) != (steps,) * 3 or tuple(nrm.shape) != (steps,) * 3 + (3,):
+            raise ValueError(f"topcd expects mean [{steps}]*3 and normal [{steps}]*3 + [3], got "
+                             f"{tuple(mean.shape)} and {tuple(nrm.shape)}")
+        dtype = N.DTYPE_F32 if mean.dtype == torch.float32 else N.DTYPE_F64
+        ws, n = self._surface_count(mean, dtype, steps, flip)
+        points = torch.empty(n, 3, dtype=torch.float64, device=dev)
+        normals = torch.empty(n, 3, dtype=mean.dtype, device=dev)
+        if n:
+            pax = self._point_axes(lb, ub, steps)
+            N.check(N.load().cdx_gpis_surface_place(N.ptr(mean), N.ptr(nrm), dtype, steps, flip, N.ptr(pax[0]),
+                                                    N.ptr(pax[1]), N.ptr(pax[2]), N.ptr(ws), n, None, N.ptr(points),
+                                                    N.ptr(normals), N.stream_ptr(dev)), "cdx_gpis_surface_place")
+        return points.cpu().numpy(), normals.cpu().numpy()
+
+    def surface(self, lb, ub, steps=100):
+        """The surface cloud straight from the state: (points [n, 3], normals [n, 3]) f64 device tensors, the
+        cloud ``topcd`` gives for the numpy outputs of ``get_visualization_data`` without the lattice leaving the
+        device.  Mean only on the lattice (no std pass), count and placement of the surface cells, then normals
+        from one mean-kernel call on the surviving cells alone.  One host sync, for the count."""
+        steps = self._check_steps(steps)
+        st = self.native_state()
+        dev = self.X1.device
+        lib = N.load()
+        with torch.no_grad():
+            mean, _, _ = self.field(lb, ub, steps, std=False, normal=False)
+            ws, n = self._surface_count(mean, N.DTYPE_F64, steps, 0)
+            points = torch.empty(n, 3, dtype=torch.float64, device=dev)
+            normals = torch.empty(n, 3, dtype=torch.float64, device=dev)
+            if n:
+                pax = self._point_axes(lb, ub, steps)
+                qax = self._query_axes(lb, ub, steps)
+                cells = torch.empty(n, dtype=torch.int64, device=dev)
+                N.check(lib.cdx_gpis_surface_place(N.ptr(mean), None, N.DTYPE_F64, steps, 0, N.ptr(pax[0]),
+                                                   N.ptr(pax[1]), N.ptr(pax[2]), N.ptr(ws), n, N.ptr(cells),
+                                                   N.ptr(points), None, N.stream_ptr(dev)), "cdx_gpis_surface_place")
+                X = torch.empty(n, 3, dtype=torch.float64, device=dev)
+                N.check(lib.cdx_gpis_field_points(N.ptr(qax[0]), N.ptr(qax[1]), N.ptr(qax[2]), steps, N.ptr(cells), n,
+                                                  N.ptr(X), N.stream_ptr(dev)), "cdx_gpis_field_points")
+                m2 = torch.empty(n, dtype=torch.float64, device=dev)
+                N.check(lib.cdx_gpis_mean(st.desc, N.ptr(X), n, N.ptr(m2), None, N.ptr(normals), N.stream_ptr(dev)),
+                        "cdx_gpis_mean")
+        return points, normals

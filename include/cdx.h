@@ -130,6 +130,46 @@ size_t cdx_gpis_screen_workspace(const cdx_gpis* g, int64_t M);
 int cdx_gpis_screen_var(const cdx_gpis* g, const double* X, int64_t M, double* var, void* workspace,
                         cdx_stream_t stream);
 
+/* GPIS field on a lattice and its surface cells: get_visualization_data (gpis.py:113-125) and topcd (:127-150)
+ * on the device.  The lattice is steps³ cells in C order; cell (i, j, k) sits at (ax[j], ay[i], az[k]) — the
+ * reference's meshgrid(..., indexing="xy") — with ax, ay, az device arrays of `steps` doubles, 1 ≤ steps ≤
+ * CDX_FIELD_MAX_STEPS.
+ *
+ * cdx_gpis_field: mean [steps³], std [steps³] (nullable; needs g->Linv_t), normal [steps³·3] (nullable), f64.  The
+ *   cells go through the cdx_gpis_mean launch (mean and normal from one pass) and the whitened std pass without a
+ *   stored V, `chunk` cells at a time (chunk > 0: any size, a test can force a ragged last chunk; 0: the largest
+ *   multiple of 128 whose workspace stays under 1 GiB, at most the lattice).  Every chunk is enqueued on the
+ *   stream; a cell's mean and normal do not depend on the chunking (bit-identical).  Workspace:
+ *   cdx_gpis_field_workspace(g, steps, chunk) bytes for the same (steps, chunk).
+ * cdx_gpis_field_points: X [n·3] = the coordinates of the cells cells[0 .. n) (cells null: cells 0 .. n in
+ *   order); an index outside the lattice gives NaN.
+ *
+ * Surface cells (the cell rule is csrc/cdx_field.h): interior cells with mean < 0 that have a face neighbour
+ * with !(mean < 0).  mean [steps³] and normal [steps³·3] are float or double (dtype = CDX_DTYPE_*).  flip_k != 0
+ * reads mean and normal at k' = steps − 1 − k, as the reference does for tensor inputs (:130-133); the points do
+ * not flip.  Ordered stream compaction without atomics: the output is in C order of (i, j, k) — numpy's
+ * boolean-mask order — and deterministic.
+ * cdx_gpis_surface_count: per-workgroup counts and their exclusive scan into the workspace
+ *   (cdx_gpis_surface_workspace(steps) bytes), *total (device int64) = the number of surface cells.  steps < 3
+ *   has no interior cell: total = 0 at once.
+ * cdx_gpis_surface_place: after a count on the same inputs and workspace.  Row r < capacity of the outputs is the
+ *   r-th surface cell: cells [capacity] its C-ordered index (nullable), points [capacity·3] = (px[j], py[i], pz[k])
+ *   from three device arrays of `steps` doubles (nullable, then px, py, pz are not read), normals [capacity·3] =
+ *   its normal in the input's dtype (nullable; needs normal).  Rows ≥ capacity are not written. */
+#define CDX_FIELD_MAX_STEPS 1024
+enum { CDX_DTYPE_F32 = 0, CDX_DTYPE_F64 = 1 };
+size_t cdx_gpis_field_workspace(const cdx_gpis* g, int32_t steps, int64_t chunk);
+int cdx_gpis_field(const cdx_gpis* g, const double* ax, const double* ay, const double* az, int32_t steps,
+                   int64_t chunk, double* mean, double* std, double* normal, void* workspace, cdx_stream_t stream);
+int cdx_gpis_field_points(const double* ax, const double* ay, const double* az, int32_t steps, const int64_t* cells,
+                          int64_t n, double* X, cdx_stream_t stream);
+size_t cdx_gpis_surface_workspace(int32_t steps);
+int cdx_gpis_surface_count(const void* mean, int32_t dtype, int32_t steps, int32_t flip_k, void* workspace,
+                           int64_t* total, cdx_stream_t stream);
+int cdx_gpis_surface_place(const void* mean, const void* normal, int32_t dtype, int32_t steps, int32_t flip_k,
+                           const double* px, const double* py, const double* pz, const void* workspace,
+                           int64_t capacity, int64_t* cells, double* points, void* normals, cdx_stream_t stream);
+
 /* ------------------------------------------------------------------ FK ----------
  * Replaces DifferentiableRobotModel.compute_forward_kinematics(q, link_names,
  * recursive=False, offsets) (robot_model.py:224-264 with update_kinematic_state
