@@ -8,6 +8,7 @@ Drop-in operators (same names / arguments as the reference):
   KinGraspOptimizer / SDFGraspOptimizer / GPISGraspOptimizer / KinGPISGraspOptimizer
                                optimize_pregrasp.py:121-511
   force_eq_reward              optimize_pregrasp.py:73-118
+  farthest_point_down_sample   open3d's PointCloud.farthest_point_down_sample (optimize_pregrasp.py:904)
 All compute runs in libcdx.so (HIP, gfx950); importing works without a GPU, calling does not.
 """
 from .gpis import GPIS  # noqa: F401
@@ -17,6 +18,7 @@ from .anneal import PregraspAnnealer  # noqa: F401
 from .force_eq import force_eq_reward  # noqa: F401
 from .optimizers import (GPISGraspOptimizer, KinGPISGraspOptimizer, KinGraspOptimizer,  # noqa: F401
                          SDFGraspOptimizer, TriangleMesh)
+from .pointcloud import completion_arrays, farthest_point_down_sample, farthest_point_sample  # noqa: F401
 from .robot_model import DifferentiableRobotModel  # noqa: F401
 from .torchsdf import PreparedMesh, compute_sdf, compute_sdf_with_faces, index_vertices_by_faces  # noqa: F401
 

@@ -1,5 +1,5 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
-// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h.
+// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
@@ -9,6 +9,7 @@
 #include "cdx_collision.h"
 #include "cdx_cost.h"
 #include "cdx_field.h"
+#include "cdx_fps.h"
 #include "cdx_gpis_mode.h"
 #include "cdx_sdf.h"
 
@@ -57,6 +58,28 @@ int64_t surface_extract(const T* mean, const T* normal, int steps, int flip_k, c
         ++n;
       }
   return n;
+}
+
+// The rule of cdx_fps.h as a plain single-threaded loop over one cloud.
+template <typename T>
+void fps_host(const T* X, int64_t P, int64_t K, int64_t start, int64_t* sel, double* radius, double* points) {
+  double* dist = new double[P];
+  for (int64_t j = 0; j < P; ++j) dist[j] = cdx::fps_init_dist(X[3 * j], X[3 * j + 1], X[3 * j + 2]);
+  int64_t s = start;
+  for (int64_t i = 0; i < K; ++i) {
+    const double cx = X[3 * s], cy = X[3 * s + 1], cz = X[3 * s + 2];
+    if (sel) sel[i] = s;
+    if (radius) radius[i] = dist[s];
+    if (points) { points[3 * i] = cx; points[3 * i + 1] = cy; points[3 * i + 2] = cz; }
+    double bd = -3.0;  // below every dist
+    int64_t bi = 0;
+    for (int64_t j = 0; j < P; ++j) {
+      dist[j] = cdx::fps_update(dist[j], cdx::fps_sqdist(X[3 * j], X[3 * j + 1], X[3 * j + 2], cx, cy, cz));
+      if (cdx::fps_beats(dist[j], j, bd, bi)) { bd = dist[j]; bi = j; }
+    }
+    s = bi;
+  }
+  delete[] dist;
 }
 
 }  // namespace
@@ -283,6 +306,22 @@ int64_t cdxh_surface_extract(const void* mean, const void* normal, int32_t dtype
     return surface_extract(static_cast<const double*>(mean), static_cast<const double*>(normal), steps, flip_k, px, py,
                            pz, capacity, cells, points, static_cast<double*>(normals));
   return CDX_EINVAL;
+}
+
+// Host build of cdx_fps (same arguments without the workspace, the mode and the stream; host pointers): the rule of
+// cdx_fps.h as a plain single-threaded loop.  tests/test_fps_cpu.py checks it against a numpy statement of the rule.
+int cdxh_fps(const void* X, int32_t dtype, int64_t P, int64_t B, int64_t K, int64_t start, int64_t* sel,
+             double* radius, double* points) {
+  if (!X || P < 1 || P >= ((int64_t)1 << 31) || B < 1 || K < 1 || K > P || start < 0 || start >= P) return CDX_EINVAL;
+  if (dtype != CDX_DTYPE_F32 && dtype != CDX_DTYPE_F64) return CDX_EINVAL;
+  for (int64_t b = 0; b < B; ++b) {
+    int64_t* sb = sel ? sel + b * K : nullptr;
+    double* rb = radius ? radius + b * K : nullptr;
+    double* pb = points ? points + b * K * 3 : nullptr;
+    if (dtype == CDX_DTYPE_F32) fps_host(static_cast<const float*>(X) + b * P * 3, P, K, start, sb, rb, pb);
+    else fps_host(static_cast<const double*>(X) + b * P * 3, P, K, start, sb, rb, pb);
+  }
+  return CDX_OK;
 }
 
 }  // extern "C"

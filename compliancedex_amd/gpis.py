@@ -8,7 +8,8 @@ gfx950 kernels (cdx_gpis_mean / cdx_gpis_std); there is no CPU path.
 Beyond the reference: ``field`` evaluates mean / std / normal on a whole lattice in one native call
 (``get_visualization_data(fused=True)`` is that plus one copy back), ``topcd`` compacts the surface cells on
 the device (cdx_gpis_surface_count / _place, the reference's triple Python loop), and ``surface`` chains the
-two without the lattice leaving the device.
+two without the lattice leaving the device; ``fit_pointcloud`` goes from a raw sensed cloud to the fitted state
+(farthest-point sampling by cdx_fps, then the reference's recipe: pointcloud.py).
 
 Differences in *how*, not *what*: ``fit`` builds R and E11 with cdx_gpis_fit, and L⁻¹ (E11 = LLᵀ),
 E11⁻¹ and α = L⁻ᵀL⁻¹y1 are factored once per state on the device by cdx_gpis_factor (blocked
@@ -254,6 +255,30 @@ class GPIS:
         self.E11 = E11
         self._state = None
         self._gen += 1
+
+    def fit_pointcloud(self, points, num_points=200, bound=0.15, n_internal=50, sharpness=30.0,
+                       noise=(0.2, 0.005, 0.1), center="bbox", weights=None, generator=None, start=0):
+        """From a raw cloud [P, 3] on the device to the fitted state (optimize_pregrasp.py:904-922): a
+        farthest-point sample of ``num_points`` rows (cdx_fps, beginning at row ``start``), the recipe of
+        ``pointcloud.completion_arrays`` around it, then ``fit``.  ``center="bbox"`` shifts the exterior points by
+        the centre of the bounding box of the whole finite cloud (:894), computed on the device; None leaves them at
+        the origin, anything else is the centre itself.  ``bound=0.1, n_internal=5, sharpness=10,
+        noise=(0.3, σ_obs, 0.02), center=None`` is train_gpis_completion.py.  The chosen rows stay in
+        ``self.sample_index`` (selection order).  No host synchronisation from the cloud to ``E11``; returns self."""
+        from . import pointcloud as PC
+        _require_cuda(points, "point cloud")
+        if points.dim() != 2:
+            raise ValueError(f"point cloud must be [P, 3], got {tuple(points.shape)}")
+        sel, _, surface = PC.fps(points, num_points, start, gather=True)
+        if isinstance(center, str):
+            if center != "bbox":
+                raise ValueError(f"center must be 'bbox', None or a point, got {center!r}")
+            center = PC.bbox_center(points)
+        X1, y, nz = PC.completion_arrays(surface, bound, n_internal, sharpness, noise, center=center, weights=weights,
+                                         generator=generator)
+        self.fit(X1, y, noise=nz)
+        self.sample_index = sel
+        return self
 
     def save_state_data(self, name="gpis_state"):
         """npz {R, X1, y1, E11, bias} under gpis_states/ (gpis.py:155-160)."""

@@ -170,6 +170,24 @@ int cdx_gpis_surface_place(const void* mean, const void* normal, int32_t dtype, 
                            const double* px, const double* py, const double* pz, const void* workspace,
                            int64_t capacity, int64_t* cells, double* points, void* normals, cdx_stream_t stream);
 
+/* Farthest-point sampling: the down-sampling in front of GPIS.fit (optimize_pregrasp.py:904 and
+ * get_observable_pcd.py:40, open3d's farthest_point_down_sample in the reference).  The rule is csrc/cdx_fps.h:
+ * float64 squared distances, a running minimum, the SMALLEST index among the rows with the largest distance, rows
+ * with a non-finite coordinate held at −1 (chosen only as `start`).  X [B·P·3] float or double (dtype = CDX_DTYPE_*):
+ * B clouds of P rows that never interact; `start` is the first index of every cloud.  Outputs, each nullable:
+ * sel [B·K] the chosen rows in selection order, radius [B·K] the squared distance of each to the ones before it
+ * (+inf for the first, −1 for a non-finite start), points [B·K·3] = X[sel] as doubles.
+ * mode 1: one workgroup per cloud, all rounds in one launch, P ≤ cdx_fps_capacity();  mode 2: one launch per round,
+ * several workgroups per cloud joined by a ticket counter (no grid barrier, no waiting), any P < 2³¹;  mode 0 picks.
+ * Both give the same bits.  Workspace: cdx_fps_workspace(P, B, mode) bytes (0 for a bad argument), never read before
+ * it is written and left ready for the next call.
+ * CDX_EINVAL: null X or workspace, K < 1, K > P, start outside 0 … P−1, B < 1, P ≥ 2³¹, an unknown dtype or mode,
+ * mode 1 beyond its capacity. */
+int64_t cdx_fps_capacity(void);
+size_t cdx_fps_workspace(int64_t P, int64_t B, int32_t mode);
+int cdx_fps(const void* X, int32_t dtype, int64_t P, int64_t B, int64_t K, int64_t start, int32_t mode,
+            void* workspace, int64_t* sel, double* radius, double* points, cdx_stream_t stream);
+
 /* ------------------------------------------------------------------ FK ----------
  * Replaces DifferentiableRobotModel.compute_forward_kinematics(q, link_names,
  * recursive=False, offsets) (robot_model.py:224-264 with update_kinematic_state
