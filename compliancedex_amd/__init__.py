@@ -9,6 +9,9 @@ Drop-in operators (same names / arguments as the reference):
                                optimize_pregrasp.py:121-511
   force_eq_reward              optimize_pregrasp.py:73-118
   farthest_point_down_sample   open3d's PointCloud.farthest_point_down_sample (optimize_pregrasp.py:904)
+  cast_rays / occluded         open3d's RaycastingScene.cast_rays (concatenate_pcd.py:41-49)
+  Camera / render_depth / depth_to_pointcloud / observable_pointcloud
+                               get_observable_pcd.py: PyBullet's depth camera, open3d's create_from_depth_image
 All compute runs in libcdx.so (HIP, gfx950); importing works without a GPU, calling does not.
 """
 from .gpis import GPIS  # noqa: F401
@@ -19,6 +22,8 @@ from .force_eq import force_eq_reward  # noqa: F401
 from .optimizers import (GPISGraspOptimizer, KinGPISGraspOptimizer, KinGraspOptimizer,  # noqa: F401
                          SDFGraspOptimizer, TriangleMesh)
 from .pointcloud import completion_arrays, farthest_point_down_sample, farthest_point_sample  # noqa: F401
+from .raycast import (Camera, cast_rays, depth_to_pointcloud, observable_pointcloud, occluded,  # noqa: F401
+                      render_depth)
 from .robot_model import DifferentiableRobotModel  # noqa: F401
 from .torchsdf import PreparedMesh, compute_sdf, compute_sdf_with_faces, index_vertices_by_faces  # noqa: F401
 

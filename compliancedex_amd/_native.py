@@ -22,6 +22,8 @@ FPS_MODES = {"auto": 0, "block": 1, "rounds": 2}  # cdx_fps mode
 PROF_STAGES = 6   # cdx_profile_read array length
 SDF_REUSE_ORDER, SDF_MESH_CULLED, SDF_MESH_EXACT = 1, 2, 4  # cdx_sdf_query flags
 SDF_SCHED_KEEP = 8  # cdx_sdf_query_batch, first query: keep the schedule's order
+RAY_MODES = {"auto": 0, "scan": 1, "walk": 2}  # CDX_RAY_*
+DEPTH_U16 = 2  # CDX_DEPTH_U16, next to DTYPE_F32 / DTYPE_F64
 ERRORS = {-1: "invalid argument", -2: "unsupported GPIS kernel", -3: "chain exceeds descriptor capacity",
           -10: "HIP launch failed"}
 
@@ -204,6 +206,17 @@ _SIGS = {
     "cdx_sdf_query_batch": (C.c_int, [C.c_int32, _P, _P, C.c_size_t, _P]),
     "cdx_sdf_query": (C.c_int, [_P, _P, _I64, _P, _I64, _P, _P, _P, _P, _P, _P, C.c_size_t, C.c_int32, _P]),
     "cdx_sdf_mesh_flags": (C.c_int, [_P, C.POINTER(C.c_int32), _P]),
+    "cdx_ray_mesh_bytes": (C.c_size_t, [_I64]),
+    "cdx_ray_mesh_prepare": (C.c_int, [_P, _I64, _P, _P]),
+    "cdx_ray_cast": (C.c_int, [_P, _P, _P, _I64, _P, _P, _I64, C.c_double, C.c_double, C.c_int32, _P, _P, _P, _P]),
+    "cdx_depth_render": (C.c_int, [_P, _P, _P, _I64, C.c_int32, C.c_int32, C.POINTER(C.c_double),
+                                   C.POINTER(C.c_double), C.c_double, C.c_double, C.c_int32, _P, _P, _P]),
+    "cdx_depth_workspace": (C.c_size_t, [C.c_int32, C.c_int32, C.c_int32]),
+    "cdx_depth_count": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_double, C.c_double, C.c_double,
+                                  _P, _P, _P]),
+    "cdx_depth_place": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(C.c_double), C.c_double,
+                                  C.c_double, C.c_double, C.POINTER(C.c_double), _P, _I64, _P, _P]),
+    "cdx_ray_stats": (C.c_int, [C.c_int32, C.POINTER(C.c_uint64), _P]),
     "cdx_version": (C.c_char_p, []),
     "cdx_abi_sizes": (None, [C.POINTER(C.c_size_t)]),
     "cdx_selftest_mfma_f64": (C.c_int, [_P, _P, _P, _P]),

@@ -43,24 +43,17 @@
 #include <vector>
 
 #include "cdx_sdf.h"
+#include "cdx_sdf_mesh.h"
 
 #pragma clang fp contract(off)
 
 namespace {
 
+using namespace cdx::mesh;  // Node, Slab, CHUNK / TOPB / RUN / RPC and the buffer's offsets
+
 constexpr int SDF_BLOCK = 256;
 constexpr int SDF_TILE = CDX_SDF_REF_TILE;
-constexpr int CHUNK = 32;           // faces per chunk (leaf node)
-constexpr int TOPB = 16;            // chunks per top node
-constexpr int RUN = 8;              // faces per run (a chunk's sub-group with its own node)
-constexpr int RPC = 32 / RUN;       // runs per chunk
 constexpr float PT_LIM = 1e4f;      // |p| bound of the culled path (face_may_nan's premise)
-
-// Bounding volume of a node: a = (centre xyz, ball radius R), b = (cylinder axis xyz, half-thickness t),
-// m = (cylinder radius rc, 1/(1 − α), w = γ·(|centre| + 3R)/(1 − α), γ) with γ = 1e-4 + 1e-8·κ.
-struct Node { float4 a, b, m; };
-// Disk slab of a face: a = (centroid xyz, in-plane radius r), b = (unit normal xyz, half-thickness t).
-struct Slab { float4 a, b; };
 
 // Diagnostic counters (cdx_sdf_stats): [0] (point, face) pairs the culled kernel evaluated (the greedy seed
 // face of every lane plus the compacted pairs), [1] pairs of the brute-force scans (exact path), [2] points
@@ -964,8 +957,6 @@ __global__ __launch_bounds__(256) void sdf_backward_kernel(const float* __restri
   for (int c = 0; c < 3; ++c) gp[3 * i + c] = (points[3 * i + c] - clst[3 * i + c]) * g;
 }
 
-size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
-
 bool sched_on() {  // CDX_SDF_SCHED=0: a batch ignores its schedule (point order, the A/B base)
   static const bool on = [] {
     const char* e = cdx::ab_env("CDX_SDF_SCHED");
@@ -983,21 +974,7 @@ int sdf_mode() {  // CDX_SDF_MODE=exact forces the brute-force kernel (benchmark
 }
 
 
-// Mesh: [header words: frame keys ×6, may-NaN flag, 0][face records: C·CHUNK FaceRec][slabs: C·CHUNK Slab]
-// [chunk nodes: C Node][top nodes: T Node], C = ⌈F/32⌉, T = ⌈C/16⌉, faces in the build's order.
-int64_t n_chunks(int64_t F) { return (F + CHUNK - 1) / CHUNK; }
-// (runs: RUN-face groups of a chunk, RPC per chunk, each with its own node — tested before the run's faces)
-int64_t n_tops(int64_t F) { return (n_chunks(F) + TOPB - 1) / TOPB; }
-size_t mesh_rec_off() { return align256(8 * sizeof(unsigned)); }
-size_t mesh_slab_off(int64_t C) { return mesh_rec_off() + align256((size_t)C * CHUNK * sizeof(cdx::FaceRec)); }
-size_t mesh_chunk_off(int64_t C) { return mesh_slab_off(C) + align256((size_t)C * CHUNK * sizeof(Slab)); }
-size_t mesh_top_off(int64_t C) { return mesh_chunk_off(C) + align256((size_t)C * sizeof(Node)); }
-size_t mesh_run_off(int64_t C) { return mesh_top_off(C) + align256((size_t)((C + TOPB - 1) / TOPB) * sizeof(Node)); }
-size_t mesh_bytes(int64_t F) {
-  const int64_t C = n_chunks(F);
-  return mesh_run_off(C) + align256((size_t)C * RPC * sizeof(Node));
-}
-
+// (the mesh buffer's layout: cdx_sdf_mesh.h)
 // Records, slabs and nodes of the faces in `order` (device int[F]).
 void mesh_fill(const float* faces, int64_t F, const int* order, char* mesh, hipStream_t s) {
   const int64_t C = n_chunks(F), T = n_tops(F);

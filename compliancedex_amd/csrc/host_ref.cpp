@@ -11,6 +11,7 @@
 #include "cdx_field.h"
 #include "cdx_fps.h"
 #include "cdx_gpis_mode.h"
+#include "cdx_ray.h"
 #include "cdx_sdf.h"
 
 namespace {
@@ -80,6 +81,21 @@ void fps_host(const T* X, int64_t P, int64_t K, int64_t start, int64_t* sel, dou
     s = bi;
   }
   delete[] dist;
+}
+
+// cdxh_depth_unproject for one depth type D, z in Z: the full count; the first `capacity` points are written.
+template <typename D, typename Z>
+int64_t depth_unproject(const D* depth, int32_t W, int32_t H, int32_t stride, const double* intr, double scale,
+                        double trunc, double z_max, const double* M, int64_t capacity, double* points) {
+  int64_t n = 0;
+  for (int i = 0; i < H; i += stride)
+    for (int j = 0; j < W; j += stride) {
+      double p[3];
+      if (!cdx::depth_point<Z>((Z)depth[(int64_t)i * W + j], i, j, intr, scale, trunc, z_max, M, p)) continue;
+      if (n < capacity) { points[3 * n] = p[0]; points[3 * n + 1] = p[1]; points[3 * n + 2] = p[2]; }
+      ++n;
+    }
+  return n;
 }
 
 }  // namespace
@@ -322,6 +338,67 @@ int cdxh_fps(const void* X, int32_t dtype, int64_t P, int64_t B, int64_t K, int6
     else fps_host(static_cast<const double*>(X) + b * P * 3, P, K, start, sb, rb, pb);
   }
   return CDX_OK;
+}
+
+// Host build of cdx_ray_cast's rule (same arguments without the meshes, the mode and the stream; host pointers): a plain
+// double loop over cdx_ray.h.  tests/test_ray_cpu.py checks it against a numpy statement of the rule; the device scan
+// and walk are checked against it.
+int cdxh_ray_cast(const float* faces, int64_t F, const double* origins, const double* dirs, int64_t R, double tmin,
+                  double tmax, double* t, int32_t* face, double* uv) {
+  if (R < 0 || F <= 0 || !faces) return CDX_EINVAL;
+  if (R == 0) return CDX_OK;
+  if (!origins || !dirs || !t || !face) return CDX_EINVAL;
+  for (int64_t r = 0; r < R; ++r) {
+    const double* o = origins + 3 * r;
+    const double* d = dirs + 3 * r;
+    cdx::RayHit best = cdx::ray_miss();
+    if (cdx::ray_valid(o, d))
+      for (int64_t f = 0; f < F; ++f) cdx::ray_update(o, d, faces + 9 * f, (int32_t)f, tmin, tmax, best);
+    double u, v;
+    cdx::ray_result(best, t[r], face[r], u, v);
+    if (uv) { uv[2 * r] = u; uv[2 * r + 1] = v; }
+  }
+  return CDX_OK;
+}
+
+// The rays cdx_depth_render generates: origins, dirs [H·W·3] in row-major pixel order.
+int cdxh_pixel_rays(int32_t W, int32_t H, const double* intr, const double* cam_to_world, double* origins,
+                    double* dirs) {
+  if (W < 1 || H < 1 || !intr || !cam_to_world || !origins || !dirs) return CDX_EINVAL;
+  for (int i = 0; i < H; ++i)
+    for (int j = 0; j < W; ++j) {
+      const int64_t q = (int64_t)i * W + j;
+      cdx::pixel_ray(i, j, intr, cam_to_world, origins + 3 * q, dirs + 3 * q);
+    }
+  return CDX_OK;
+}
+
+// Test hook of the walk's node skip: cdx::ray_ball_miss for n (ray, ball) pairs, balls [n·4] = (centre, radius);
+// cdx::ray_in_domain into dom when given.
+void cdxh_ray_ball_miss(const double* origins, const double* dirs, const double* s0, const double* s1,
+                        const float* balls, int64_t n, int32_t* miss, int32_t* dom) {
+  for (int64_t i = 0; i < n; ++i) {
+    const float* b = balls + 4 * i;
+    miss[i] = cdx::ray_ball_miss(origins + 3 * i, dirs + 3 * i, s0[i], s1[i], b[0], b[1], b[2], b[3]) ? 1 : 0;
+    if (dom) dom[i] = cdx::ray_in_domain(origins + 3 * i, dirs + 3 * i) ? 1 : 0;
+  }
+}
+
+// Host build of cdx_depth_count + cdx_depth_place (host pointers): returns the full count of points, or CDX_EINVAL.
+int64_t cdxh_depth_unproject(const void* depth, int32_t dtype, int32_t W, int32_t H, int32_t stride, const double* intr,
+                             double depth_scale, double depth_trunc, double z_max, const double* transform,
+                             int64_t capacity, double* points) {
+  if (!depth || !intr || W < 1 || H < 1 || stride < 1 || capacity < 0 || (capacity > 0 && !points)) return CDX_EINVAL;
+  if (dtype == CDX_DTYPE_F32)
+    return depth_unproject<float, float>(static_cast<const float*>(depth), W, H, stride, intr, depth_scale, depth_trunc,
+                                         z_max, transform, capacity, points);
+  if (dtype == CDX_DTYPE_F64)
+    return depth_unproject<double, double>(static_cast<const double*>(depth), W, H, stride, intr, depth_scale,
+                                           depth_trunc, z_max, transform, capacity, points);
+  if (dtype == CDX_DEPTH_U16)
+    return depth_unproject<uint16_t, float>(static_cast<const uint16_t*>(depth), W, H, stride, intr, depth_scale,
+                                            depth_trunc, z_max, transform, capacity, points);
+  return CDX_EINVAL;
 }
 
 }  // extern "C"

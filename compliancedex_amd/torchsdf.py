@@ -62,10 +62,27 @@ class PreparedMesh:
         N.check(lib.cdx_sdf_mesh_flags(N.ptr(self.buf), C.byref(kind), stream), "cdx_sdf_mesh_flags")
         self.kind = kind.value  # SDF_MESH_CULLED, or SDF_MESH_EXACT for a mesh with a NaN-capable face
         self._ws = QueryWorkspace()
+        self._ray = None
 
     @property
     def num_faces(self):
         return self.faces.shape[0]
+
+    def ray_records(self):
+        """The ray walk's records of this mesh (cdx_ray_mesh_prepare), built on first use and kept."""
+        if self._ray is None:
+            lib = N.load()
+            F = self.faces.shape[0]
+            ray = torch.empty(lib.cdx_ray_mesh_bytes(F), dtype=torch.uint8, device=self.faces.device)
+            N.check(lib.cdx_ray_mesh_prepare(N.ptr(self.buf), F, N.ptr(ray), N.stream_ptr(self.faces.device)),
+                    "cdx_ray_mesh_prepare")
+            self._ray = ray
+        return self._ray
+
+    def cast_rays(self, origins, directions, tmin=0.0, tmax=float("inf"), mode="auto", want_uv=False):
+        """``raycast.cast_rays`` on this mesh."""
+        from .raycast import cast_rays
+        return cast_rays(self, origins, directions, tmin, tmax, mode, want_uv)
 
     def query(self, points, want_face=False, workspace=None, reuse_order=False, out=None):
         """(sqdist, sign, normals, clst, face | None) of float32 points [P, 3] (cdx_sdf_query).  ``workspace``: a

@@ -709,6 +709,58 @@ int cdx_sdf_stats(int32_t enable, uint64_t* out3, cdx_stream_t stream);
  * since counting was enabled, summed over waves. */
 int cdx_sdf_chunk_visits(uint64_t* out, cdx_stream_t stream);
 
+/* ------------------------------------------------------------- ray casting ----------
+ * First hit of R rays on a float32 triangle mesh, and the depth camera built on it: what the reference takes
+ * from PyBullet's depth image, open3d's create_from_depth_image (get_observable_pcd.py:26-40) and open3d's
+ * RaycastingScene.cast_rays (concatenate_pcd.py:41-49).  The rule is csrc/cdx_ray.h: the float64 Möller–Trumbore test
+ * on the widened float32 vertices with a relative determinant threshold of 2⁻²⁰, tmin ≤ t ≤ tmax inclusive, d not
+ * normalised (t in units of |d|), the smallest t wins and equal t goes to the smallest ORIGINAL face index.  Parity
+ * with open3d, Embree and PyBullet is unpinned (none is a dependency).
+ * cdx_ray_cast: origins, dirs [R·3] doubles.  Outputs t [R] (+inf on a miss), face [R] (−1 on a miss), uv [R·2]
+ *   (nullable; the hit's barycentric u, v: the point is (1 − u − v)·v0 + u·v1 + v·v2; 0 on a miss).  A ray with a
+ *   non-finite component or d = 0 is a miss.  mode CDX_RAY_SCAN: every face against every ray, on `faces` alone
+ *   (mesh and ray_mesh may be NULL); CDX_RAY_WALK: the hierarchy of a prepared mesh — `mesh` from
+ *   cdx_sdf_mesh_prepare and `ray_mesh` from cdx_ray_mesh_prepare, both of these `faces`; CDX_RAY_AUTO: the walk
+ *   when both are given.  Both modes give the same bits on every mesh; on a mesh with a NaN-capable face
+ *   (CDX_SDF_MESH_EXACT) the walk skips nothing, so the scan is the one to ask for.
+ *   CDX_EINVAL: R < 0, F ≤ 0, F > INT32_MAX/9, null faces, origins, dirs, t or face (R > 0), an unknown mode, the
+ *   walk without mesh or ray_mesh.  Nothing is written then.
+ * cdx_ray_mesh_prepare: the walk's records (node balls, face vertices with their original index, in the mesh's
+ *   order) from a prepared mesh of F faces into ray_mesh, cdx_ray_mesh_bytes(F) caller-owned device bytes
+ *   (0 for a bad F).  One launch, no sync.
+ * cdx_depth_render: the cast with the rays of a W×H pinhole camera generated in the kernel: pixel (i, j) — row i,
+ *   column j — has the camera-frame direction ((j − cx)/fx, (i − cy)/fy, 1), x right, y down, z forward; intr =
+ *   (fx, fy, cx, cy) and cam_to_world (row-major 4×4) are HOST doubles, read during the call.  depth [H·W] doubles =
+ *   t, the z-depth (0 on a miss); face [H·W] (nullable).
+ * Depth unprojection (create_from_depth_image, stated in csrc/cdx_ray.h): depth [H·W] of dtype CDX_DTYPE_F32,
+ *   CDX_DTYPE_F64 or CDX_DEPTH_U16; pixels i, j = 0, stride, … in row-major order; z = depth/depth_scale in the depth's
+ *   precision (float for uint16); dropped if depth == 0, z ≥ depth_trunc or — z_max not NaN — !(z < z_max); x, y in
+ *   float64; `transform` (HOST, row-major 4×4, nullable) applied last.  Ordered compaction without atomics.
+ *   cdx_depth_count: counts and their scan into workspace (cdx_depth_workspace(W, H, stride) bytes), *total (device
+ *   int64) = the number of points.  cdx_depth_place: after a count on the same inputs and workspace; rows
+ *   < capacity of points [capacity·3] are written. */
+#define CDX_RAY_AUTO 0
+#define CDX_RAY_SCAN 1
+#define CDX_RAY_WALK 2
+#define CDX_DEPTH_U16 2 /* depth dtype next to CDX_DTYPE_F32 / CDX_DTYPE_F64 */
+size_t cdx_ray_mesh_bytes(int64_t F);
+int cdx_ray_mesh_prepare(const void* mesh, int64_t F, void* ray_mesh, cdx_stream_t stream);
+int cdx_ray_cast(const void* mesh, const void* ray_mesh, const float* faces, int64_t F, const double* origins,
+                 const double* dirs, int64_t R, double tmin, double tmax, int32_t mode, double* t, int32_t* face,
+                 double* uv, cdx_stream_t stream);
+int cdx_depth_render(const void* mesh, const void* ray_mesh, const float* faces, int64_t F, int32_t W, int32_t H,
+                     const double* intr, const double* cam_to_world, double tmin, double tmax, int32_t mode,
+                     double* depth, int32_t* face, cdx_stream_t stream);
+size_t cdx_depth_workspace(int32_t W, int32_t H, int32_t stride);
+int cdx_depth_count(const void* depth, int32_t dtype, int32_t W, int32_t H, int32_t stride, double depth_scale,
+                    double depth_trunc, double z_max, void* workspace, int64_t* total, cdx_stream_t stream);
+int cdx_depth_place(const void* depth, int32_t dtype, int32_t W, int32_t H, int32_t stride, const double* intr,
+                    double depth_scale, double depth_trunc, double z_max, const double* transform,
+                    const void* workspace, int64_t capacity, double* points, cdx_stream_t stream);
+/* Diagnostic counters of the walk: out2 (nullable, host) = [(ray, face) pairs evaluated, rays cast]; enable as
+ * cdx_sdf_stats. */
+int cdx_ray_stats(int32_t enable, uint64_t* out2, cdx_stream_t stream);
+
 /* Library identification (gfx arch string compiled in). */
 const char* cdx_version(void);
 
