@@ -12,6 +12,9 @@ Drop-in operators (same names / arguments as the reference):
   cast_rays / occluded         open3d's RaycastingScene.cast_rays (concatenate_pcd.py:41-49)
   Camera / render_depth / depth_to_pointcloud / observable_pointcloud
                                get_observable_pcd.py: PyBullet's depth camera, open3d's create_from_depth_image
+  GPIS.tomesh / surface_mesh   the mesh of the completed shape (train_gpis_completion.py:67-76 uses open3d's Poisson
+                               reconstruction; here marching tetrahedra on the field lattice, parity unpinned), with
+                               EdgeRefiner / mesh_face_vertices / to_triangle_mesh around it
 All compute runs in libcdx.so (HIP, gfx950); importing works without a GPU, calling does not.
 """
 from .gpis import GPIS  # noqa: F401
@@ -21,6 +24,7 @@ from .anneal import PregraspAnnealer  # noqa: F401
 from .force_eq import force_eq_reward  # noqa: F401
 from .optimizers import (GPISGraspOptimizer, KinGPISGraspOptimizer, KinGraspOptimizer,  # noqa: F401
                          SDFGraspOptimizer, TriangleMesh)
+from .mesh import EdgeRefiner, mesh_face_vertices, refine_vertices, to_triangle_mesh  # noqa: F401
 from .pointcloud import completion_arrays, farthest_point_down_sample, farthest_point_sample  # noqa: F401
 from .raycast import (Camera, cast_rays, depth_to_pointcloud, observable_pointcloud, occluded,  # noqa: F401
                       render_depth)

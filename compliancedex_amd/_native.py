@@ -167,6 +167,11 @@ _SIGS = {
     "cdx_gpis_surface_count": (C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P]),
     "cdx_gpis_surface_place": (C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _I64, _P, _P, _P,
                                          _P]),
+    "cdx_gpis_mesh_workspace": (C.c_size_t, [C.c_int32]),
+    "cdx_gpis_mesh_count": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P]),
+    "cdx_gpis_mesh_place": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _I64, _I64, _P, _P, _P, _P]),
+    "cdx_gpis_mesh_refine_init": (C.c_int, [_P, C.c_int32, C.c_int32, _P, _P, _P, _P, _I64, _P, _P, _P]),
+    "cdx_gpis_mesh_refine_step": (C.c_int, [_P, C.c_int32, _P, _P, _P, _P, _I64, _P, _P, _P]),
     "cdx_fps_capacity": (_I64, []),
     "cdx_fps_workspace": (C.c_size_t, [_I64, _I64, C.c_int32]),
     "cdx_fps": (C.c_int, [_P, C.c_int32, _I64, _I64, _I64, _I64, C.c_int32, _P, _P, _P, _P, _P]),

@@ -1,5 +1,5 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
-// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h.
+// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
@@ -11,6 +11,7 @@
 #include "cdx_field.h"
 #include "cdx_fps.h"
 #include "cdx_gpis_mode.h"
+#include "cdx_mesh.h"
 #include "cdx_ray.h"
 #include "cdx_sdf.h"
 
@@ -59,6 +60,55 @@ int64_t surface_extract(const T* mean, const T* normal, int steps, int flip_k, c
         ++n;
       }
   return n;
+}
+
+// The rule of cdx_mesh.h as plain loops: the nodes in C order (vertices in ascending key order, each node's first
+// vertex number kept), then the cubes in C order (their tetrahedra's triangles).  counts[0] = V, counts[1] = F; at most
+// vcap / fcap rows are written.
+template <typename T>
+void mesh_extract(const T* mean, int steps, const double* px, const double* py, const double* pz, int64_t vcap,
+                  int64_t fcap, double* vertices, int64_t* edges, int32_t* faces, int64_t* counts) {
+  const int64_t total = (int64_t)steps * steps * steps;
+  int64_t* base = new int64_t[total];
+  int64_t V = 0, F = 0;
+  for (int64_t c = 0; c < total; ++c) {
+    int i, j, k;
+    cdx::field_cell(c, steps, i, j, k);
+    const int ex = cdx::mesh_exists(steps, i, j, k);
+    const int cross = cdx::mesh_cross_mask(cdx::mesh_corner_bits(mean, steps, i, j, k, ex), ex);
+    base[c] = V;
+    for (int d = 0; d < 7; ++d) {
+      if (!((cross >> d) & 1)) continue;
+      if (V < vcap) {
+        cdx::mesh_vertex(mean, steps, px, py, pz, i, j, k, d, vertices + 3 * V);
+        if (edges) edges[V] = 7 * c + d;
+      }
+      ++V;
+    }
+  }
+  const int gs = cdx::mesh_axes_sign(px[steps - 1] - px[0], py[steps - 1] - py[0], pz[steps - 1] - pz[0]);
+  for (int i = 0; i < steps - 1; ++i)
+    for (int j = 0; j < steps - 1; ++j)
+      for (int k = 0; k < steps - 1; ++k) {
+        const int bits = cdx::mesh_corner_bits(mean, steps, i, j, k, 0xff);
+        for (int tet = 0; tet < 6; ++tet) {
+          uint32_t tris;
+          const int nt = cdx::mesh_tet_faces(cdx::mesh_tet_bits(tet, bits), cdx::mesh_tet_sign(tet) * gs, tris);
+          for (int t = 0; t < nt; ++t, ++F) {
+            if (F >= fcap) continue;
+            for (int v = 0; v < 3; ++v) {
+              int m, d;
+              cdx::mesh_tet_edge_node(tet, (tris >> (4 * (3 * t + v))) & 15u, m, d);
+              const int ni = i + (m & 1), nj = j + ((m >> 1) & 1), nk = k + ((m >> 2) & 1);
+              faces[3 * F + v] = (int32_t)(base[cdx::field_src(steps, ni, nj, nk, 0)] +
+                                           cdx::mesh_cross_below(mean, steps, ni, nj, nk, d));
+            }
+          }
+        }
+      }
+  delete[] base;
+  counts[0] = V;
+  counts[1] = F;
 }
 
 // The rule of cdx_fps.h as a plain single-threaded loop over one cloud.
@@ -322,6 +372,42 @@ int64_t cdxh_surface_extract(const void* mean, const void* normal, int32_t dtype
     return surface_extract(static_cast<const double*>(mean), static_cast<const double*>(normal), steps, flip_k, px, py,
                            pz, capacity, cells, points, static_cast<double*>(normals));
   return CDX_EINVAL;
+}
+
+// Host build of cdx_gpis_mesh_count + cdx_gpis_mesh_place (host pointers, no workspace): counts [2] = (V, F) in full,
+// at most vcap vertices (and keys, nullable) and fcap faces written.  tests/test_mesh_cpu.py checks it against a numpy
+// statement of the rule; the device passes are checked against it.
+int cdxh_mesh_extract(const void* mean, int32_t dtype, int32_t steps, const double* px, const double* py,
+                      const double* pz, int64_t vcap, int64_t fcap, double* vertices, int64_t* edges, int32_t* faces,
+                      int64_t* counts) {
+  if (!mean || !counts || steps < 1 || steps > CDX_FIELD_MAX_STEPS || vcap < 0 || fcap < 0 || !px || !py || !pz ||
+      (vcap > 0 && !vertices) || (fcap > 0 && !faces))
+    return CDX_EINVAL;
+  counts[0] = counts[1] = 0;
+  if (steps < 2) return CDX_OK;
+  if (dtype == CDX_DTYPE_F32)
+    mesh_extract(static_cast<const float*>(mean), steps, px, py, pz, vcap, fcap, vertices, edges, faces, counts);
+  else if (dtype == CDX_DTYPE_F64)
+    mesh_extract(static_cast<const double*>(mean), steps, px, py, pz, vcap, fcap, vertices, edges, faces, counts);
+  else
+    return CDX_EINVAL;
+  return counts[0] >= ((int64_t)1 << 31) || counts[1] >= ((int64_t)1 << 31) ? CDX_EINVAL : CDX_OK;
+}
+
+// Host build of cdx_gpis_mesh_refine_init (fv null) / _step (host pointers): cdx::mesh_refine_vertex over the vertices.
+int cdxh_mesh_refine(const void* mean, int32_t dtype, const double* fv, int32_t steps, const double* px,
+                     const double* py, const double* pz, const int64_t* edges, int64_t V, double* state,
+                     double* vertices) {
+  if (steps < 1 || steps > CDX_FIELD_MAX_STEPS || !px || !py || !pz || V < 0 || (!fv && !mean)) return CDX_EINVAL;
+  if (V > 0 && (!edges || !state || !vertices)) return CDX_EINVAL;
+  if (!fv && dtype != CDX_DTYPE_F32 && dtype != CDX_DTYPE_F64) return CDX_EINVAL;
+  for (int64_t r = 0; r < V; ++r) {
+    if (!fv && dtype == CDX_DTYPE_F32)
+      cdx::mesh_refine_vertex(static_cast<const float*>(mean), fv, steps, px, py, pz, edges, V, r, state, vertices);
+    else
+      cdx::mesh_refine_vertex(static_cast<const double*>(mean), fv, steps, px, py, pz, edges, V, r, state, vertices);
+  }
+  return CDX_OK;
 }
 
 // Host build of cdx_fps (same arguments without the workspace, the mode and the stream; host pointers): the rule of

@@ -9,7 +9,10 @@ Beyond the reference: ``field`` evaluates mean / std / normal on a whole lattice
 (``get_visualization_data(fused=True)`` is that plus one copy back), ``topcd`` compacts the surface cells on
 the device (cdx_gpis_surface_count / _place, the reference's triple Python loop), and ``surface`` chains the
 two without the lattice leaving the device; ``fit_pointcloud`` goes from a raw sensed cloud to the fitted state
-(farthest-point sampling by cdx_fps, then the reference's recipe: pointcloud.py).
+(farthest-point sampling by cdx_fps, then the reference's recipe: pointcloud.py); ``tomesh`` turns a lattice field into
+a watertight triangle mesh by marching tetrahedra on the device (cdx_gpis_mesh_count / _place, the rule of
+csrc/cdx_mesh.h; the reference's Poisson reconstruction is not reproduced) and ``surface_mesh`` goes from the state to
+that mesh, optionally refined along the lattice edges, without the lattice leaving the device.
 
 Differences in *how*, not *what*: ``fit`` builds R and E11 with cdx_gpis_fit, and L⁻¹ (E11 = LLᵀ),
 E11⁻¹ and α = L⁻ᵀL⁻¹y1 are factored once per state on the device by cdx_gpis_factor (blocked
@@ -523,3 +526,88 @@ class GPIS:
                 N.check(lib.cdx_gpis_mean(st.desc, N.ptr(X), n, N.ptr(m2), None, N.ptr(normals), N.stream_ptr(dev)),
                         "cdx_gpis_mean")
         return points, normals
+
+    # ------------------------------------------------------- iso-surface mesh
+    def _mesh_extract(self, mean, dtype, steps, pax):
+        """count → ONE host read (both totals) → place: (vertices [V, 3] f64, edges [V] int64, faces [F, 3] int32)."""
+        lib = N.load()
+        dev = mean.device
+        ws = torch.empty(max(lib.cdx_gpis_mesh_workspace(steps), 1), dtype=torch.uint8, device=dev)
+        totals = torch.zeros(2, dtype=torch.int64, device=dev)
+        N.check(lib.cdx_gpis_mesh_count(N.ptr(mean), dtype, steps, N.ptr(ws), N.ptr(totals), N.stream_ptr(dev)),
+                "cdx_gpis_mesh_count")
+        nv, nf = (int(x) for x in totals.cpu())
+        vertices = torch.empty(nv, 3, dtype=torch.float64, device=dev)
+        edges = torch.empty(nv, dtype=torch.int64, device=dev)
+        faces = torch.empty(nf, 3, dtype=torch.int32, device=dev)
+        if nv:
+            N.check(lib.cdx_gpis_mesh_place(N.ptr(mean), dtype, steps, N.ptr(pax[0]), N.ptr(pax[1]), N.ptr(pax[2]),
+                                            N.ptr(ws), nv, nf, N.ptr(vertices), N.ptr(edges), N.ptr(faces),
+                                            N.stream_ptr(dev)), "cdx_gpis_mesh_place")
+        return vertices, edges, faces
+
+    def tomesh(self, test_mean, lb, ub, steps=100):
+        """Triangle mesh of the zero level of a lattice field: (vertices float64 [V, 3], triangles int32 [F, 3]) as
+        numpy.  ``test_mean`` [steps]*3 is a numpy array or a tensor, float32 or float64, read as it stands (no flip:
+        that is ``topcd``'s reference quirk) on ``topcd``'s float64 point lattice.  Marching tetrahedra on the lattice
+        (csrc/cdx_mesh.h): a vertex on every lattice edge whose ends differ in mean < 0, triangles wound outwards,
+        closed and manifold wherever the surface stays off the lattice's border.  The reference meshes its completed
+        shape with open3d's Poisson reconstruction (train_gpis_completion.py:67-76); parity with it is not attempted.
+        Count and ordered placement run on the device (cdx_gpis_mesh_count / _place); one host read for the totals."""
+        steps = self._check_steps(steps)
+        _require_cuda(self.X1, "GPIS state")
+        dev = self.X1.device
+        mean = (test_mean.detach() if torch.is_tensor(test_mean) else
+                torch.from_numpy(np.ascontiguousarray(test_mean))).to(dev)
+        if mean.dtype not in (torch.float32, torch.float64):
+            mean = mean.double()
+        mean = mean.contiguous()
+        if tuple(mean.shape) != (steps,) * 3:
+            raise ValueError(f"tomesh expects mean [{steps}]*3, got {tuple(mean.shape)}")
+        dtype = N.DTYPE_F32 if mean.dtype == torch.float32 else N.DTYPE_F64
+        vertices, _, faces = self._mesh_extract(mean, dtype, steps, self._point_axes(lb, ub, steps))
+        return vertices.cpu().numpy(), faces.cpu().numpy()
+
+    def surface_mesh(self, lb, ub, steps=100, refine=0, normals=True):
+        """The mesh straight from the state: (vertices [V, 3] f64, faces [F, 3] int32, normals [V, 3] f64 or None) as
+        device tensors.  The mean alone is evaluated on the lattice of the float64 point axes (one set of axes for
+        evaluation and placement: a vertex's end values are the field at its end positions), then count, one host
+        read, place — ``tomesh`` of that lattice without it leaving the device.  ``refine`` steps of bracketed regula
+        falsi move every vertex along its own lattice edge towards the zero of the GPIS mean (cdx_gpis_mesh_refine_init /
+        _step with one cdx_gpis_mean call per step; ``mesh.EdgeRefiner`` is the same rule in torch ops, with the same
+        bits); the faces do not change.  The normals are the GPIS normals at the vertices (one
+        cdx_gpis_mean call, as ``surface`` does)."""
+        steps = self._check_steps(steps)
+        st = self.native_state()
+        dev = self.X1.device
+        lib = N.load()
+        with torch.no_grad():
+            pax = self._point_axes(lb, ub, steps)
+            mean = torch.empty(steps, steps, steps, dtype=torch.float64, device=dev)
+            ws = torch.empty(max(lib.cdx_gpis_field_workspace(st.desc, steps, 0), 1), dtype=torch.uint8, device=dev)
+            N.check(lib.cdx_gpis_field(st.desc, N.ptr(pax[0]), N.ptr(pax[1]), N.ptr(pax[2]), steps, 0, N.ptr(mean), None,
+                                       None, N.ptr(ws), N.stream_ptr(dev)), "cdx_gpis_field")
+            vertices, edges, faces = self._mesh_extract(mean, N.DTYPE_F64, steps, pax)
+            nv = vertices.shape[0]
+            if refine and nv:
+                # bracketed regula falsi along each vertex's own edge (csrc/cdx_mesh.h; mesh.EdgeRefiner states it
+                # in torch ops): cdx_gpis_mesh_refine_init, then per step one cdx_gpis_mean and one _refine_step
+                state = torch.empty(5, nv, dtype=torch.float64, device=dev)
+                fv = torch.empty(nv, dtype=torch.float64, device=dev)
+                s = N.stream_ptr(dev)
+                N.check(lib.cdx_gpis_mesh_refine_init(N.ptr(mean), N.DTYPE_F64, steps, N.ptr(pax[0]), N.ptr(pax[1]),
+                                                      N.ptr(pax[2]), N.ptr(edges), nv, N.ptr(state), N.ptr(vertices), s),
+                        "cdx_gpis_mesh_refine_init")
+                for _ in range(int(refine)):
+                    N.check(lib.cdx_gpis_mean(st.desc, N.ptr(vertices), nv, N.ptr(fv), None, None, s), "cdx_gpis_mean")
+                    N.check(lib.cdx_gpis_mesh_refine_step(N.ptr(fv), steps, N.ptr(pax[0]), N.ptr(pax[1]), N.ptr(pax[2]),
+                                                          N.ptr(edges), nv, N.ptr(state), N.ptr(vertices), s),
+                            "cdx_gpis_mesh_refine_step")
+            nrm = None
+            if normals:
+                nrm = torch.empty(nv, 3, dtype=torch.float64, device=dev)
+                if nv:
+                    m2 = torch.empty(nv, dtype=torch.float64, device=dev)
+                    N.check(lib.cdx_gpis_mean(st.desc, N.ptr(vertices), nv, N.ptr(m2), None, N.ptr(nrm),
+                                              N.stream_ptr(dev)), "cdx_gpis_mean")
+        return vertices, faces, nrm

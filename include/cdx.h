@@ -170,6 +170,43 @@ int cdx_gpis_surface_place(const void* mean, const void* normal, int32_t dtype, 
                            const double* px, const double* py, const double* pz, const void* workspace,
                            int64_t capacity, int64_t* cells, double* points, void* normals, cdx_stream_t stream);
 
+/* Iso-surface mesh of a lattice field: GPIS.tomesh / surface_mesh, marching tetrahedra on the field lattice (the
+ * rule is csrc/cdx_mesh.h; the reference meshes its completed shape with open3d's Poisson reconstruction,
+ * train_gpis_completion.py:67-76 — a different, global algorithm whose output is not pinned here).  mean [steps³] is
+ * float or double (dtype = CDX_DTYPE_*), read unflipped; node c = (i·steps + j)·steps + k sits at (px[j], py[i], pz[k]);
+ * inside = mean < 0.  A vertex sits on every lattice edge (seven types per node, key 7c + d) whose ends differ in
+ * `inside`, at the linear zero of the two end values (the midpoint when that is not in [0, 1]: never non-finite);
+ * vertices are in ascending key order.  Every cube's six Kuhn tetrahedra give 0, 1 or 2 triangles each, in the order
+ * (cube, tetrahedron, triangle), wound so that cross(v1 − v0, v2 − v0) points from inside to outside; away from the
+ * lattice's border the faces are a closed oriented 2-manifold.  Two ordered stream compactions without atomics.
+ * cdx_gpis_mesh_count: per-workgroup vertex and face counts and their exclusive scans into the workspace
+ *   (cdx_gpis_mesh_workspace(steps) bytes), totals (device int64[2]) = (V, F).  steps < 2 has no edge: V = F = 0 at
+ *   once.
+ * cdx_gpis_mesh_place: after a count on the same inputs and workspace.  vertices [vcap·3] f64, edges [vcap] the
+ *   vertices' keys (nullable), faces [fcap·3] int32 vertex numbers; px, py, pz device arrays of `steps` doubles.  A
+ *   capacity cuts the rows written, never the totals (a face may then name a vertex past vcap).  CDX_EINVAL if V or
+ *   F ≥ 2³¹ (only lattices above 564 steps can reach that; for those the call reads the totals back and so waits for
+ *   the stream).
+ *
+ * Refinement of the vertices along their own lattice edges (bracketed regula falsi; the faces never change): edges [V]
+ * are the keys a place wrote, state [5·V] doubles = ta, fa, tb, fb, t (the bracket's ends as parameters of the edge,
+ * the field there, and the vertex), vertices [V·3].  cdx_gpis_mesh_refine_init starts the state at the edges' ends
+ * with the lattice's values and writes the rule's own vertices; cdx_gpis_mesh_refine_step takes fv [V], the field at
+ * the current vertices (the caller's cdx_gpis_mean between two steps), replaces the bracket end whose `inside` is
+ * the vertex's, sets t = ta + (tb − ta)·fa/(fa − fb) — the midpoint unless that lies in [ta, tb] — and writes the new
+ * vertices; a non-finite fv leaves its vertex alone.  A key that is no edge of the lattice gives a NaN vertex. */
+size_t cdx_gpis_mesh_workspace(int32_t steps);
+int cdx_gpis_mesh_count(const void* mean, int32_t dtype, int32_t steps, void* workspace, int64_t* totals,
+                        cdx_stream_t stream);
+int cdx_gpis_mesh_place(const void* mean, int32_t dtype, int32_t steps, const double* px, const double* py,
+                        const double* pz, void* workspace, int64_t vcap, int64_t fcap, double* vertices,
+                        int64_t* edges, int32_t* faces, cdx_stream_t stream);
+int cdx_gpis_mesh_refine_init(const void* mean, int32_t dtype, int32_t steps, const double* px, const double* py,
+                              const double* pz, const int64_t* edges, int64_t V, double* state, double* vertices,
+                              cdx_stream_t stream);
+int cdx_gpis_mesh_refine_step(const double* fv, int32_t steps, const double* px, const double* py, const double* pz,
+                              const int64_t* edges, int64_t V, double* state, double* vertices, cdx_stream_t stream);
+
 /* Farthest-point sampling: the down-sampling in front of GPIS.fit (optimize_pregrasp.py:904 and
  * get_observable_pcd.py:40, open3d's farthest_point_down_sample in the reference).  The rule is csrc/cdx_fps.h:
  * float64 squared distances, a running minimum, the SMALLEST index among the rows with the largest distance, rows
