@@ -15,6 +15,9 @@ Drop-in operators (same names / arguments as the reference):
   GPIS.tomesh / surface_mesh   the mesh of the completed shape (train_gpis_completion.py:67-76 uses open3d's Poisson
                                reconstruction; here marching tetrahedra on the field lattice, parity unpinned), with
                                EdgeRefiner / mesh_face_vertices / to_triangle_mesh around it
+  SurfaceSampler / sample_points_uniformly / sample_points_poisson_disk / GPIS.fit_mesh
+                               open3d's TriangleMesh.sample_points_* (optimize_pregrasp.py:887, gpis.py:199-263):
+                               area-weighted samples of a mesh's surface, parity unpinned
 All compute runs in libcdx.so (HIP, gfx950); importing works without a GPU, calling does not.
 """
 from .gpis import GPIS  # noqa: F401
@@ -28,6 +31,8 @@ from .mesh import EdgeRefiner, mesh_face_vertices, refine_vertices, to_triangle_
 from .pointcloud import completion_arrays, farthest_point_down_sample, farthest_point_sample  # noqa: F401
 from .raycast import (Camera, cast_rays, depth_to_pointcloud, observable_pointcloud, occluded,  # noqa: F401
                       render_depth)
+from .sampling import (SurfaceSampler, sample_points_poisson_disk, sample_points_uniformly,  # noqa: F401
+                       surface_sampler)
 from .robot_model import DifferentiableRobotModel  # noqa: F401
 from .torchsdf import PreparedMesh, compute_sdf, compute_sdf_with_faces, index_vertices_by_faces  # noqa: F401
 

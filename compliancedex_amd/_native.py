@@ -19,7 +19,8 @@ SCREEN_BANDS = 24  # CDX_SCREEN_BANDS
 FIELD_MAX_STEPS = 1024  # CDX_FIELD_MAX_STEPS
 DTYPE_F32, DTYPE_F64 = 0, 1  # CDX_DTYPE_*
 FPS_MODES = {"auto": 0, "block": 1, "rounds": 2}  # cdx_fps mode
-PROF_STAGES = 6   # cdx_profile_read array length
+SAMPLE_MODES = {"auto": 0, "table": 1, "splitters": 2}  # cdx_sample_draw mode
+PROF_STAGES = 6  # cdx_profile_read array length
 SDF_REUSE_ORDER, SDF_MESH_CULLED, SDF_MESH_EXACT = 1, 2, 4  # cdx_sdf_query flags
 SDF_SCHED_KEEP = 8  # cdx_sdf_query_batch, first query: keep the schedule's order
 RAY_MODES = {"auto": 0, "scan": 1, "walk": 2}  # CDX_RAY_*
@@ -175,6 +176,12 @@ _SIGS = {
     "cdx_fps_capacity": (_I64, []),
     "cdx_fps_workspace": (C.c_size_t, [_I64, _I64, C.c_int32]),
     "cdx_fps": (C.c_int, [_P, C.c_int32, _I64, _I64, _I64, _I64, C.c_int32, _P, _P, _P, _P, _P]),
+    "cdx_sample_scan_faces": (_I64, []),
+    "cdx_sample_table_capacity": (_I64, []),
+    "cdx_sample_prepare_workspace": (C.c_size_t, [_I64]),
+    "cdx_sample_prepare": (C.c_int, [_P, C.c_int32, _I64, _P, _P, _P, _P]),
+    "cdx_sample_draw": (C.c_int, [_P, C.c_int32, _I64, _P, C.c_uint64, C.c_uint64, _I64, C.c_int32, _P, _P, _P, _P,
+                                  _P]),
     "cdx_gpis_fit": (C.c_int, [_P, C.c_int32, _P, C.c_int32, C.c_double, _P, _P, _P]),
     "cdx_gpis_factor_workspace": (C.c_size_t, [C.c_int32]),
     "cdx_gpis_factor": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),

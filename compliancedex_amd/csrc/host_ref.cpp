@@ -1,5 +1,5 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
-// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h.
+// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h / cdx_sample.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
@@ -13,6 +13,7 @@
 #include "cdx_gpis_mode.h"
 #include "cdx_mesh.h"
 #include "cdx_ray.h"
+#include "cdx_sample.h"
 #include "cdx_sdf.h"
 
 namespace {
@@ -485,6 +486,57 @@ int64_t cdxh_depth_unproject(const void* depth, int32_t dtype, int32_t W, int32_
     return depth_unproject<uint16_t, float>(static_cast<const uint16_t*>(depth), W, H, stride, intr, depth_scale,
                                             depth_trunc, z_max, transform, capacity, points);
   return CDX_EINVAL;
+}
+
+// Host build of cdx_sample_prepare (same arguments without the workspace and the stream; host pointers): the rule of
+// cdx_sample.h as plain loops.  tests/test_sample_cpu.py checks it against a numpy statement of the rule.
+int cdxh_sample_prepare(const void* faces, int32_t dtype, int64_t F, uint64_t* cdf, int32_t* info) {
+  if (!faces || !cdf || !info || F < 1 || F > 0x7fffffff / 9) return CDX_EINVAL;
+  if (dtype != CDX_DTYPE_F32 && dtype != CDX_DTYPE_F64) return CDX_EINVAL;
+  auto area = [&](int64_t f) {
+    return dtype == CDX_DTYPE_F32 ? cdx::sample_area(cdx::sample_face(static_cast<const float*>(faces) + 9 * f))
+                                  : cdx::sample_area(cdx::sample_face(static_cast<const double*>(faces) + 9 * f));
+  };
+  double A = 0.0;
+  for (int64_t f = 0; f < F; ++f) A = fmax(A, area(f));
+  uint64_t c = 0;
+  for (int64_t f = 0; f < F; ++f) cdf[f] = c += cdx::sample_weight(area(f), A);
+  *info = A > 0.0 ? 0 : 1;
+  return CDX_OK;
+}
+
+// Host build of cdx_sample_draw (same arguments without the mode and the stream; host pointers).
+int cdxh_sample_draw(const void* faces, int32_t dtype, int64_t F, const uint64_t* cdf, uint64_t seed, uint64_t first,
+                     int64_t K, double* points, int64_t* face, double* bary, double* normal) {
+  if (!faces || !cdf || F < 1 || F > 0x7fffffff / 9 || K < 0) return CDX_EINVAL;
+  if (dtype != CDX_DTYPE_F32 && dtype != CDX_DTYPE_F64) return CDX_EINVAL;
+  const uint64_t total = cdf[F - 1];
+  for (int64_t row = 0; row < K; ++row) {
+    uint64_t t;
+    double u, v, p[3], n[3];
+    cdx::sample_uniforms(seed, first + (uint64_t)row, total, t, u, v);
+    const int64_t f = total != 0 ? cdx::sample_upper(cdf, 0, F, t) : -1;
+    if (f >= 0 && f < F) {
+      const cdx::SampleFace s = dtype == CDX_DTYPE_F32 ? cdx::sample_face(static_cast<const float*>(faces) + 9 * f)
+                                                       : cdx::sample_face(static_cast<const double*>(faces) + 9 * f);
+      cdx::sample_point(s, u, v, p);
+      cdx::sample_normal(s, n);
+    } else {
+      u = v = p[0] = p[1] = p[2] = n[0] = n[1] = n[2] = (double)NAN;
+    }
+    if (face) face[row] = f >= 0 && f < F ? f : -1;
+    for (int k = 0; k < 3; ++k) {
+      if (points) points[3 * row + k] = p[k];
+      if (normal) normal[3 * row + k] = n[k];
+    }
+    if (bary) { bary[2 * row] = u; bary[2 * row + 1] = v; }
+  }
+  return CDX_OK;
+}
+
+// cdx::philox4x32_10 for the known-answer vectors: counter [4], key [2] → out [4].
+void cdxh_philox4x32_10(const uint32_t* counter, const uint32_t* key, uint32_t* out) {
+  cdx::philox4x32_10(counter[0], counter[1], counter[2], counter[3], key[0], key[1], out);
 }
 
 }  // extern "C"

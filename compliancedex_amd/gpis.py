@@ -283,6 +283,19 @@ class GPIS:
         self.sample_index = sel
         return self
 
+    def fit_mesh(self, mesh, num_points=200, cloud_points=4096, init_factor=5, seed=0, **recipe):
+        """From a ground-truth mesh to the fitted state: the Poisson-disk cloud the reference opens with
+        (``sampling.sample_points_poisson_disk(mesh, cloud_points, init_factor, seed)``, optimize_pregrasp.py:887),
+        then ``fit_pointcloud`` on it with ``num_points`` and the ``recipe`` arguments — the exterior points sit
+        around the bounding-box centre of that cloud (:888).  ``mesh``: a ``TriangleMesh``, a ``PreparedMesh``, a
+        ``SurfaceSampler`` or an [F, 3, 3] device tensor.  The cloud stays in ``self.sample_cloud``.  No host
+        synchronisation beyond the sampler's one word per mesh; returns self."""
+        from .sampling import sample_points_poisson_disk
+        cloud = sample_points_poisson_disk(mesh, cloud_points, init_factor=init_factor, seed=seed)
+        self.fit_pointcloud(cloud, num_points=num_points, **recipe)
+        self.sample_cloud = cloud
+        return self
+
     def save_state_data(self, name="gpis_state"):
         """npz {R, X1, y1, E11, bias} under gpis_states/ (gpis.py:155-160)."""
         os.makedirs("gpis_states", exist_ok=True)

@@ -58,6 +58,18 @@ class TriangleMesh:
         self.vertices = (self.vertices - c) * factor + c
         return self
 
+    def sample_points_uniformly(self, number_of_points, seed=0, device="cuda", **kw):
+        """``sampling.sample_points_uniformly`` on this mesh: a device tensor [K, 3] float64, not an open3d cloud."""
+        from .sampling import sample_points_uniformly
+        return sample_points_uniformly(self, number_of_points, seed=seed, device=device, **kw)
+
+    def sample_points_poisson_disk(self, number_of_points, init_factor=5, seed=0, device="cuda", **kw):
+        """``sampling.sample_points_poisson_disk`` on this mesh: a device tensor [K, 3] float64, not an open3d
+        cloud."""
+        from .sampling import sample_points_poisson_disk
+        return sample_points_poisson_disk(self, number_of_points, init_factor=init_factor, seed=seed, device=device,
+                                          **kw)
+
 
 def _face_vertices(mesh, device):
     tri = np.asarray(mesh.triangles)

@@ -63,6 +63,7 @@ class PreparedMesh:
         self.kind = kind.value  # SDF_MESH_CULLED, or SDF_MESH_EXACT for a mesh with a NaN-capable face
         self._ws = QueryWorkspace()
         self._ray = None
+        self._sampler = None  # sampling.surface_sampler keeps the mesh's SurfaceSampler here
 
     @property
     def num_faces(self):

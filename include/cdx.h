@@ -225,6 +225,30 @@ size_t cdx_fps_workspace(int64_t P, int64_t B, int32_t mode);
 int cdx_fps(const void* X, int32_t dtype, int64_t P, int64_t B, int64_t K, int64_t start, int32_t mode,
             void* workspace, int64_t* sel, double* radius, double* points, cdx_stream_t stream);
 
+/* Area-weighted surface sampling: a cloud of a mesh's whole surface (optimize_pregrasp.py:887 and gpis.py:199-263,
+ * open3d's sample_points_poisson_disk in the reference, whose first step is a uniform sample).  The rule is
+ * csrc/cdx_sample.h: float64 face areas, integer weights floor(area/max area · 2³²) and their running sums C [F]
+ * uint64, Philox4x32-10 keyed by `seed` at counter first + row, the face by a search of C, a uniform point of it.
+ * faces [F·9] float or double (dtype = CDX_DTYPE_*), 1 ≤ F ≤ INT32_MAX/9.  A face with a non-finite coordinate, no
+ * area, or less than 2⁻³² of the largest area is never drawn.
+ * cdx_sample_prepare, once per mesh: C into cdf [F], and *info (device) = 1 when no face has area, else 0.
+ *   Workspace: cdx_sample_prepare_workspace(F) bytes (0 for a bad F), never read before it is written.
+ * cdx_sample_draw: samples first … first + K − 1 of the stream `seed`.  Outputs, each nullable: points [K·3], face [K],
+ *   bary [K·2] = (u, v) with point = v0 + u·(v1 − v0) + v·(v2 − v0), normal [K·3] = the face's unit normal.  From a
+ *   table whose info is 1 every face is −1 and every other output NaN.  A sample depends on (seed, first + row) only.
+ *   mode 1: C whole in LDS, F ≤ cdx_sample_table_capacity();  mode 2: splitters of C in LDS, the search ends in global
+ *   memory, any F;  mode 0 picks.  Both give the same bits.  K = 0 is a no-op.
+ * CDX_EINVAL: null faces, workspace, cdf or info, F out of range, K < 0, an unknown dtype or mode, mode 1 beyond its
+ * capacity.  cdx_sample_scan_faces(): faces per workgroup of prepare's scan (for tests of its seams). */
+int64_t cdx_sample_scan_faces(void);
+int64_t cdx_sample_table_capacity(void);
+size_t cdx_sample_prepare_workspace(int64_t F);
+int cdx_sample_prepare(const void* faces, int32_t dtype, int64_t F, void* workspace, uint64_t* cdf, int32_t* info,
+                       cdx_stream_t stream);
+int cdx_sample_draw(const void* faces, int32_t dtype, int64_t F, const uint64_t* cdf, uint64_t seed, uint64_t first,
+                    int64_t K, int32_t mode, double* points, int64_t* face, double* bary, double* normal,
+                    cdx_stream_t stream);
+
 /* ------------------------------------------------------------------ FK ----------
  * Replaces DifferentiableRobotModel.compute_forward_kinematics(q, link_names,
  * recursive=False, offsets) (robot_model.py:224-264 with update_kinematic_state

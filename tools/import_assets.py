@@ -68,7 +68,8 @@ def obj_faces(path):
 
 
 def sample_surface(vs, fs, n, rng):
-    """Area-weighted uniform samples on a triangle mesh."""
+    """Area-weighted uniform samples on a triangle mesh.  This ran once, on the host, for the stored
+    data/config3_surface.npz; the product's sampler is compliancedex_amd.sample_points_uniformly (csrc/cdx_sample.h)."""
     tri = vs[fs]
     area = 0.5 * np.linalg.norm(np.cross(tri[:, 1] - tri[:, 0], tri[:, 2] - tri[:, 0]), axis=1)
     pick = rng.choice(len(fs), n, p=area / area.sum())
