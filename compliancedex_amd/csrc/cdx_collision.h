@@ -1,6 +1,10 @@
 // Per-candidate collision loss and its gradient (optimize_pregrasp.py:671-701), f64 with the
 // anchors from f32 FK like the reference (:674-676).  Shared by the gfx950 kernel and the
 // host test build.
+//
+// The reference masks a term by multiplying it by 0 (:684-698), so a non-finite candidate's cost and
+// gradients are NaN whichever way its comparisons fall.  The masked branches below add the same
+// term·0: +0 (or a −0 onto a sum that is never −0) for a finite candidate, whose bits do not change.
 #pragma once
 #include "cdx_cost.h"
 
@@ -32,6 +36,10 @@ CDX_HD void collision_candidate(const cdx_collision& C, const double* q, const d
       pair_cost += 1.0 / dist;
       const double s = -1.0 / (dist * dist) / dist;  // d(1/dist)/dd = −d/dist³
       for (int i = 0; i < 3; ++i) { ga[l][i] += s * d[i]; ga[r][i] -= s * d[i]; }
+    } else {
+      const double z0 = (1.0 / dist) * 0.0;
+      pair_cost += z0;
+      for (int i = 0; i < 3; ++i) { ga[l][i] += z0 * d[i]; ga[r][i] -= z0 * d[i]; }
     }
   }
   // floor (1/z)·0.1 below floor_z (:688-691)
@@ -41,6 +49,9 @@ CDX_HD void collision_candidate(const cdx_collision& C, const double* q, const d
     if (z < C.floor_z) {
       z_cost += (1.0 / z) * 0.1;
       ga[k][2] += -0.1 / (z * z);
+    } else {
+      z_cost += (1.0 / z) * 0.1 * 0.0;
+      ga[k][2] += (-0.1 / (z * z)) * 0.0;
     }
   }
   double c = pair_cost + z_cost;
@@ -49,6 +60,9 @@ CDX_HD void collision_candidate(const cdx_collision& C, const double* q, const d
   if (C.palm_term && pp[2] < C.floor_z) {
     c += 1.0 / pp[2];
     g_pp[2] += -1.0 / (pp[2] * pp[2]);
+  } else if (C.palm_term) {
+    c += (1.0 / pp[2]) * 0.0;
+    g_pp[2] += (-1.0 / (pp[2] * pp[2])) * 0.0;
   }
   cost = c;
   // back through a = Rp·tl + pp and the f32 FK

@@ -80,7 +80,10 @@ __device__ __forceinline__ void mean_tps_moments(const cdx_gpis& g, int64_t M, i
       s1x += v.w * px; s1y += v.w * py; s1z += v.w * pz;
       s2 += v.w * (px * px + py * py + pz * pz);
     } else {
-      v.x = x0 + 1.0; v.y = v.z = 0.0; v.w = 0.0;  // any finite point; α = 0
+      // padding: the first inducing point with α = 0.  A point of the state, never of a query: a non-finite query
+      // must not reach the other 31 queries of its workgroup through 0·NaN.  A finite query adds ±0 whatever the
+      // finite point (its distance to a real inducing point is already handled, r = 0 included).
+      v.x = c0; v.y = c1; v.z = c2; v.w = 0.0;
     }
     sp[tid] = v;
     __syncthreads();
@@ -169,7 +172,7 @@ __global__ __launch_bounds__(MEAN_BLOCK) void gpis_mean_kernel(cdx_gpis g, const
     if (j < g.N) {
       v.x = g.X1[3 * j]; v.y = g.X1[3 * j + 1]; v.z = g.X1[3 * j + 2]; v.w = g.alpha[j];
     } else {
-      v.x = x0 + 1.0; v.y = v.z = 0.0; v.w = 0.0;  // any finite point; α = 0
+      v.x = g.X1[0]; v.y = g.X1[1]; v.z = g.X1[2]; v.w = 0.0;  // as mean_tps_moments: a point of the state; α = 0
     }
     sp[tid] = v;
     __syncthreads();

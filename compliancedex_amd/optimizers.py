@@ -548,8 +548,9 @@ class _GpisModeLoop:
         self.state = gpis.native_state()
         self.hist = None
         # the iteration's query points in one buffer: the fingertips, then — from the next multiple of the mean
-        # kernel's 32-query workgroup on, so that every row is computed exactly as by a launch of its own, a workgroup
-        # holding a non-finite query included — the targets; the rows between hold a finite filler point
+        # kernel's 32-query workgroup on, so that every row is computed exactly as by a launch of its own — the
+        # targets; the rows between hold a finite filler point.  (A non-finite query stays in its own row of
+        # cdx_gpis_mean whatever shares its workgroup: tests/test_gpu_rows.py, test_gpu_gpis_mode.py.)
         M = E * T
         Mp = (M + _MEAN_TILE - 1) // _MEAN_TILE * _MEAN_TILE
         self.Mp = Mp

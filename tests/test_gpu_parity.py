@@ -575,17 +575,15 @@ def test_kin_one_launch_iteration_equals_two_launches(monkeypatch, robot):
             assert _bitwise_equal_nan_aware(a, b)
 
 
-@pytest.mark.parametrize("mode", ["alt", "nocache"])
-def test_kin_fk_walk_cache_equals_walking(monkeypatch, mode):
+def _kin_fk_walk_cache(monkeypatch, mode, E):
     """The one-launch Kin iteration's FK-walk cache (cdx_kin_opt_buffers::fk_state: the step's next-fingertip walk kept
     for the next iteration's FK backward, used only when the candidate's joint row still has the bits it was walked on)
     against walking every iteration: "nocache" runs the one-launch loop without the cache (CDX_KIN_FK_CACHE=0), "alt"
     alternates two-launch and one-launch iterations, so that every one-launch iteration finds the cache one step stale
     (written two iterations back) and must detect it and walk.  Both give the bits of the cached loop and of the
-    all-two-launch loop — deep iiwa7_allegro chain, E = 3000 (a partial last workgroup)."""
+    all-two-launch loop — deep iiwa7_allegro chain, E candidates (a partial last workgroup)."""
     from compliancedex_amd import KinGraspOptimizer
     from compliancedex_amd.workloads import banana_mesh, config4_kin_inputs
-    E = 3000
     links, offs, palm, q, target, comp = config4_kin_inputs(E, device=DEV, q_scale=0.3)
     outs = {}
     for name, env in (("cached", {"CDX_KIN_FUSED_STEP": "1", "CDX_KIN_FK_CACHE": "1"}),
@@ -607,6 +605,21 @@ def test_kin_fk_walk_cache_equals_walking(monkeypatch, mode):
                 assert np.array_equal(a.view(np.uint64), b.view(np.uint64)), other
             else:
                 assert _bitwise_equal_nan_aware(a, b), other
+
+
+@pytest.mark.parametrize("mode", ["alt", "nocache"])
+def test_kin_fk_walk_cache_equals_walking(monkeypatch, mode):
+    """_kin_fk_walk_cache at E = 3000."""
+    _kin_fk_walk_cache(monkeypatch, mode, 3000)
+
+
+@pytest.mark.parametrize("mode", ["alt", "nocache"])
+def test_kin_fk_walk_cache_equals_walking_unaligned_tail(monkeypatch, mode):
+    """_kin_fk_walk_cache at E = 3001: with D = 23 the last workgroup's joint rows end 3 floats into a 16-byte unit,
+    where the kernel's row check re-reads the block's first unit (cdx_kin.hip, the cache's row compare) — the last
+    candidate's tail joints are then compared with candidate e0's first joints, one row reading another.  The results
+    must still be those of walking, to the bit."""
+    _kin_fk_walk_cache(monkeypatch, mode, 3001)
 
 
 def test_sdf_one_launch_iteration_equals_two_launches(monkeypatch):
