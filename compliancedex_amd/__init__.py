@@ -18,6 +18,11 @@ Drop-in operators (same names / arguments as the reference):
   SurfaceSampler / sample_points_uniformly / sample_points_poisson_disk / GPIS.fit_mesh
                                open3d's TriangleMesh.sample_points_* (optimize_pregrasp.py:887, gpis.py:199-263):
                                area-weighted samples of a mesh's surface, parity unpinned
+  knn / KnnGrid / estimate_normals / orient_normals_towards_camera_location / statistical_outlier_mask /
+  remove_statistical_outlier / point_cloud_distance
+                               open3d's KDTreeFlann searches, estimate_normals (concatenate_pcd.py:35-36),
+                               remove_statistical_outlier and compute_point_cloud_distance: k nearest neighbours
+                               of a cloud on the device, parity with open3d's covariance and eigen-solver unpinned
 All compute runs in libcdx.so (HIP, gfx950); importing works without a GPU, calling does not.
 """
 from .gpis import GPIS  # noqa: F401
@@ -28,7 +33,9 @@ from .force_eq import force_eq_reward  # noqa: F401
 from .optimizers import (GPISGraspOptimizer, KinGPISGraspOptimizer, KinGraspOptimizer,  # noqa: F401
                          SDFGraspOptimizer, TriangleMesh)
 from .mesh import EdgeRefiner, mesh_face_vertices, refine_vertices, to_triangle_mesh  # noqa: F401
-from .pointcloud import completion_arrays, farthest_point_down_sample, farthest_point_sample  # noqa: F401
+from .pointcloud import (KnnGrid, completion_arrays, estimate_normals, farthest_point_down_sample,  # noqa: F401
+                         farthest_point_sample, knn, orient_normals_towards_camera_location, point_cloud_distance,
+                         remove_statistical_outlier, statistical_outlier_mask)
 from .raycast import (Camera, cast_rays, depth_to_pointcloud, observable_pointcloud, occluded,  # noqa: F401
                       render_depth)
 from .sampling import (SurfaceSampler, sample_points_poisson_disk, sample_points_uniformly,  # noqa: F401

@@ -20,6 +20,8 @@ FIELD_MAX_STEPS = 1024  # CDX_FIELD_MAX_STEPS
 DTYPE_F32, DTYPE_F64 = 0, 1  # CDX_DTYPE_*
 FPS_MODES = {"auto": 0, "block": 1, "rounds": 2}  # cdx_fps mode
 SAMPLE_MODES = {"auto": 0, "table": 1, "splitters": 2}  # cdx_sample_draw mode
+KNN_MODES = {"auto": 0, "scan": 1, "grid": 2}  # CDX_KNN_*
+KNN_MAX_K = 64  # CDX_KNN_MAX_K
 PROF_STAGES = 6  # cdx_profile_read array length
 SDF_REUSE_ORDER, SDF_MESH_CULLED, SDF_MESH_EXACT = 1, 2, 4  # cdx_sdf_query flags
 SDF_SCHED_KEEP = 8  # cdx_sdf_query_batch, first query: keep the schedule's order
@@ -176,6 +178,12 @@ _SIGS = {
     "cdx_fps_capacity": (_I64, []),
     "cdx_fps_workspace": (C.c_size_t, [_I64, _I64, C.c_int32]),
     "cdx_fps": (C.c_int, [_P, C.c_int32, _I64, _I64, _I64, _I64, C.c_int32, _P, _P, _P, _P, _P]),
+    "cdx_knn_auto_rows": (_I64, []),
+    "cdx_knn_grid_bytes": (C.c_size_t, [_I64]),
+    "cdx_knn_prepare": (C.c_int, [_P, C.c_int32, _I64, _P, _P]),
+    "cdx_knn_workspace": (C.c_size_t, [_I64, _I64, _I64, C.c_int32]),
+    "cdx_knn": (C.c_int, [_P, C.c_int32, _I64, _P, _P, _I64, _I64, C.c_double, C.c_int32, _P, _P, _P, _P, _P]),
+    "cdx_cloud_normals": (C.c_int, [_P, C.c_int32, _I64, _P, _P, _I64, C.POINTER(C.c_double), _P, _P, _P]),
     "cdx_sample_scan_faces": (_I64, []),
     "cdx_sample_table_capacity": (_I64, []),
     "cdx_sample_prepare_workspace": (C.c_size_t, [_I64]),

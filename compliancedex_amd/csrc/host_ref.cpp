@@ -1,16 +1,21 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
-// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h / cdx_sample.h.
+// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h / cdx_sample.h / cdx_knn.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
 // product path never loads it; the Python package loads only the gfx950 libcdx.so.
+#include <stdlib.h>
 #include <string.h>
+
+#include <algorithm>
+#include <vector>
 
 #include "cdx_collision.h"
 #include "cdx_cost.h"
 #include "cdx_field.h"
 #include "cdx_fps.h"
 #include "cdx_gpis_mode.h"
+#include "cdx_knn.h"
 #include "cdx_mesh.h"
 #include "cdx_ray.h"
 #include "cdx_sample.h"
@@ -110,6 +115,178 @@ void mesh_extract(const T* mean, int steps, const double* px, const double* py, 
   delete[] base;
   counts[0] = V;
   counts[1] = F;
+}
+
+// The sorted list of one query of cdx_knn.h: insertion of (d, i) into at most K pairs.
+struct KnnHostList {
+  double d[CDX_KNN_MAX_K];
+  int64_t i[CDX_KNN_MAX_K];
+  int n, K;
+  double max_d2;
+  void offer(double cd, int64_t ci) {
+    if (cd > max_d2 || cd != cd) return;
+    if (n == K && !cdx::knn_before(cd, ci, d[K - 1], i[K - 1])) return;
+    int at = n < K ? n : K - 1;
+    while (at > 0 && cdx::knn_before(cd, ci, d[at - 1], i[at - 1])) {
+      d[at] = d[at - 1];
+      i[at] = i[at - 1];
+      --at;
+    }
+    d[at] = cd;
+    i[at] = ci;
+    if (n < K) ++n;
+  }
+};
+
+// The grid of cdx_knn.h on the host: shape, cell of every row (−1 for a non-finite row) and the running extrema.
+template <typename T>
+void knn_grid_host(const T* X, int64_t P, cdx::KnnGrid& g, int32_t* cell, double* below, double* above) {
+  const double inf = (double)INFINITY;
+  double lo[3] = {inf, inf, inf}, hi[3] = {-inf, -inf, -inf};
+  bool any = false;
+  for (int64_t j = 0; j < P; ++j) {
+    const double p[3] = {(double)X[3 * j], (double)X[3 * j + 1], (double)X[3 * j + 2]};
+    if (!cdx::knn_finite3(p[0], p[1], p[2])) continue;
+    any = true;
+    for (int a = 0; a < 3; ++a) {
+      lo[a] = p[a] < lo[a] ? p[a] : lo[a];
+      hi[a] = p[a] > hi[a] ? p[a] : hi[a];
+    }
+  }
+  const int n0 = cdx::knn_grid_n0(P);
+  double ext = 0.0;
+  for (int a = 0; a < 3; ++a) {
+    g.lo[a] = any ? lo[a] : 0.0;
+    hi[a] = any ? hi[a] : 0.0;
+    const double e = hi[a] - g.lo[a];
+    ext = e > ext ? e : ext;
+  }
+  g.inv = cdx::knn_grid_inv(ext, n0);
+  for (int a = 0; a < 3; ++a) {
+    const int n = cdx::knn_cell_raw(hi[a], g.lo[a], g.inv) + 1;
+    g.n[a] = n < n0 ? n : n0;
+  }
+  g.pad = 0;
+  for (int k = 0; k < 3 * CDX_KNN_MAX_DIM; ++k) {
+    below[k] = -inf;
+    above[k] = inf;
+  }
+  for (int64_t j = 0; j < P; ++j) {
+    const double p[3] = {(double)X[3 * j], (double)X[3 * j + 1], (double)X[3 * j + 2]};
+    const bool ok = cdx::knn_finite3(p[0], p[1], p[2]);
+    for (int a = 0; a < 3; ++a) {
+      if (!ok) {
+        cell[3 * j + a] = -1;
+        continue;
+      }
+      const int c = cdx::knn_cell(p[a], g.lo[a], g.inv, g.n[a]);
+      cell[3 * j + a] = c;
+      double& b = below[a * CDX_KNN_MAX_DIM + c];
+      double& t = above[a * CDX_KNN_MAX_DIM + c];
+      b = p[a] > b ? p[a] : b;
+      t = p[a] < t ? p[a] : t;
+    }
+  }
+  for (int a = 0; a < 3; ++a) {
+    for (int c = 1; c < CDX_KNN_MAX_DIM; ++c) {
+      double& b = below[a * CDX_KNN_MAX_DIM + c];
+      const double pb = below[a * CDX_KNN_MAX_DIM + c - 1];
+      b = pb > b ? pb : b;
+    }
+    for (int c = CDX_KNN_MAX_DIM - 2; c >= 0; --c) {
+      double& t = above[a * CDX_KNN_MAX_DIM + c];
+      const double pt = above[a * CDX_KNN_MAX_DIM + c + 1];
+      t = pt < t ? pt : t;
+    }
+  }
+}
+
+template <typename T>
+void knn_host(const T* X, int64_t P, const T* Q, int64_t M, int K, double max_d2, int mode, int64_t* idx, double* d2,
+              int32_t* count) {
+  cdx::KnnGrid g;
+  std::vector<int32_t> cell;
+  std::vector<double> below, above;
+  std::vector<std::vector<int64_t>> rows;  // of every cell
+  if (mode == CDX_KNN_GRID) {
+    cell.resize(3 * P);
+    below.resize(3 * CDX_KNN_MAX_DIM);
+    above.resize(3 * CDX_KNN_MAX_DIM);
+    knn_grid_host(X, P, g, cell.data(), below.data(), above.data());
+    rows.resize((size_t)g.n[0] * g.n[1] * g.n[2]);
+    for (int64_t j = 0; j < P; ++j)
+      if (cell[3 * j] >= 0) rows[((size_t)cell[3 * j] * g.n[1] + cell[3 * j + 1]) * g.n[2] + cell[3 * j + 2]].push_back(j);
+  }
+  for (int64_t m = 0; m < M; ++m) {
+    const double q[3] = {(double)Q[3 * m], (double)Q[3 * m + 1], (double)Q[3 * m + 2]};
+    KnnHostList l;
+    l.n = 0;
+    l.K = K;
+    l.max_d2 = max_d2;
+    auto offer = [&](int64_t j) {
+      const double x = (double)X[3 * j], y = (double)X[3 * j + 1], z = (double)X[3 * j + 2];
+      if (cdx::knn_finite3(x, y, z)) l.offer(cdx::fps_sqdist(x, y, z, q[0], q[1], q[2]), j);
+    };
+    if (cdx::knn_finite3(q[0], q[1], q[2])) {
+      if (mode != CDX_KNN_GRID) {
+        for (int64_t j = 0; j < P; ++j) offer(j);
+      } else {
+        int cq[3];
+        for (int a = 0; a < 3; ++a) cq[a] = cdx::knn_cell(q[a], g.lo[a], g.inv, g.n[a]);
+        const int rings = std::max(g.n[0], std::max(g.n[1], g.n[2]));
+        for (int r = 0; r < rings; ++r) {
+          for (int x = std::max(cq[0] - r, 0); x <= std::min(cq[0] + r, g.n[0] - 1); ++x)
+            for (int y = std::max(cq[1] - r, 0); y <= std::min(cq[1] + r, g.n[1] - 1); ++y)
+              for (int z = std::max(cq[2] - r, 0); z <= std::min(cq[2] + r, g.n[2] - 1); ++z) {
+                const int ch = std::max(std::abs(x - cq[0]), std::max(std::abs(y - cq[1]), std::abs(z - cq[2])));
+                if (ch != r) continue;
+                for (int64_t j : rows[((size_t)x * g.n[1] + y) * g.n[2] + z]) offer(j);
+              }
+          bool none;
+          const double bound = cdx::knn_ring_bound(g, below.data(), above.data(), q, cq, r, &none);
+          const double kth = l.n == K ? l.d[K - 1] : (double)INFINITY;
+          if (none || bound > kth || bound > max_d2) break;
+        }
+      }
+    }
+    for (int t = 0; t < K; ++t) {
+      idx[m * K + t] = t < l.n ? l.i[t] : -1;
+      if (d2) d2[m * K + t] = t < l.n ? l.d[t] : (double)INFINITY;
+    }
+    if (count) count[m] = l.n;
+  }
+}
+
+template <typename T>
+void normals_host(const T* X, int64_t P, const int64_t* idx, const int32_t* count, int K, const double* eye,
+                  double* normals, double* eigenvalues, double* cov) {
+  for (int64_t row = 0; row < P; ++row) {
+    int c = count[row];
+    c = c < 0 ? 0 : (c > K ? K : c);
+    const int64_t* list = idx + row * K;
+    cdx::KnnMoments k;
+    cdx::knn_moments_init(k);
+    for (int t = 0; t < c; ++t) {
+      const int64_t j = list[t];
+      if (j < 0 || j >= P) {
+        c = t;
+        break;
+      }
+      cdx::knn_moments_sum(k, (double)X[3 * j], (double)X[3 * j + 1], (double)X[3 * j + 2]);
+    }
+    if (c > 0) cdx::knn_moments_mean(k, c);
+    for (int t = 0; t < c; ++t) {
+      const int64_t j = list[t];
+      cdx::knn_moments_cov(k, (double)X[3 * j], (double)X[3 * j + 1], (double)X[3 * j + 2]);
+    }
+    const double p[3] = {(double)X[3 * row], (double)X[3 * row + 1], (double)X[3 * row + 2]};
+    double n[3], w[3];
+    cdx::knn_normal_finish(k, c, p, eye != nullptr, eye, n, w, cov ? cov + 6 * row : nullptr);
+    for (int a = 0; a < 3; ++a) {
+      normals[3 * row + a] = n[a];
+      if (eigenvalues) eigenvalues[3 * row + a] = w[a];
+    }
+  }
 }
 
 // The rule of cdx_fps.h as a plain single-threaded loop over one cloud.
@@ -423,6 +600,83 @@ int cdxh_fps(const void* X, int32_t dtype, int64_t P, int64_t B, int64_t K, int6
     double* pb = points ? points + b * K * 3 : nullptr;
     if (dtype == CDX_DTYPE_F32) fps_host(static_cast<const float*>(X) + b * P * 3, P, K, start, sb, rb, pb);
     else fps_host(static_cast<const double*>(X) + b * P * 3, P, K, start, sb, rb, pb);
+  }
+  return CDX_OK;
+}
+
+// Host build of cdx_knn (same arguments without the grid, the workspace and the stream; host pointers).  mode
+// CDX_KNN_SCAN (or AUTO): brute force over the rule of cdx_knn.h.  CDX_KNN_GRID: the ring walk over a grid built here
+// with the rule's own cell assignment and bound.  tests/test_knn_cpu.py checks both against a numpy statement.
+int cdxh_knn(const void* X, int32_t dtype, int64_t P, const void* Q, int64_t M, int64_t K, double max_d2, int32_t mode,
+             int64_t* idx, double* d2, int32_t* count) {
+  if (!X || P < 1 || P >= ((int64_t)1 << 31) - 1024 || M < 0 || K < 1 || K > CDX_KNN_MAX_K) return CDX_EINVAL;
+  if ((dtype != CDX_DTYPE_F32 && dtype != CDX_DTYPE_F64) || mode < CDX_KNN_AUTO || mode > CDX_KNN_GRID)
+    return CDX_EINVAL;
+  if (!Q) {
+    Q = X;
+    M = P;
+  }
+  if (M == 0) return CDX_OK;
+  if (!idx) return CDX_EINVAL;
+  if (dtype == CDX_DTYPE_F32)
+    knn_host(static_cast<const float*>(X), P, static_cast<const float*>(Q), M, (int)K, max_d2, mode, idx, d2, count);
+  else
+    knn_host(static_cast<const double*>(X), P, static_cast<const double*>(Q), M, (int)K, max_d2, mode, idx, d2, count);
+  return CDX_OK;
+}
+
+// Host build of cdx_cloud_normals (no stream; host pointers); cov [P·6], nullable, receives each row's covariance.
+int cdxh_cloud_normals(const void* X, int32_t dtype, int64_t P, const int64_t* idx, const int32_t* count, int64_t K,
+                       const double* eye, double* normals, double* eigenvalues, double* cov) {
+  if (!X || !idx || !count || !normals || P < 1 || K < 1 || K > CDX_KNN_MAX_K) return CDX_EINVAL;
+  if (dtype != CDX_DTYPE_F32 && dtype != CDX_DTYPE_F64) return CDX_EINVAL;
+  if (dtype == CDX_DTYPE_F32)
+    normals_host(static_cast<const float*>(X), P, idx, count, (int)K, eye, normals, eigenvalues, cov);
+  else
+    normals_host(static_cast<const double*>(X), P, idx, count, (int)K, eye, normals, eigenvalues, cov);
+  return CDX_OK;
+}
+
+// cdx::sym3_eig on n symmetric matrices A [n·6] = (a00, a01, a02, a11, a12, a22): w [n·3] ascending, V [n·9] row-major
+// with the eigenvectors in columns.
+void cdxh_sym3_eig(const double* A, int64_t n, double* w, double* V) {
+  for (int64_t k = 0; k < n; ++k) {
+    const double* a = A + 6 * k;
+    cdx::sym3_eig(a[0], a[1], a[2], a[3], a[4], a[5], w + 3 * k, V + 9 * k);
+  }
+}
+
+// The grid of cdx_knn.h for a float64 cloud: info = (lo[3], inv) doubles and dims = n[3]; cell [P·3] the cell of every
+// row (−1 for a non-finite one); below / above [3·CDX_KNN_MAX_DIM].
+int cdxh_knn_grid(const double* X, int64_t P, double* info, int32_t* dims, int32_t* cell, double* below,
+                  double* above) {
+  if (!X || P < 1 || !info || !dims || !cell || !below || !above) return CDX_EINVAL;
+  cdx::KnnGrid g;
+  knn_grid_host(X, P, g, cell, below, above);
+  for (int a = 0; a < 3; ++a) {
+    info[a] = g.lo[a];
+    dims[a] = g.n[a];
+  }
+  info[3] = g.inv;
+  return CDX_OK;
+}
+
+// Cell cq [3] of the queries Q [M·3] in that grid and, for ring r, cdx::knn_ring_bound of each: bound [M], none [M].
+int cdxh_knn_ring_bound(const double* info, const int32_t* dims, const double* below, const double* above,
+                        const double* Q, int64_t M, int32_t r, int32_t* cq, double* bound, int32_t* none) {
+  cdx::KnnGrid g;
+  for (int a = 0; a < 3; ++a) {
+    g.lo[a] = info[a];
+    g.n[a] = dims[a];
+  }
+  g.inv = info[3];
+  g.pad = 0;
+  for (int64_t m = 0; m < M; ++m) {
+    int c[3];
+    for (int a = 0; a < 3; ++a) c[a] = cq[3 * m + a] = cdx::knn_cell(Q[3 * m + a], g.lo[a], g.inv, g.n[a]);
+    bool nn;
+    bound[m] = cdx::knn_ring_bound(g, below, above, Q + 3 * m, c, r, &nn);
+    none[m] = nn;
   }
   return CDX_OK;
 }

@@ -260,18 +260,26 @@ class GPIS:
         self._gen += 1
 
     def fit_pointcloud(self, points, num_points=200, bound=0.15, n_internal=50, sharpness=30.0,
-                       noise=(0.2, 0.005, 0.1), center="bbox", weights=None, generator=None, start=0):
+                       noise=(0.2, 0.005, 0.1), center="bbox", weights=None, generator=None, start=0,
+                       outlier=None):
         """From a raw cloud [P, 3] on the device to the fitted state (optimize_pregrasp.py:904-922): a
         farthest-point sample of ``num_points`` rows (cdx_fps, beginning at row ``start``), the recipe of
         ``pointcloud.completion_arrays`` around it, then ``fit``.  ``center="bbox"`` shifts the exterior points by
         the centre of the bounding box of the whole finite cloud (:894), computed on the device; None leaves them at
         the origin, anything else is the centre itself.  ``bound=0.1, n_internal=5, sharpness=10,
         noise=(0.3, σ_obs, 0.02), center=None`` is train_gpis_completion.py.  The chosen rows stay in
-        ``self.sample_index`` (selection order).  No host synchronisation from the cloud to ``E11``; returns self."""
+        ``self.sample_index`` (selection order).  ``outlier=(nb_neighbors, std_ratio)`` first sets the rows that
+        ``pointcloud.statistical_outlier_mask`` rejects to NaN: they are then never sampled and are left out of the
+        bounding-box centre (``start`` itself is taken as given).  No host synchronisation from the cloud to
+        ``E11``; returns self."""
         from . import pointcloud as PC
         _require_cuda(points, "point cloud")
         if points.dim() != 2:
             raise ValueError(f"point cloud must be [P, 3], got {tuple(points.shape)}")
+        if outlier is not None:
+            nb_neighbors, std_ratio = outlier
+            keep = PC.statistical_outlier_mask(points, int(nb_neighbors), float(std_ratio))
+            points = torch.where(keep.unsqueeze(1), points.detach(), torch.full_like(points, float("nan")))
         sel, _, surface = PC.fps(points, num_points, start, gather=True)
         if isinstance(center, str):
             if center != "bbox":

@@ -249,6 +249,41 @@ int cdx_sample_draw(const void* faces, int32_t dtype, int64_t F, const uint64_t*
                     int64_t K, int32_t mode, double* points, int64_t* face, double* bary, double* normal,
                     cdx_stream_t stream);
 
+/* k-nearest-neighbour search in a cloud, and the normals of a cloud from its neighbour lists (concatenate_pcd.py:35-36:
+ * open3d's estimate_normals and orient_normals_towards_camera_location in the reference; open3d's
+ * remove_statistical_outlier and compute_point_cloud_distance are the same query).  The rule is csrc/cdx_knn.h.
+ * X [P·3] and Q [M·3] float or double (one dtype = CDX_DTYPE_* for both), 1 ≤ P < 2³¹ − 1024, 1 ≤ K ≤ CDX_KNN_MAX_K.
+ * cdx_knn: row m of idx [M·K] / d2 [M·K] (nullable) holds the K smallest (d2, index) pairs of query m in ascending
+ *   order, d2 = (dx·dx + dy·dy) + dz·dz in float64, ties to the smaller index; pairs with d2 > max_d2 are left out
+ *   (+inf: none); count [M] (nullable) = pairs found, the slots past it hold −1 and +inf.  A cloud row with a
+ *   non-finite coordinate is never a neighbour, a query with one gets count 0.  Q null: the queries are X's rows (M
+ *   is then P whatever was passed).  M = 0 is a no-op.
+ *   mode CDX_KNN_SCAN: every row against every query, `grid` may be NULL;  CDX_KNN_GRID: the uniform grid of
+ *   cdx_knn_prepare on these X and P;  CDX_KNN_AUTO: the grid when one is given and P is above the measured threshold
+ *   (DESIGN §5i), else the scan.  All give the same bits.
+ *   Workspace: cdx_knn_workspace(P, M, K, mode) bytes (0 for a bad argument); reserved — both paths keep their lists in
+ *   registers and neither reads nor writes it, so NULL is accepted.
+ * cdx_knn_prepare: the grid of X into `grid`, caller-owned cdx_knn_grid_bytes(P) bytes (0 for a bad P), which need no
+ *   clearing and may be prepared again for any cloud whose cdx_knn_grid_bytes fits.  No host synchronisation.
+ * cdx_cloud_normals: normals [P·3] and eigenvalues [P·3] (nullable, ascending) of X's rows from their lists idx [P·K],
+ *   count [P]; eye: 3 host doubles to orient the normals towards, or NULL for the largest-component-positive sign.
+ *   Fewer than 3 neighbours: (0, 0, 1) and NaN eigenvalues; a non-finite row: NaN.
+ * CDX_EINVAL: K outside 1 … CDX_KNN_MAX_K, P out of range, M < 0, null X (idx with M > 0; idx, count or normals for the
+ *   normals), CDX_KNN_GRID without a grid, an unknown dtype or mode. */
+#define CDX_KNN_AUTO 0
+#define CDX_KNN_SCAN 1
+#define CDX_KNN_GRID 2
+#define CDX_KNN_MAX_K 64
+int64_t cdx_knn_auto_rows(void); /* CDX_KNN_AUTO scans clouds of up to this many rows */
+size_t cdx_knn_grid_bytes(int64_t P);
+int cdx_knn_prepare(const void* X, int32_t dtype, int64_t P, void* grid, cdx_stream_t stream);
+size_t cdx_knn_workspace(int64_t P, int64_t M, int64_t K, int32_t mode);
+int cdx_knn(const void* X, int32_t dtype, int64_t P, const void* grid, const void* Q, int64_t M, int64_t K,
+            double max_d2, int32_t mode, void* workspace, int64_t* idx, double* d2, int32_t* count,
+            cdx_stream_t stream);
+int cdx_cloud_normals(const void* X, int32_t dtype, int64_t P, const int64_t* idx, const int32_t* count, int64_t K,
+                      const double* eye, double* normals, double* eigenvalues, cdx_stream_t stream);
+
 /* ------------------------------------------------------------------ FK ----------
  * Replaces DifferentiableRobotModel.compute_forward_kinematics(q, link_names,
  * recursive=False, offsets) (robot_model.py:224-264 with update_kinematic_state
