@@ -2,7 +2,10 @@
 
 Drop-in operators (same names / arguments as the reference):
   GPIS                         gpis.py:4-168
-  DifferentiableRobotModel     differentiable_robot_model/robot_model.py (FK)
+  DifferentiableRobotModel     differentiable_robot_model/robot_model.py (FK, compute_endeffector_jacobian)
+  solve_ik / IKResult / DifferentiableRobotModel.inverse_kinematics / results.joint_angles_from_contacts
+                               PyBullet's calculateInverseKinematics (verify_pregrasp.py:50-53): fingertips → joint
+                               angles for E candidates in one launch, parity with PyBullet's solver unpinned
   compute_sdf                  torchsdf/sdf.py
   ProbabilisticGraspOptimizer  optimize_pregrasp.py:614-839
   KinGraspOptimizer / SDFGraspOptimizer / GPISGraspOptimizer / KinGPISGraspOptimizer
@@ -41,6 +44,7 @@ from .raycast import (Camera, cast_rays, depth_to_pointcloud, observable_pointcl
 from .sampling import (SurfaceSampler, sample_points_poisson_disk, sample_points_uniformly,  # noqa: F401
                        surface_sampler)
 from .robot_model import DifferentiableRobotModel  # noqa: F401
+from .ik import IKResult, solve_ik  # noqa: F401
 from .torchsdf import PreparedMesh, compute_sdf, compute_sdf_with_faces, index_vertices_by_faces  # noqa: F401
 
 __version__ = "0.1.0"

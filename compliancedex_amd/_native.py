@@ -49,6 +49,12 @@ class CdxChain(C.Structure):
                 ("bodies", CdxBody * MAX_BODIES)]
 
 
+class CdxIkParams(C.Structure):
+    _fields_ = [("lower", C.c_double * MAX_DOFS), ("upper", C.c_double * MAX_DOFS), ("ref_q", C.c_double * MAX_DOFS),
+                ("rho", C.c_double), ("tol", C.c_double), ("mu0", C.c_double), ("mu_min", C.c_double),
+                ("mu_max", C.c_double), ("nu", C.c_double), ("max_iters", C.c_int32), ("_pad", C.c_int32)]
+
+
 class CdxProblem(C.Structure):
     _fields_ = [("chain", CdxChain), ("gpis", CdxGpis), ("n_levels", C.c_int32), ("n_query_levels", C.c_int32),
                 ("level_query", C.c_int32 * MAX_LEVELS), ("coeff", (C.c_float * MAX_TIPS) * MAX_LEVELS),
@@ -195,6 +201,12 @@ _SIGS = {
     "cdx_gpis_factor": (C.c_int, [_P, _P, C.c_int32, C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     "cdx_fk_forward": (C.c_int, [C.POINTER(CdxChain), _P, _I64, _P, _P, _P]),
     "cdx_fk_backward": (C.c_int, [C.POINTER(CdxChain), _P, _I64, _P, _P, _P]),
+    "cdx_fk_jacobian": (C.c_int, [C.POINTER(CdxChain), _P, _I64, _P, _P, _P]),
+    "cdx_ik_workspace": (C.c_size_t, [_I64, C.c_int32, C.c_int32]),
+    "cdx_ik_rows_per_block": (C.c_int32, [C.c_int32, C.c_int32]),
+    "cdx_ik_abi_size": (C.c_size_t, []),
+    "cdx_ik_solve": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxIkParams), _I64, _P, C.c_int32, _P, _P,
+                               C.POINTER(C.c_double), _P, _P, _P, _P, _P, _P, _P]),
     "cdx_force_eq_forward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
                                        _P]),
     "cdx_force_eq_backward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
@@ -296,6 +308,9 @@ def load():
         mine = [C.sizeof(CdxGpisModeParams), C.sizeof(CdxGpisModeOpt), C.sizeof(CdxGpisModeBuffers)]
         if list(sizes) != mine:
             raise ImportError(f"ABI struct size mismatch (GPIS mode): library {list(sizes)} vs binding {mine}")
+        if lib.cdx_ik_abi_size() != C.sizeof(CdxIkParams):
+            raise ImportError(f"ABI struct size mismatch (IK): library {lib.cdx_ik_abi_size()} vs binding "
+                              f"{C.sizeof(CdxIkParams)}")
         info = build_info()
         if not info["matches"] and "CDX_LIB" not in os.environ:
             import warnings

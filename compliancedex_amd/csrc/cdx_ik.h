@@ -1,0 +1,362 @@
+// Fingertip Jacobians and batched inverse kinematics: the rule shared by the kernels (cdx_ik.hip) and the host build
+// (host_ref.cpp: cdxh_fk_jacobian, cdxh_ik_solve, the CPU yardsticks of those kernels).  The reference turns fingertips
+// back into a hand pose with PyBullet's calculateInverseKinematics (verify_pregrasp.py:50-53, bullet_robot.py:262-280)
+// and has compute_endeffector_jacobian (robot_model.py:643-683); parity with PyBullet's solver is unpinned.
+//
+// Jacobian.  For tip k of the chain at joint row q (float32), with p the tip position of cdx_fk_forward (offset
+//   included), and for every moving joint j on the tip's path its world axis ω_j = R_parent·F_j·e_axis and world
+//   origin o_j (what fk_tip_walk3s keeps):
+//     lin[:, dof_j] = sign_j · ω_j × (p − o_j),   ang[:, dof_j] = sign_j · ω_j        (robot_model.py:677-678)
+//   all in float32 with the functions of the FK kernels (chain_step, tip_from_pose); the columns of joints off the
+//   path are exactly 0.  Two walks of the path: the first gives p, the second the columns — no per-level storage.
+//   This is the TRUE derivative of the fingertip position.  It is deliberately NOT cdx_fk_backward's, which
+//   reproduces the reference autograd's detached quaternion scale (cdx_fk.h) and so differs wherever a tip offset is
+//   set.
+//
+// Inverse kinematics.  Per candidate row, independent of every other row.  Inputs: q0 [D] (float64, or float32
+//   widened), target [T][3], palm [6] = position + XYZ Euler angles (null: identity), w [T] (null: all 1), and per call
+//   palm_offset [3] and cdx_ik_params.  A row with a non-finite q0 (as given or rounded to float32), target, palm or w
+//   has status 2: its q is q0 unchanged, its err NaN, its iters 0.  w ≥ 0 is the caller's contract and is not checked.
+//   Fingertips.  tip_k(q) = (Rp·double(FK_f32(q)_k) + palm_pos) + palm_offset, Rp = euler_xyz(palm[3:6]) in float64
+//     (cdx_cost.h), the products summed left to right.  d_k = target_k − tip_k, e_k = sqrt((dx² + dy²) + dz²),
+//     r_k = w_k·d_k, cost(q) = ½·Σ_k ((rx² + ry²) + rz²) + ½·ρ·Σ_d (q_d − ref_d)², emax = max_k w_k·e_k.
+//   Bounds.  lower / upper are rounded INWARD to float32 once (ik_prepare), so a float32 q never leaves the float64 box;
+//     if that crosses them (lower == upper not a float32) both become float(lower).  q ← clamp(float(q0)).
+//   Loop, with μ = mu0 and iters = 0:
+//     if emax ≤ tol: status 0, stop.   if iters == max_iters: status 1, stop.   iters += 1.
+//     Jl [3T × D] = lin of every tip at q, widened.  The weighted world Jacobian is Jw = diag(w)·blockdiag(Rp)·Jl; Rp is
+//       orthogonal and w is constant per tip, so Jw·Jwᵀ + κI = blockdiag(Rp)·(W·Jl·Jlᵀ·W + κI)·blockdiag(Rp)ᵀ and the
+//       whole step is taken in the palm frame with u_k = w_k·Rpᵀ·r_k: the same step up to rounding, Jl kept as the
+//       float32 it is.
+//     g_d = Σ_rows Jl[row][d]·u[row] + ρ·(ref_d − q_d).
+//     A joint with q_d ≤ lower_d and g_d < 0, or q_d ≥ upper_d and g_d > 0, is fixed for this step: g_d = 0 and column d
+//       of Jl is zeroed.
+//     κ = μ + ρ.  A = W·Jl·Jlᵀ·W + κI (3T × 3T, lower triangle, A_ab = (w_a·w_b)·Σ_d Jl[a][d]·Jl[b][d]);
+//       b_a = w_a·Σ_d Jl[a][d]·g_d;  A = L·Lᵀ by Cholesky (row by row), y = A⁻¹·b by two substitutions;
+//       δ_d = (g_d − Σ_a Jl[a][d]·(w_a·y_a)) / κ — the damped step (JwᵀJw + κI)⁻¹·g through the 3T × 3T system.
+//     q′_d = float(clamp(double(q_d) + δ_d, lower_d, upper_d)).
+//     Accepted if every pivot was > 0 and cost(q′) < cost(q): q ← q′, μ ← max(μ/ν, μ_min).  Else μ ← min(μ·ν, μ_max).
+//     The accepted cost never rises.
+//   Outputs: q (float32 values), err_k = e_k at the returned q (unweighted), iters, status.
+//
+// Storage.  Every per-row array (IkMem) is addressed as base[i·s]: s = 1 on the host, and on the device the arrays of
+// the lanes of a workgroup are interleaved in LDS (s = lanes, base shifted by the lane), so no array indexed at run time
+// lives in registers (it would go to scratch).
+#pragma once
+#include "cdx_cost.h"
+
+// The inner loops of the solve run over run-time bounds and read LDS: unrolled by four, the loads of four terms are in
+// flight together while the sums keep their order (the same bits).
+#if defined(__HIPCC__)
+#define CDX_IK_UNROLL _Pragma("unroll 4")
+#else
+#define CDX_IK_UNROLL
+#endif
+
+namespace cdx {
+
+// q[i] of a strided float row.
+struct QStride {
+  const float* p;
+  int s;
+  CDX_HDM float operator[](int i) const { return p[(size_t)i * s]; }
+};
+
+// q0[i] as a double from a float64 or float32 row.
+struct Q0Row {
+  const void* p;
+  int f64;
+  CDX_HDM double operator[](int i) const { return f64 ? ((const double*)p)[i] : (double)((const float*)p)[i]; }
+};
+
+// The Jacobian columns of tip k at q, given its position p (fk_tip): col(dof, lin[3], ang[3]) once per moving joint on
+// the path, in root→tip order.  The poses are chain_step's, as in the FK kernels.
+template <class Q, class COL>
+CDX_HD void fk_tip_columns(const cdx_chain& c, int k, const Q& q, const float* p, COL&& col) {
+  float R[9] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f}, t[3] = {0.f, 0.f, 0.f};
+  for (uint32_t m = chain_path_mask(c, c.tip_body[k]); m; m &= m - 1) {
+    const cdx_body& b = c.bodies[low_bit(m)];
+    float Rn[9], tn[3];
+    chain_step(b, q, R, t, Rn, tn);
+    if (b.dof >= 0) {
+      const int ax = b.axis;  // (selects, not an index: see fk_tip_bwd2)
+      const float fa[3] = {ax == 0 ? b.F[0] : (ax == 1 ? b.F[1] : b.F[2]), ax == 0 ? b.F[3] : (ax == 1 ? b.F[4] : b.F[5]),
+                           ax == 0 ? b.F[6] : (ax == 1 ? b.F[7] : b.F[8])};
+      float om[3];
+      mat3_vec(R, fa, om);
+      const float d[3] = {p[0] - tn[0], p[1] - tn[1], p[2] - tn[2]};
+      const float lin[3] = {b.sign * (om[1] * d[2] - om[2] * d[1]), b.sign * (om[2] * d[0] - om[0] * d[2]),
+                            b.sign * (om[0] * d[1] - om[1] * d[0])};
+      const float ang[3] = {b.sign * om[0], b.sign * om[1], b.sign * om[2]};
+      col((int)b.dof, lin, ang);
+    }
+    for (int i = 0; i < 9; ++i) R[i] = Rn[i];
+    for (int i = 0; i < 3; ++i) t[i] = tn[i];
+  }
+}
+
+// lin / ang [3][D] of one (row, tip); ang nullable.
+template <class Q>
+CDX_HD void fk_jacobian_tip(const cdx_chain& c, int k, const Q& q, float* lin, float* ang) {
+  const int D = c.n_dofs;
+  for (int i = 0; i < 3 * D; ++i) {
+    lin[i] = 0.f;
+    if (ang) ang[i] = 0.f;
+  }
+  float p[3];
+  fk_tip(c, k, q, p, nullptr);
+  fk_tip_columns(c, k, q, p, [&](int d, const float* l, const float* a) {
+    for (int i = 0; i < 3; ++i) {
+      lin[i * D + d] = l[i];
+      if (ang) ang[i * D + d] = a[i];
+    }
+  });
+}
+
+// Per-row storage of the solve, element i at base[i·s].
+struct IkMem {
+  double *A, *g, *y, *dv;  // A: n(n+1)/2 (lower triangle, row-major), g: D, y: n, dv: 2·n (two d buffers)
+  float *J, *q, *qn;       // J: n·D (row-major), q / qn: D
+  int s;
+};
+CDX_HD int ik_mem_doubles(int T, int D) { return (3 * T) * (3 * T + 1) / 2 + D + 3 * T + 6 * T; }
+CDX_HD int ik_mem_floats(int T, int D) { return 3 * T * D + 2 * D; }
+CDX_HD size_t ik_mem_bytes(int T, int D) { return (size_t)ik_mem_doubles(T, D) * 8 + (size_t)ik_mem_floats(T, D) * 4; }
+// The arrays of `lane` among `s` lanes in a block of ik_mem_bytes(T, D)·s bytes (8-byte aligned).
+CDX_HD IkMem ik_mem_at(void* base, int T, int D, int lane, int s) {
+  const int n = 3 * T;
+  IkMem m;
+  double* d = (double*)base + lane;
+  m.A = d;
+  d += (size_t)(n * (n + 1) / 2) * s;
+  m.g = d;
+  d += (size_t)D * s;
+  m.y = d;
+  d += (size_t)n * s;
+  m.dv = d;
+  d += (size_t)(2 * n) * s;
+  float* f = (float*)((double*)base + (size_t)ik_mem_doubles(T, D) * s) + lane;
+  m.J = f;
+  f += (size_t)(n * D) * s;
+  m.q = f;
+  f += (size_t)D * s;
+  m.qn = f;
+  m.s = s;
+  return m;
+}
+
+// Checks the parameters and rounds the bounds inward to float32 (see above).  0, CDX_EINVAL, or CDX_ECHAIN for null.
+CDX_HD int ik_prepare(const cdx_ik_params* in, int D, cdx_ik_params* out) {
+  if (!in) return CDX_ECHAIN;
+  *out = *in;
+  if (in->max_iters < 0) return CDX_EINVAL;
+  const double pos[5] = {in->tol, in->mu0, in->mu_min, in->mu_max, in->nu};
+  for (int i = 0; i < 5; ++i)
+    if (!(__builtin_isfinite(pos[i]) && pos[i] > 0.0)) return CDX_EINVAL;
+  if (!(__builtin_isfinite(in->rho) && in->rho >= 0.0)) return CDX_EINVAL;
+  for (int d = 0; d < D; ++d) {
+    const double lo = in->lower[d], hi = in->upper[d];
+    if (!(lo <= hi) || !__builtin_isfinite(in->ref_q[d])) return CDX_EINVAL;  // (a NaN bound fails lo <= hi)
+    float l = (float)lo, h = (float)hi;
+    if ((double)l < lo) l = nextafterf(l, INFINITY);
+    if ((double)h > hi) h = nextafterf(h, -INFINITY);
+    if (l > h) l = h = (float)lo;
+    out->lower[d] = (double)l;
+    out->upper[d] = (double)h;
+  }
+  return CDX_OK;
+}
+
+// The chain checks of the two entries: null → CDX_ECHAIN, sizes over the descriptor's → CDX_EINVAL, a malformed
+// tree → CDX_ECHAIN.
+CDX_HD int ik_chain_code(const cdx_chain* c) {
+  if (!c) return CDX_ECHAIN;
+  if (c->n_bodies <= 0 || c->n_bodies > CDX_MAX_BODIES || c->n_dofs < 0 || c->n_dofs > CDX_MAX_DOFS || c->n_tips <= 0 ||
+      c->n_tips > CDX_MAX_TIPS)
+    return CDX_EINVAL;
+  for (int i = 1; i < c->n_bodies; ++i)
+    if (c->bodies[i].parent < 0 || c->bodies[i].parent >= i || c->bodies[i].dof >= c->n_dofs) return CDX_ECHAIN;
+  for (int k = 0; k < c->n_tips; ++k)
+    if (c->tip_body[k] < 0 || c->tip_body[k] >= c->n_bodies) return CDX_ECHAIN;
+  return CDX_OK;
+}
+
+// d = target − tip(q) into dv (stride s), cost(q) and emax.
+template <class Q>
+CDX_HD double ik_eval(const cdx_chain& c, const cdx_ik_params& p, const Q& q, const double* target, const double* w,
+                      const double* Rp, const double* pp, const double* po, double* dv, int s, double* emax) {
+  double ss = 0.0, em = 0.0;
+  for (int k = 0; k < c.n_tips; ++k) {
+    float pf[3];
+    fk_tip(c, k, q, pf, nullptr);
+    const double v[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
+    double x[3];
+    mat3_vec(Rp, v, x);
+    const double wk = w ? w[k] : 1.0;
+    double d[3];
+    for (int i = 0; i < 3; ++i) {
+      d[i] = target[3 * k + i] - ((x[i] + pp[i]) + po[i]);
+      dv[(size_t)(3 * k + i) * s] = d[i];
+    }
+    const double e = wk * sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    em = e > em ? e : em;
+    const double r[3] = {wk * d[0], wk * d[1], wk * d[2]};
+    ss += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+  }
+  double sq = 0.0;
+  for (int d = 0; d < c.n_dofs; ++d) {
+    const double dq = (double)q[d] - p.ref_q[d];
+    sq += dq * dq;
+  }
+  *emax = em;
+  return 0.5 * ss + (0.5 * p.rho) * sq;
+}
+
+// One row of the solve (p: after ik_prepare; po: 3 doubles).  Leaves the result in m.q, writes err [T] and *iters,
+// returns the status.  Status 2 leaves m untouched.
+CDX_HD int ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0, const double* target,
+                  const double* palm, const double* w, const IkMem& m, double* err, int32_t* iters) {
+  const int T = c.n_tips, D = c.n_dofs, n = 3 * T, s = m.s;
+  bool fin = true;
+  for (int d = 0; d < D; ++d) {
+    const double v = q0[d];
+    fin = fin && __builtin_isfinite(v) && __builtin_isfinite((float)v);
+  }
+  for (int i = 0; i < n; ++i) fin = fin && __builtin_isfinite(target[i]);
+  if (palm)
+    for (int i = 0; i < 6; ++i) fin = fin && __builtin_isfinite(palm[i]);
+  if (w)
+    for (int k = 0; k < T; ++k) fin = fin && __builtin_isfinite(w[k]);
+  *iters = 0;
+  if (!fin) {
+    for (int k = 0; k < T; ++k) err[k] = NAN;
+    return 2;
+  }
+  double Rp[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, pp[3] = {0.0, 0.0, 0.0};
+  if (palm) {
+    euler_xyz(palm + 3, Rp, nullptr, nullptr, nullptr);
+    for (int i = 0; i < 3; ++i) pp[i] = palm[i];
+  }
+  for (int d = 0; d < D; ++d) {
+    const float f = (float)q0[d], lo = (float)p.lower[d], hi = (float)p.upper[d];
+    m.q[(size_t)d * s] = f < lo ? lo : (f > hi ? hi : f);
+  }
+  const QStride q{m.q, s}, qn{m.qn, s};
+  int cur = 0;
+  double emax;
+  double cost = ik_eval(c, p, q, target, w, Rp, pp, po, m.dv, s, &emax);
+  double mu = p.mu0;
+  int it = 0, status;
+  for (;;) {
+    if (emax <= p.tol) { status = 0; break; }
+    if (it >= p.max_iters) { status = 1; break; }
+    ++it;
+    // Jl at q
+    CDX_IK_UNROLL
+    for (int i = 0; i < n * D; ++i) m.J[(size_t)i * s] = 0.f;
+    for (int k = 0; k < T; ++k) {
+      float pf[3];
+      fk_tip(c, k, q, pf, nullptr);
+      fk_tip_columns(c, k, q, pf, [&](int d, const float* l, const float*) {
+        for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * k + i) * D + d) * s] = l[i];
+      });
+    }
+    // u = w·Rpᵀ·(w·d) into y
+    const double* dc = m.dv + (size_t)(cur * n) * s;
+    for (int k = 0; k < T; ++k) {
+      const double wk = w ? w[k] : 1.0;
+      const double r[3] = {wk * dc[(size_t)(3 * k) * s], wk * dc[(size_t)(3 * k + 1) * s], wk * dc[(size_t)(3 * k + 2) * s]};
+      double u[3];
+      mat3t_vec(Rp, r, u);
+      for (int i = 0; i < 3; ++i) m.y[(size_t)(3 * k + i) * s] = wk * u[i];
+    }
+    // g, and the joints fixed on their bounds
+    for (int d = 0; d < D; ++d) {
+      double acc = 0.0;
+      CDX_IK_UNROLL
+      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * D + d) * s] * m.y[(size_t)a * s];
+      const double qd = (double)q[d];
+      double g = acc + p.rho * (p.ref_q[d] - qd);
+      if ((qd <= p.lower[d] && g < 0.0) || (qd >= p.upper[d] && g > 0.0)) {
+        g = 0.0;
+        for (int a = 0; a < n; ++a) m.J[(size_t)(a * D + d) * s] = 0.f;
+      }
+      m.g[(size_t)d * s] = g;
+    }
+    const double kappa = mu + p.rho;
+    // A and b
+    for (int a = 0; a < n; ++a) {
+      const double wa = w ? w[a / 3] : 1.0;
+      for (int b = 0; b <= a; ++b) {
+        const double wb = w ? w[b / 3] : 1.0;
+        double acc = 0.0;
+        CDX_IK_UNROLL
+        for (int d = 0; d < D; ++d) acc += (double)m.J[(size_t)(a * D + d) * s] * (double)m.J[(size_t)(b * D + d) * s];
+        acc = (wa * wb) * acc;
+        if (a == b) acc += kappa;
+        m.A[(size_t)(a * (a + 1) / 2 + b) * s] = acc;
+      }
+      double acc = 0.0;
+      CDX_IK_UNROLL
+      for (int d = 0; d < D; ++d) acc += (double)m.J[(size_t)(a * D + d) * s] * m.g[(size_t)d * s];
+      m.y[(size_t)a * s] = wa * acc;
+    }
+    // A = L·Lᵀ in place
+    bool pd = true;
+    for (int i = 0; i < n; ++i)
+      for (int j = 0; j <= i; ++j) {
+        double sum = m.A[(size_t)(i * (i + 1) / 2 + j) * s];
+        CDX_IK_UNROLL
+        for (int k = 0; k < j; ++k) sum -= m.A[(size_t)(i * (i + 1) / 2 + k) * s] * m.A[(size_t)(j * (j + 1) / 2 + k) * s];
+        if (i == j) {
+          pd = pd && sum > 0.0;
+          m.A[(size_t)(i * (i + 1) / 2 + j) * s] = sqrt(sum);
+        } else {
+          m.A[(size_t)(i * (i + 1) / 2 + j) * s] = sum / m.A[(size_t)(j * (j + 1) / 2 + j) * s];
+        }
+      }
+    for (int i = 0; i < n; ++i) {
+      double sum = m.y[(size_t)i * s];
+      CDX_IK_UNROLL
+      for (int k = 0; k < i; ++k) sum -= m.A[(size_t)(i * (i + 1) / 2 + k) * s] * m.y[(size_t)k * s];
+      m.y[(size_t)i * s] = sum / m.A[(size_t)(i * (i + 1) / 2 + i) * s];
+    }
+    for (int i = n - 1; i >= 0; --i) {
+      double sum = m.y[(size_t)i * s];
+      CDX_IK_UNROLL
+      for (int k = i + 1; k < n; ++k) sum -= m.A[(size_t)(k * (k + 1) / 2 + i) * s] * m.y[(size_t)k * s];
+      m.y[(size_t)i * s] = sum / m.A[(size_t)(i * (i + 1) / 2 + i) * s];
+    }
+    for (int a = 0; a < n; ++a) m.y[(size_t)a * s] = (w ? w[a / 3] : 1.0) * m.y[(size_t)a * s];
+    // the trial point
+    for (int d = 0; d < D; ++d) {
+      double acc = 0.0;
+      CDX_IK_UNROLL
+      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * D + d) * s] * m.y[(size_t)a * s];
+      const double v = (double)q[d] + (m.g[(size_t)d * s] - acc) / kappa;
+      m.qn[(size_t)d * s] = (float)(v < p.lower[d] ? p.lower[d] : (v > p.upper[d] ? p.upper[d] : v));
+    }
+    double emn;
+    const double cn = ik_eval(c, p, qn, target, w, Rp, pp, po, m.dv + (size_t)((1 - cur) * n) * s, s, &emn);
+    if (pd && cn < cost) {
+      for (int d = 0; d < D; ++d) m.q[(size_t)d * s] = m.qn[(size_t)d * s];
+      cur = 1 - cur;
+      cost = cn;
+      emax = emn;
+      mu = mu / p.nu;
+      mu = mu > p.mu_min ? mu : p.mu_min;
+    } else {
+      mu = mu * p.nu;
+      mu = mu < p.mu_max ? mu : p.mu_max;
+    }
+  }
+  const double* dc = m.dv + (size_t)(cur * n) * s;
+  for (int k = 0; k < T; ++k) {
+    const double d[3] = {dc[(size_t)(3 * k) * s], dc[(size_t)(3 * k + 1) * s], dc[(size_t)(3 * k + 2) * s]};
+    err[k] = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+  }
+  *iters = it;
+  return status;
+}
+
+}  // namespace cdx

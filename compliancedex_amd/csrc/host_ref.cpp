@@ -15,6 +15,7 @@
 #include "cdx_field.h"
 #include "cdx_fps.h"
 #include "cdx_gpis_mode.h"
+#include "cdx_ik.h"
 #include "cdx_knn.h"
 #include "cdx_mesh.h"
 #include "cdx_ray.h"
@@ -342,6 +343,53 @@ void cdxh_fk_backward(const cdx_chain* c, const float* q, int64_t B, const float
     for (int i = 0; i < c->n_dofs; ++i) g[i] = 0.f;
     for (int k = 0; k < c->n_tips; ++k) cdx::fk_tip_bwd(*c, k, q + b * c->n_dofs, gpos + (b * c->n_tips + k) * 3, cdx::GqAdd{g});
   }
+}
+
+// Geometric fingertip Jacobians and the batched IK solve (cdx_ik.h), with the device entries' argument checks.
+int cdxh_fk_jacobian(const cdx_chain* c, const float* q, int64_t B, float* lin, float* ang) {
+  const int rc = cdx::ik_chain_code(c);
+  if (rc) return rc;
+  if (B < 0) return CDX_EINVAL;
+  if (B == 0) return CDX_OK;
+  if (!q || !lin) return CDX_ECHAIN;
+  const int T = c->n_tips, D = c->n_dofs;
+  for (int64_t t = 0; t < B * T; ++t)
+    cdx::fk_jacobian_tip(*c, (int)(t % T), q + (t / T) * D, lin + t * 3 * D, ang ? ang + t * 3 * D : nullptr);
+  return CDX_OK;
+}
+
+int cdxh_ik_solve(const cdx_chain* c, const cdx_ik_params* params, int64_t E, const void* q0, int32_t q_dtype,
+                  const double* target, const double* palm, const double* palm_offset, const double* w, void* q,
+                  double* err, int32_t* iters, int32_t* status) {
+  int rc = cdx::ik_chain_code(c);
+  if (rc) return rc;
+  cdx_ik_params p;
+  rc = cdx::ik_prepare(params, c->n_dofs, &p);
+  if (rc) return rc;
+  if (E < 0 || (q_dtype != CDX_DTYPE_F32 && q_dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (!q0 || !target || !q || !err || !iters || !status) return CDX_ECHAIN;
+  double po[3];
+  for (int i = 0; i < 3; ++i) {
+    po[i] = palm_offset ? palm_offset[i] : 0.0;
+    if (!__builtin_isfinite(po[i])) return CDX_EINVAL;
+  }
+  const int T = c->n_tips, D = c->n_dofs, f64 = q_dtype == CDX_DTYPE_F64;
+  std::vector<double> mem((cdx::ik_mem_bytes(T, D) + 7) / 8);
+  const cdx::IkMem m = cdx::ik_mem_at(mem.data(), T, D, 0, 1);
+  for (int64_t e = 0; e < E; ++e) {
+    const cdx::Q0Row q0r{f64 ? (const void*)((const double*)q0 + e * D) : (const void*)((const float*)q0 + e * D), f64};
+    const int st = cdx::ik_row(*c, p, po, q0r, target + e * T * 3, palm ? palm + e * 6 : nullptr,
+                               w ? w + e * T : nullptr, m, err + e * T, iters + e);
+    for (int d = 0; d < D; ++d) {
+      if (f64)
+        ((double*)q)[e * D + d] = st == 2 ? ((const double*)q0)[e * D + d] : (double)m.q[d];
+      else
+        ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : m.q[d];
+    }
+    status[e] = st;
+  }
+  return CDX_OK;
 }
 
 int64_t cdxh_n_queries(const cdx_problem* P, int64_t E) { return cdx::n_queries(*P, E); }

@@ -43,3 +43,21 @@ def optimize_and_save(optimizer, gpis, init_joint_angles, target_pose, complianc
     contact = optimizer.forward_kinematics(q, palm)
     save_results(exp_name, contact, target, palm, comp, q, data_dir)
     return dict(joint_angle=q, compliance=comp, target=target, wrist=palm, margin=margin, contact=contact)
+
+
+def joint_angles_from_contacts(robot_model, hand_config, contact, wrist=None, q0=None, **ik):
+    """Joint angles for a result set's ``contact`` [E, T, 3] (and its ``wrist`` [E, 6] rows, if it has them) by the
+    device IK → (joint_angle [E, D] float64, status [E] int32; 0 = reached within tol).  This fills
+    ``save_results(..., joint_angle)`` for the fingertip-space optimisers (GPISGraspOptimizer, SDFGraspOptimizer), whose
+    result the reference's writer cannot complete (optimize_pregrasp.py:1005, :1020).  ``hand_config``: the robot's
+    config dict (ee_link_name, ee_link_offset, ref_q); ``q0`` None starts at ref_q; ``ik``: options of
+    ik.solve_ik (palm_offset, weights, rho, max_iters, tol, …).  Copies the result to the host."""
+    import torch
+    dev = robot_model._device
+    contact = torch.as_tensor(contact, dtype=torch.float64, device=dev)
+    if wrist is not None:
+        wrist = torch.as_tensor(wrist, dtype=torch.float64, device=dev)
+    ref_q = ik.pop("ref_q", hand_config.get("ref_q"))
+    res = robot_model.inverse_kinematics(contact, hand_config["ee_link_name"], hand_config.get("ee_link_offset"), q0=q0,
+                                         palm_pose=wrist, ref_q=ref_q, **ik)
+    return res.q.double().cpu().numpy(), res.status.cpu().numpy()

@@ -1,7 +1,9 @@
 """Drop-in for ``DifferentiableRobotModel`` FK (thirdparty/differentiable-robot-model/
 differentiable_robot_model/robot_model.py) on MI355X: ``compute_forward_kinematics``
 (:224-264) with the reference's float32 arithmetic and gradient (cdx_fk_forward /
-cdx_fk_backward).  Dynamics (ID/FD/ABA/Jacobians, :266-806) are not on the path.
+cdx_fk_backward), ``compute_endeffector_jacobian`` (:643-683, cdx_fk_jacobian) and, beyond the
+reference, batched inverse kinematics (cdx_ik_solve, ik.py).  Dynamics (ID/FD/ABA, :266-806) are
+not on the path.
 """
 from __future__ import annotations
 
@@ -70,6 +72,15 @@ class DifferentiableRobotModel(torch.nn.Module):
         ``recursive=True`` returns the same fresh-state result: the reference's recursive
         branch composes with each body's pose left over from the previous call
         (rigid_body.py:111-118) and is used only by the out-of-scope Kin/WC optimizers."""
+        self._check_q(q)
+        squeeze = q.ndim == 1
+        q2 = q.unsqueeze(0) if squeeze else q
+        pos, quat = _FK.apply(q2, self._descriptor(link_names, offsets))
+        if squeeze:
+            return pos[0], quat[0]
+        return pos, quat
+
+    def _check_q(self, q):
         if q.device.type != self._device.type:
             raise AssertionError(f"Input argument of different device as module: {q.device}")
         if q.ndim not in (1, 2):
@@ -78,9 +89,34 @@ class DifferentiableRobotModel(torch.nn.Module):
             raise AssertionError(f"q must have {self._n_dofs} joints")
         if not q.is_cuda:
             raise RuntimeError("compliancedex_amd FK runs on the GPU only")
-        squeeze = q.ndim == 1
-        q2 = q.unsqueeze(0) if squeeze else q
-        pos, quat = _FK.apply(q2, self._descriptor(link_names, offsets))
-        if squeeze:
-            return pos[0], quat[0]
-        return pos, quat
+
+    def compute_fingertip_jacobians(self, q: torch.Tensor, link_names: list, offsets=None):
+        """→ (lin [B, T, 3, D], ang [B, T, 3, D]) float32: the geometric Jacobians of the links' positions (with
+        ``offsets``: of the offset points) and the joint axes, columns of joints off a link's path 0.  ``q`` is
+        rounded to float32 like the FK's.  The true derivative of ``compute_forward_kinematics``'s positions — its
+        autograd gradient differs where an offset is set (the reference's detached quaternion scale).  No autograd
+        through it."""
+        self._check_q(q)
+        lib = N.load()
+        qf = q.detach().to(torch.float32)
+        qf = (qf.unsqueeze(0) if qf.ndim == 1 else qf).contiguous()
+        B, T, D = qf.shape[0], len(link_names), self._n_dofs
+        lin = torch.empty(B, T, 3, D, dtype=torch.float32, device=q.device)
+        ang = torch.empty(B, T, 3, D, dtype=torch.float32, device=q.device)
+        N.check(lib.cdx_fk_jacobian(self._descriptor(link_names, offsets), N.ptr(qf), B, N.ptr(lin), N.ptr(ang),
+                                    N.stream_ptr(q.device)), "cdx_fk_jacobian")
+        return lin, ang
+
+    def compute_endeffector_jacobian(self, q: torch.Tensor, link_name: str, offset=None):
+        """→ (lin_jac [B, 3, n_dofs], ang_jac [B, 3, n_dofs]) float32 (robot_model.py:643-683; ``offset``, a point in
+        the link's frame, is the one addition)."""
+        lin, ang = self.compute_fingertip_jacobians(q, [link_name], None if offset is None else [offset])
+        return lin[:, 0], ang[:, 0]
+
+    def inverse_kinematics(self, target, link_names, offsets=None, q0=None, palm_pose=None, palm_offset=None,
+                           weights=None, ref_q=None, rho=0.0, max_iters=50, tol=1e-5, **lm):
+        """Joint angles whose fingertips reach ``target`` [E, T, 3] → IKResult(q, err, iters, status); see
+        ik.solve_ik."""
+        from .ik import solve_ik
+        return solve_ik(self, target, link_names, offsets, q0, palm_pose, palm_offset, weights, ref_q, rho, max_iters,
+                        tol, **lm)

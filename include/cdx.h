@@ -321,6 +321,45 @@ int cdx_fk_forward(const cdx_chain* chain, const float* q, int64_t B, float* pos
 int cdx_fk_backward(const cdx_chain* chain, const float* q, int64_t B, const float* grad_pos,
                     float* grad_q, cdx_stream_t stream);
 
+/* Geometric fingertip Jacobians (compute_endeffector_jacobian, robot_model.py:643-683; the rule is csrc/cdx_ik.h):
+ * q [B*n_dofs] f32 → lin [B*n_tips*3*n_dofs] f32, the derivative of cdx_fk_forward's pos (tip offsets included) with
+ * respect to q, and ang [B*n_tips*3*n_dofs] f32 (nullable), the joint axes; columns of joints off a tip's path are 0.
+ * This is the true derivative, not cdx_fk_backward's (which keeps the reference autograd's detached quaternion scale).
+ * Return codes of this entry and of cdx_ik_solve: a null required pointer → CDX_ECHAIN (−3), as a null chain gives
+ * everywhere; n_tips / n_dofs / n_bodies outside the descriptor's capacity, B < 0 → CDX_EINVAL; B = 0 is a no-op. */
+int cdx_fk_jacobian(const cdx_chain* chain, const float* q, int64_t B, float* lin, float* ang, cdx_stream_t stream);
+
+/* Batched inverse kinematics: joint angles whose fingertips reach `target`, E independent rows, the WHOLE solve in one
+ * launch (what the reference leaves to PyBullet's calculateInverseKinematics, verify_pregrasp.py:50-53).  The rule is
+ * csrc/cdx_ik.h: Levenberg–Marquardt on ½‖w·(target − tip)‖² + ½·rho·‖q − ref_q‖² with the joints projected onto
+ * [lower, upper], float32 FK (the fingertips are cdx_fk_forward's, bit for bit) and float64 algebra.
+ *   q0 [E*D] of q_dtype (CDX_DTYPE_F32 / CDX_DTYPE_F64; a double is rounded to float32 like the FK's input);
+ *   target [E*T*3] f64;  palm [E*6] f64 (nullable: identity) = position + XYZ Euler angles, held fixed;
+ *   palm_offset: 3 HOST doubles added to every fingertip (nullable: 0);  w [E*T] f64 ≥ 0 (nullable: 1), 0 drops a tip.
+ * Outputs: q [E*D] of q_dtype (float32 values), err [E*T] f64 the unweighted fingertip distances at q, iters [E],
+ *   status [E]: 0 = largest weighted fingertip error ≤ tol (tested before each iteration), 1 = max_iters used,
+ *   2 = a non-finite input in this row (q = q0 as given, err = NaN, iters = 0).
+ * No workspace is needed (per-row state lives in LDS): cdx_ik_workspace returns 0 and `workspace` may be NULL.
+ * CDX_EINVAL besides the above: E < 0, an unknown q_dtype, max_iters < 0, tol / mu0 / mu_min / mu_max / nu not finite
+ * and positive, rho negative or not finite, a non-finite ref_q, lower > upper or a NaN bound (±inf: unbounded). */
+typedef struct {
+  double lower[CDX_MAX_DOFS];
+  double upper[CDX_MAX_DOFS];
+  double ref_q[CDX_MAX_DOFS]; /* rest pose of the rho term */
+  double rho;                 /* rest-pose weight, ≥ 0 */
+  double tol;                 /* metres */
+  double mu0, mu_min, mu_max, nu;
+  int32_t max_iters;
+  int32_t _pad;
+} cdx_ik_params;
+size_t cdx_ik_workspace(int64_t E, int32_t n_tips, int32_t n_dofs);
+int cdx_ik_solve(const cdx_chain* chain, const cdx_ik_params* params, int64_t E, const void* q0, int32_t q_dtype,
+                 const double* target, const double* palm, const double* palm_offset, const double* w,
+                 void* workspace, void* q, double* err, int32_t* iters, int32_t* status, cdx_stream_t stream);
+/* Rows per workgroup of cdx_ik_solve for a chain of these sizes (for tests of its seams), and sizeof(cdx_ik_params). */
+int32_t cdx_ik_rows_per_block(int32_t n_tips, int32_t n_dofs);
+size_t cdx_ik_abi_size(void);
+
 /* ------------------------------------------------------ prob-mode closure -------
  * Replaces ProbabilisticGraspOptimizer.closure (optimize_pregrasp.py:741-769) —
  * forward AND backward for E candidates — plus its callees compute_loss (:713-739),

@@ -1,0 +1,195 @@
+"""Batched inverse kinematics (cdx_ik_solve) timed on the GPU: E = 4096, 16 384 and 65 536 candidates of the Allegro hand
+(D = 16) and of iiwa7_allegro (D = 23, the fingertip links and offsets of the FK fixture's case), targets FK(q*) with q*
+in the inner 80 % of every joint range, starts q* ± 0.3 rad (± 0.2 rad for the arm) clamped to the limits.
+
+Per shape: the one-launch solve (the time of ``solve_ik``, which allocates its four outputs); a torch statement of the
+same rule on the device — fingertips from ``compute_forward_kinematics``, the Jacobian from
+``compute_fingertip_jacobians``, batched ``torch.linalg.solve_ex`` for the 3T × 3T systems, row masks for the per-row stop and one
+``any()`` per iteration to end the loop —; and the host build of the rule on one core (cdxh_ik_solve, wall clock) up
+to --host-rows.  Besides the times the record keeps the share of rows each path converged, the iteration counts, and how
+far the torch statement's joint angles are from the kernel's.
+
+Device times are HIP events around one call after a warm-up call of every path, the paths alternating within each
+repeat; the median of --reps and the spread (max − min)/median are kept.
+
+Without --robot the tool is the driver: every shape runs in a child process of its own under ``timeout``, one after the
+other, and the first that fails, faults or runs out of time ends the run.  One JSON line per shape is printed and
+appended to the record (default profiles/ik.jsonl).  Needs a GPU: there is no fallback.
+
+  python tools/ik.py [--reps 7] [--rows 4096,16384,65536] [--robots allegro,iiwa7_allegro] [--out PATH]
+"""
+import argparse
+import ctypes as C
+import json
+import os
+import subprocess
+import sys
+import time
+
+REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, REPO)
+
+from tools.fps import event_ms, stats  # noqa: E402
+
+IIWA7_LINKS = ["link_3.0_tip", "link_7.0_tip", "link_11.0_tip", "link_15.0_tip"]
+IIWA7_OFFSETS = [[0.0, -0.04, 0.015], [0.0, -0.04, 0.015], [0.0, -0.04, 0.015], [0.0, -0.05, -0.015]]
+
+
+def inputs(rm, links, offsets, E, spread, seed=0):
+    """(q0, target) on the device: q* in the inner 80 % of the joint box, q0 = q* ± spread clamped."""
+    import torch
+    from compliancedex_amd.ik import joint_box
+    lower, upper = joint_box(rm.get_joint_limits())
+    lo, hi = torch.tensor(lower, dtype=torch.float64), torch.tensor(upper, dtype=torch.float64)
+    g = torch.Generator().manual_seed(seed)
+    mid, half = 0.5 * (lo + hi), 0.5 * (hi - lo)
+    qs = mid + 0.8 * half * (2.0 * torch.rand(E, len(lower), generator=g, dtype=torch.float64) - 1.0)
+    q0 = torch.minimum(torch.maximum(qs + spread * (2.0 * torch.rand(qs.shape, generator=g, dtype=torch.float64) - 1.0),
+                                     lo), hi)
+    target = rm.compute_forward_kinematics(qs.cuda().float(), links, offsets=offsets)[0].double().view(E, len(links), 3)
+    return q0.cuda(), target, lo.cuda(), hi.cuda()
+
+
+def torch_ik(rm, links, offsets, q0, target, lo, hi, max_iters=50, tol=1e-5, mu0=1e-3, mu_min=1e-9, mu_max=1e6, nu=4.0):
+    """The rule of csrc/cdx_ik.h (ρ = 0, no palm, unit weights) with torch operators on the device."""
+    import torch
+    E, D = q0.shape
+    T = len(links)
+    lo32, hi32 = lo.float(), hi.float()
+
+    def residual(q32):
+        tips = rm.compute_forward_kinematics(q32, links, offsets=offsets)[0].double().view(E, T, 3)
+        return (target - tips).reshape(E, 3 * T)
+
+    q = torch.minimum(torch.maximum(q0.float(), lo32), hi32)
+    r = residual(q)
+    cost = 0.5 * (r * r).sum(1)
+    mu = torch.full((E,), mu0, dtype=torch.float64, device=q0.device)
+    iters = torch.zeros(E, dtype=torch.int32, device=q0.device)
+    eye = torch.eye(3 * T, dtype=torch.float64, device=q0.device)
+    for _ in range(max_iters):
+        act = r.view(E, T, 3).norm(dim=2).amax(1) > tol
+        if not bool(act.any()):
+            break
+        iters += act
+        J = rm.compute_fingertip_jacobians(q, links, offsets)[0].double().view(E, 3 * T, D)
+        g = torch.bmm(J.transpose(1, 2), r.unsqueeze(2)).squeeze(2)
+        qd = q.double()
+        free = ~(((qd <= lo) & (g < 0)) | ((qd >= hi) & (g > 0)))
+        J = J * free.unsqueeze(1)
+        g = g * free
+        A = torch.bmm(J, J.transpose(1, 2)) + mu.view(E, 1, 1) * eye
+        # (solve_ex, not cholesky_ex: with the Cholesky pair no row converged at E = 65 536 and fewer did as E grew,
+        # though both are right on well-conditioned batches of that size; LU with pivoting has no pivot to fail on)
+        y, info = torch.linalg.solve_ex(A, torch.bmm(J, g.unsqueeze(2)))
+        delta = (g - torch.bmm(J.transpose(1, 2), y).squeeze(2)) / mu.view(E, 1)
+        qn = torch.minimum(torch.maximum(qd + delta, lo), hi).float()
+        rn = residual(qn)
+        cn = 0.5 * (rn * rn).sum(1)
+        ok = act & (info == 0) & (cn < cost)
+        q = torch.where(ok.unsqueeze(1), qn, q)
+        r = torch.where(ok.unsqueeze(1), rn, r)
+        cost = torch.where(ok, cn, cost)
+        mu = torch.where(act, torch.where(ok, (mu / nu).clamp(min=mu_min), (mu * nu).clamp(max=mu_max)), mu)
+    return q, r.view(E, T, 3).norm(dim=2), iters
+
+
+def host_seconds(rm, links, offsets, q0, target):
+    """Seconds of cdxh_ik_solve on one core, and its status / iteration arrays."""
+    import numpy as np
+    from compliancedex_amd import _native as N
+    from compliancedex_amd.ik import ik_params, joint_box
+    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
+    if not os.path.exists(path):
+        from compliancedex_amd.build import build_host
+        build_host()
+    lib = C.CDLL(path)
+    lib.cdxh_ik_solve.restype = C.c_int
+    lib.cdxh_ik_solve.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxIkParams), C.c_int64, C.c_void_p, C.c_int32] + \
+        [C.c_void_p] * 8
+    params = ik_params(*joint_box(rm.get_joint_limits()))
+    desc = rm._descriptor(links, offsets)
+    q0, target = np.ascontiguousarray(q0.cpu().numpy()), np.ascontiguousarray(target.cpu().numpy())
+    E, T = q0.shape[0], len(links)
+    q, err = np.empty_like(q0), np.empty((E, T))
+    iters, status = np.empty(E, np.int32), np.empty(E, np.int32)
+    t = time.perf_counter()
+    rc = lib.cdxh_ik_solve(desc, C.byref(params), E, q0.ctypes.data, N.DTYPE_F64, target.ctypes.data, None, None, None,
+                           q.ctypes.data, err.ctypes.data, iters.ctypes.data, status.ctypes.data)
+    dt = time.perf_counter() - t
+    assert rc == 0
+    return dt, status, iters
+
+
+def run_shape(robot, E, args):
+    import torch
+    from compliancedex_amd import DifferentiableRobotModel, solve_ik
+    rm = DifferentiableRobotModel(robot, device="cuda")
+    if robot == "iiwa7_allegro":
+        links, offsets, spread = IIWA7_LINKS, IIWA7_OFFSETS, 0.2
+    else:
+        links, offsets, spread = rm.chain.config["ee_link_name"], rm.chain.config["ee_link_offset"], 0.3
+    q0, target, lo, hi = inputs(rm, links, offsets, E, spread)
+    paths = {"kernel": lambda: solve_ik(rm, target, links, offsets, q0=q0),
+             "torch": lambda: torch_ik(rm, links, offsets, q0, target, lo, hi)}
+    for f in paths.values():  # warm-up: code objects, allocator blocks
+        f()
+    torch.cuda.synchronize()
+    ms = {n: [] for n in paths}
+    for _ in range(args.reps):
+        for n, f in paths.items():
+            ms[n].append(event_ms(f)[0])
+    rec = {"robot": robot, "E": E, "D": rm._n_dofs, "T": len(links), **{n: stats(v) for n, v in ms.items()}}
+    res = paths["kernel"]()
+    tq, terr, titers = paths["torch"]()
+    rec["kernel_converged"] = round(float((res.status == 0).double().mean()), 5)
+    rec["kernel_iters_median_max"] = [int(res.iters.median()), int(res.iters.max())]
+    rec["torch_converged"] = round(float((terr.amax(1) <= 1e-5).double().mean()), 5)
+    rec["torch_iters_median_max"] = [int(titers.median()), int(titers.max())]
+    rec["torch_q_max_abs_diff"] = float((tq.double() - res.q).abs().max())
+    rec["torch_over_kernel"] = round(rec["torch"]["median_ms"] / rec["kernel"]["median_ms"], 1)
+    if E <= args.host_rows:
+        sec, hstatus, hiters = host_seconds(rm, links, offsets, q0, target)
+        rec["host_one_core_ms"] = round(sec * 1e3, 2)
+        rec["host_converged"] = round(float((hstatus == 0).mean()), 5)
+        rec["host_over_kernel"] = round(sec * 1e3 / rec["kernel"]["median_ms"], 1)
+    rec["device"] = torch.cuda.get_device_name(0)
+    return rec
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=7)
+    ap.add_argument("--rows", default="4096,16384,65536")
+    ap.add_argument("--robots", default="allegro,iiwa7_allegro")
+    ap.add_argument("--robot", default=None, help="child mode: one shape in this process (with --rows one size)")
+    ap.add_argument("--host-rows", type=int, default=65536)
+    ap.add_argument("--step-seconds", type=int, default=150, help="time limit of each shape's process")
+    ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ik.jsonl"))
+    args = ap.parse_args()
+    rows = [int(v) for v in args.rows.split(",")]
+    if args.robot is None:
+        for robot in args.robots.split(","):
+            for E in rows:
+                cmd = ["timeout", "-k", "10", str(args.step_seconds), sys.executable, os.path.abspath(__file__), "--robot",
+                       robot, "--rows", str(E), "--reps", str(args.reps), "--host-rows", str(args.host_rows), "--out",
+                       args.out]
+                rc = subprocess.run(cmd).returncode
+                if rc != 0:
+                    raise SystemExit(f"{robot} E={E} ended with status {rc}: nothing more is started")
+        return
+    import torch
+    if not torch.cuda.is_available():
+        raise SystemExit("tools/ik.py needs a GPU: a CPU run gives no time")
+    from compliancedex_amd import _native
+    _native.load()
+    os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+    rec = run_shape(args.robot, rows[0], args)
+    line = json.dumps(rec)
+    print(line, flush=True)
+    with open(args.out, "a") as f:
+        f.write(line + "\n")
+
+
+if __name__ == "__main__":
+    main()
