@@ -13,6 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_DIR = os.path.join(_HERE, "lib")
 
 MAX_BODIES, MAX_TIPS, MAX_DOFS, MAX_LEVELS = 32, 8, 32, 4
+MAX_DEPTH = 16  # CDX_MAX_DEPTH: bodies on the longest root→tip path
 KERNELS = {"tps": 0, "rbf": 1, "joint": 2}
 NPAD_ALIGN = 256  # CDX_NPAD_ALIGN
 SCREEN_BANDS = 24  # CDX_SCREEN_BANDS

@@ -5,7 +5,7 @@ import ctypes
 
 import torch
 
-from ._native import MAX_BODIES, MAX_DOFS, MAX_TIPS, CdxChain
+from ._native import MAX_BODIES, MAX_DEPTH, MAX_DOFS, MAX_TIPS, CdxChain
 
 
 def _axis_rot_f32(axis, angle):
@@ -92,6 +92,12 @@ class Chain:
             if name not in self.index:
                 raise KeyError(name)
             c.tip_body[k] = self.index[name]
+            depth, b = 0, self.index[name]
+            while b > 0:
+                depth, b = depth + 1, self.bodies[b]["parent"]
+            if depth > MAX_DEPTH:
+                raise ValueError(f"tip {name!r} lies {depth} bodies below the root; the FK walks at most {MAX_DEPTH} "
+                                 f"(CDX_MAX_DEPTH)")
             if offsets is not None:
                 for i in range(3):
                     c.tip_offset[k][i] = float(torch.tensor(float(offsets[k][i]), dtype=torch.float32))

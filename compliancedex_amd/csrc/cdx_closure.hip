@@ -507,17 +507,7 @@ __global__ __launch_bounds__(COMBINE_BLOCK) void closure_combine_kernel(
   for (int i = 0; i < 3; ++i) { g_palm_pos[3 * e + i] = gpp[i]; g_palm_ori[3 * e + i] = go[i]; }
 }
 
-bool chain_ok(const cdx_chain* c) {
-  if (!(c && c->n_bodies > 0 && c->n_bodies <= CDX_MAX_BODIES && c->n_dofs >= 0 && c->n_dofs <= CDX_MAX_DOFS &&
-        c->n_tips > 0 && c->n_tips <= CDX_MAX_TIPS))
-    return false;
-  // parents precede children (the FK walks a tip's path in ascending body order), DOFs in range
-  for (int i = 1; i < c->n_bodies; ++i)
-    if (c->bodies[i].parent < 0 || c->bodies[i].parent >= i || c->bodies[i].dof >= c->n_dofs) return false;
-  for (int k = 0; k < c->n_tips; ++k)
-    if (c->tip_body[k] < 0 || c->tip_body[k] >= c->n_bodies) return false;
-  return true;
-}
+using cdx::chain_ok;  // (cdx_fk.h: sizes, parent order, tip range and depth)
 
 // fk_tip_bwd register bound for a chain: 8 levels (the hands) or CDX_MAX_DEPTH (arm + hand).
 bool shallow_chain(const cdx_chain& c) { return cdx::chain_max_depth(c) <= 8; }
@@ -977,6 +967,7 @@ int cdx_closure(const cdx_problem* p, int64_t E, const double* q, const double* 
                 void* workspace, double* total_loss, double* total_margin, double* pregrasp_tip, double* g_q,
                 double* g_comp, double* g_target, double* g_palm_pos, double* g_palm_ori, int32_t* flip,
                 cdx_stream_t stream) {
+  if (p && cdx::chain_code(&p->chain) == CDX_ECHAIN) return CDX_ECHAIN;  // a malformed or over-deep tree
   if (!problem_ok(p)) return CDX_EINVAL;
   if (E < 0) return CDX_EINVAL;
   if (E == 0) return CDX_OK;

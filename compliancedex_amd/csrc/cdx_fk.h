@@ -32,13 +32,13 @@ CDX_HD void axis_rot(int axis, float th, float* A, float* dA) {
   }
 }
 
-// Longest root→tip path a chain may have (iiwa7_allegro: 13).
-#define CDX_MAX_DEPTH 16
+// CDX_MAX_DEPTH (include/cdx.h): the longest root→tip path a chain may have (iiwa7_allegro: 13).
 
 // Bodies on the path from the root's child down to `body` as a bit mask (root = body 0 is the
-// identity pose).  Parents precede children (urdf.py enforces it, chain_ok re-checks it), so
+// identity pose).  Parents precede children (urdf.py enforces it, chain_code re-checks it), so
 // ascending bit order is root→tip order: the path is walked without a per-thread array, which
-// on the GPU would live in scratch memory.
+// on the GPU would live in scratch memory.  The walk stops after CDX_MAX_DEPTH levels: every entry
+// refuses a chain with a deeper tip (chain_code) before any code comes here.
 CDX_HD uint32_t chain_path_mask(const cdx_chain& c, int body) {
   uint32_t m = 0;
   for (int n = 0; body > 0 && n < CDX_MAX_DEPTH; ++n) {
@@ -403,6 +403,28 @@ CDX_HD int chain_max_depth(const cdx_chain& c) {
   }
   return d;
 }
+
+// The host-side chain check of every entry that walks a chain: null → CDX_ECHAIN; sizes over the descriptor's →
+// CDX_EINVAL; a malformed tree (a parent that does not precede its child, a DOF or a tip body out of range) or a tip
+// more than CDX_MAX_DEPTH levels below the root → CDX_ECHAIN.  The depth is counted by walking the parents, not through
+// chain_path_mask, which stops at the limit.
+CDX_HD int chain_code(const cdx_chain* c) {
+  if (!c) return CDX_ECHAIN;
+  if (c->n_bodies <= 0 || c->n_bodies > CDX_MAX_BODIES || c->n_dofs < 0 || c->n_dofs > CDX_MAX_DOFS || c->n_tips <= 0 ||
+      c->n_tips > CDX_MAX_TIPS)
+    return CDX_EINVAL;
+  for (int i = 1; i < c->n_bodies; ++i)
+    if (c->bodies[i].parent < 0 || c->bodies[i].parent >= i || c->bodies[i].dof >= c->n_dofs) return CDX_ECHAIN;
+  for (int k = 0; k < c->n_tips; ++k) {
+    if (c->tip_body[k] < 0 || c->tip_body[k] >= c->n_bodies) return CDX_ECHAIN;
+    int depth = 0;
+    for (int b = c->tip_body[k]; b > 0; b = c->bodies[b].parent) ++depth;  // (parent < body: it ends)
+    if (depth > CDX_MAX_DEPTH) return CDX_ECHAIN;
+  }
+  return CDX_OK;
+}
+// The entries whose every chain failure is CDX_ECHAIN (FK, closure, collision).
+CDX_HD bool chain_ok(const cdx_chain* c) { return chain_code(c) == CDX_OK; }
 
 // Array accumulator for fk_tip_bwd: g[dof] += v.
 struct GqAdd {

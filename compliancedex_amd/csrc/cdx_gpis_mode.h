@@ -269,6 +269,10 @@ CDX_HD int gpis_mode_check(const cdx_chain* chain, const cdx_gpis_mode_params* p
     return CDX_EINVAL;
   return CDX_OK;
 }
+// After gpis_mode_check: the chain's tree (parent order, DOF / tip range, depth) in mode 1 → CDX_ECHAIN.
+CDX_HD int gpis_mode_check_chain(const cdx_chain* chain, const cdx_gpis_mode_params* p) {
+  return p->mode == 1 && chain_code(chain) ? CDX_ECHAIN : CDX_OK;
+}
 CDX_HD int gpis_mode_check_cost(const cdx_gpis_mode_params* p, const cdx_gpis_mode_buffers* b) {
   if (!b || !b->pose || !b->target || !b->comp || !b->mean || !b->gmean || !b->normal || !b->std || !b->gstd ||
       !b->tmean || !b->tgmean || !b->loss || !b->g_pose || !b->g_target || !b->g_comp || !b->margin[0] || !b->margin[1] ||

@@ -93,6 +93,7 @@ extern "C" int cdx_gpis_mode_cost(const cdx_chain* chain, const cdx_gpis_mode_pa
                                   int64_t E, int32_t n_tips, const double* noise, uint64_t seed, int32_t iteration,
                                   cdx_stream_t stream) {
   if (cdx::gpis_mode_check(chain, p, E, n_tips) || iteration < 0) return CDX_EINVAL;
+  if (cdx::gpis_mode_check_chain(chain, p)) return CDX_ECHAIN;
   if (E == 0) return CDX_OK;
   if (cdx::gpis_mode_check_cost(p, buf)) return CDX_EINVAL;
   return launch<PHASE_COST>(chain, p, nullptr, buf, E, n_tips, noise, seed, iteration, 0, stream);
@@ -102,6 +103,7 @@ extern "C" int cdx_gpis_mode_step(const cdx_chain* chain, const cdx_gpis_mode_pa
                                   const cdx_gpis_mode_buffers* buf, int64_t E, int32_t n_tips, int32_t iteration,
                                   int32_t finalize, cdx_stream_t stream) {
   if (cdx::gpis_mode_check(chain, p, E, n_tips) || !opt) return CDX_EINVAL;
+  if (cdx::gpis_mode_check_chain(chain, p)) return CDX_ECHAIN;
   if (E == 0) return CDX_OK;
   if (cdx::gpis_mode_check_step(opt, buf, iteration, finalize)) return CDX_EINVAL;
   return launch<PHASE_STEP>(chain, p, opt, buf, E, n_tips, nullptr, 0, iteration, finalize, stream);
@@ -112,6 +114,7 @@ extern "C" int cdx_gpis_mode_iteration(const cdx_chain* chain, const cdx_gpis_mo
                                        int32_t n_tips, const double* noise, uint64_t seed, int32_t iteration,
                                        cdx_stream_t stream) {
   if (cdx::gpis_mode_check(chain, p, E, n_tips) || !opt) return CDX_EINVAL;
+  if (cdx::gpis_mode_check_chain(chain, p)) return CDX_ECHAIN;
   if (E == 0) return CDX_OK;
   if (cdx::gpis_mode_check_cost(p, buf) || cdx::gpis_mode_check_step(opt, buf, iteration, 0)) return CDX_EINVAL;
   if (n_tips != 4) {  // the two launches

@@ -168,18 +168,8 @@ CDX_HD int ik_prepare(const cdx_ik_params* in, int D, cdx_ik_params* out) {
 }
 
 // The chain checks of the two entries: null → CDX_ECHAIN, sizes over the descriptor's → CDX_EINVAL, a malformed
-// tree → CDX_ECHAIN.
-CDX_HD int ik_chain_code(const cdx_chain* c) {
-  if (!c) return CDX_ECHAIN;
-  if (c->n_bodies <= 0 || c->n_bodies > CDX_MAX_BODIES || c->n_dofs < 0 || c->n_dofs > CDX_MAX_DOFS || c->n_tips <= 0 ||
-      c->n_tips > CDX_MAX_TIPS)
-    return CDX_EINVAL;
-  for (int i = 1; i < c->n_bodies; ++i)
-    if (c->bodies[i].parent < 0 || c->bodies[i].parent >= i || c->bodies[i].dof >= c->n_dofs) return CDX_ECHAIN;
-  for (int k = 0; k < c->n_tips; ++k)
-    if (c->tip_body[k] < 0 || c->tip_body[k] >= c->n_bodies) return CDX_ECHAIN;
-  return CDX_OK;
-}
+// tree or an over-deep tip → CDX_ECHAIN (chain_code, cdx_fk.h).
+CDX_HD int ik_chain_code(const cdx_chain* c) { return chain_code(c); }
 
 // d = target − tip(q) into dv (stride s), cost(q) and emax.
 template <class Q>

@@ -671,6 +671,7 @@ extern "C" int cdx_kin_cost(const cdx_chain* chain, const cdx_kin_params* p, int
   if (chain && (chain->n_tips != p->fe.n_tips || chain->n_dofs < 0 || chain->n_dofs > CDX_MAX_DOFS ||
                 chain->n_bodies < 1 || chain->n_bodies > CDX_MAX_BODIES))
     return CDX_EINVAL;
+  if (chain && cdx::chain_code(chain)) return CDX_ECHAIN;  // parent order, DOF / tip range, depth
   if (E < 0) return CDX_EINVAL;
   if (E == 0) return CDX_OK;
   if (!tip || !target || !comp || !sign1 || !n1 || !sqdist || !sign2 || !n2 || !clst || !tsqdist || !tsign || !tclst ||
@@ -829,6 +830,7 @@ extern "C" int cdx_kin_step(const cdx_chain* chain, const cdx_kin_opt* cfg, cons
   if (kin && (!chain || chain->n_tips != n_tips || chain->n_dofs < 1 || chain->n_dofs > CDX_MAX_DOFS ||
               chain->n_bodies < 1 || chain->n_bodies > CDX_MAX_BODIES))
     return CDX_EINVAL;
+  if (kin && cdx::chain_code(chain)) return CDX_ECHAIN;
   if (E == 0) return CDX_OK;
   const cdx_kin_opt_buffers& b = *buf;
   if (!b.margin[0] || !b.margin[1] || !b.normal[0] || !b.normal[1] || !b.opt_margin || !b.opt_normal || !b.any)
@@ -876,6 +878,7 @@ extern "C" int cdx_kin_iteration(const cdx_chain* chain, const cdx_kin_params* p
   if (E < 0 || (kin && (chain->n_tips != 4 || chain->n_dofs < 1 || chain->n_dofs > CDX_MAX_DOFS ||
                         chain->n_bodies < 1 || chain->n_bodies > CDX_MAX_BODIES)))
     return CDX_EINVAL;
+  if (kin && cdx::chain_code(chain)) return CDX_ECHAIN;
   if (E == 0) return CDX_OK;
   if (!b.pose || !b.target || !b.comp || !g_pose || !g_target || !g_comp || (kin && (!b.m_pose || !b.m_target)) ||
       !b.v_pose ||

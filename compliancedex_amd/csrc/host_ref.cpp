@@ -331,18 +331,23 @@ int64_t depth_unproject(const D* depth, int32_t W, int32_t H, int32_t stride, co
 
 extern "C" {
 
-void cdxh_fk_forward(const cdx_chain* c, const float* q, int64_t B, float* pos, float* quat) {
+// (the chain checks of the device entries: a malformed or over-deep chain → CDX_ECHAIN, nothing written)
+int cdxh_fk_forward(const cdx_chain* c, const float* q, int64_t B, float* pos, float* quat) {
+  if (!cdx::chain_ok(c)) return CDX_ECHAIN;
   for (int64_t b = 0; b < B; ++b)
     for (int k = 0; k < c->n_tips; ++k)
       cdx::fk_tip(*c, k, q + b * c->n_dofs, pos + (b * c->n_tips + k) * 3, quat ? quat + (b * c->n_tips + k) * 4 : nullptr);
+  return CDX_OK;
 }
 
-void cdxh_fk_backward(const cdx_chain* c, const float* q, int64_t B, const float* gpos, float* gq) {
+int cdxh_fk_backward(const cdx_chain* c, const float* q, int64_t B, const float* gpos, float* gq) {
+  if (!cdx::chain_ok(c)) return CDX_ECHAIN;
   for (int64_t b = 0; b < B; ++b) {
     float* g = gq + b * c->n_dofs;
     for (int i = 0; i < c->n_dofs; ++i) g[i] = 0.f;
     for (int k = 0; k < c->n_tips; ++k) cdx::fk_tip_bwd(*c, k, q + b * c->n_dofs, gpos + (b * c->n_tips + k) * 3, cdx::GqAdd{g});
   }
+  return CDX_OK;
 }
 
 // Geometric fingertip Jacobians and the batched IK solve (cdx_ik.h), with the device entries' argument checks.
@@ -394,8 +399,9 @@ int cdxh_ik_solve(const cdx_chain* c, const cdx_ik_params* params, int64_t E, co
 
 int64_t cdxh_n_queries(const cdx_problem* P, int64_t E) { return cdx::n_queries(*P, E); }
 
-void cdxh_closure_queries(const cdx_problem* P, int64_t E, const double* q, const double* target, const double* palm_pos,
-                          const double* palm_ori, double* X) {
+int cdxh_closure_queries(const cdx_problem* P, int64_t E, const double* q, const double* target, const double* palm_pos,
+                         const double* palm_ori, double* X) {
+  if (!P || !cdx::chain_ok(&P->chain)) return CDX_ECHAIN;
   const int T = P->chain.n_tips, D = P->chain.n_dofs, Lq = P->n_query_levels;
   for (int64_t e = 0; e < E; ++e) {
     double tip[CDX_MAX_TIPS][3], Rp[9];
@@ -419,13 +425,15 @@ void cdxh_closure_queries(const cdx_problem* P, int64_t E, const double* q, cons
     if (P->optimize_palm)
       for (int i = 0; i < 3; ++i) X[3 * cdx::q_palm(Lq, e, E, T) + i] = palm_pos[3 * e + i];
   }
+  return CDX_OK;
 }
 
-void cdxh_closure_cost(const cdx_problem* P, int64_t E, const double* q, const double* comp, const double* target,
-                       const double* palm_pos, const double* palm_ori, const double* noise, const double* mean,
-                       const double* gmean, const double* normal, const double* std_, const double* gstd,
-                       double* total_loss, double* total_margin, double* g_q, double* g_comp, double* g_target,
-                       double* g_palm_pos, double* g_palm_ori, int32_t* flip) {
+int cdxh_closure_cost(const cdx_problem* P, int64_t E, const double* q, const double* comp, const double* target,
+                      const double* palm_pos, const double* palm_ori, const double* noise, const double* mean,
+                      const double* gmean, const double* normal, const double* std_, const double* gstd,
+                      double* total_loss, double* total_margin, double* g_q, double* g_comp, double* g_target,
+                      double* g_palm_pos, double* g_palm_ori, int32_t* flip) {
+  if (!P || !cdx::chain_ok(&P->chain)) return CDX_ECHAIN;
   const int T = P->chain.n_tips, D = P->chain.n_dofs;
   HostGpis g{mean, gmean, normal, std_, gstd, E, 0, T, P->n_query_levels};
   for (int64_t e = 0; e < E; ++e) {
@@ -450,13 +458,16 @@ void cdxh_closure_cost(const cdx_problem* P, int64_t E, const double* q, const d
     for (int i = 0; i < 3; ++i) { g_palm_pos[3 * e + i] = out.g_palm_pos[i]; g_palm_ori[3 * e + i] = out.g_palm_ori[i]; }
     for (int k = 0; k < P->n_levels; ++k) flip[k * E + e] = out.flip[k];
   }
+  return CDX_OK;
 }
 
-void cdxh_collision(const cdx_collision* C, int64_t E, const double* q, const double* pp, const double* po,
-                    double* cost, double* g_q, double* g_pp, double* g_po) {
+int cdxh_collision(const cdx_collision* C, int64_t E, const double* q, const double* pp, const double* po,
+                   double* cost, double* g_q, double* g_pp, double* g_po) {
+  if (!C || !cdx::chain_ok(&C->chain)) return CDX_ECHAIN;
   const int D = C->chain.n_dofs;
   for (int64_t e = 0; e < E; ++e)
     cdx::collision_candidate(*C, q + e * D, pp + 3 * e, po + 3 * e, cost[e], g_q + e * D, g_pp + 3 * e, g_po + 3 * e);
+  return CDX_OK;
 }
 
 void cdxh_force_eq(const cdx_force_eq* p, int64_t B, const double* tip, const double* target, const double* comp,
@@ -493,6 +504,7 @@ void cdxh_force_eq(const cdx_force_eq* p, int64_t B, const double* tip, const do
 int cdxh_gpis_mode_cost(const cdx_chain* chain, const cdx_gpis_mode_params* p, const cdx_gpis_mode_buffers* buf,
                         int64_t E, int32_t n_tips, const double* noise, uint64_t seed, int32_t iteration) {
   if (cdx::gpis_mode_check(chain, p, E, n_tips) || iteration < 0) return CDX_EINVAL;
+  if (cdx::gpis_mode_check_chain(chain, p)) return CDX_ECHAIN;
   if (E == 0) return CDX_OK;
   if (cdx::gpis_mode_check_cost(p, buf)) return CDX_EINVAL;
   const cdx_gpis_mode_buffers& b = *buf;
@@ -522,6 +534,7 @@ int cdxh_gpis_mode_step(const cdx_chain* chain, const cdx_gpis_mode_params* p, c
                         const cdx_gpis_mode_buffers* buf, int64_t E, int32_t n_tips, int32_t iteration,
                         int32_t finalize) {
   if (cdx::gpis_mode_check(chain, p, E, n_tips) || !opt) return CDX_EINVAL;
+  if (cdx::gpis_mode_check_chain(chain, p)) return CDX_ECHAIN;
   if (E == 0) return CDX_OK;
   if (cdx::gpis_mode_check_step(opt, buf, iteration, finalize)) return CDX_EINVAL;
   const cdx_gpis_mode_buffers& b = *buf;

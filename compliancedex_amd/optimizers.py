@@ -118,6 +118,35 @@ def _noise(tape, s):
     return None if tape is None else tape[s]
 
 
+def kin_fk_cache_view(fk_state, max_depth):
+    """The fused Kin loop's FK-walk cache (``last_loop.fk_state``, csrc/cdx_kin.hip) as host arrays, one row per lane
+    (lane 4·e + f holds fingertip f of candidate e; the last workgroup's lanes past 4·E are there too):
+    ``tag`` [L] uint32 — the iteration that wrote the lane's slots + 1; ``qcheck`` [L, 8] uint32 — the bits of the joint
+    angles the walk read (the lane's DOFs f + 4·u in slot u, 0 past the row); ``pose`` [L, 12] float32 — the walk's
+    final R and t.  ``max_depth``: the chain's deepest tip path (it picks the kernel's level bound, 8 or 16, and with
+    it the slots of the q-check and the tag).  Slot s of lane l of a workgroup lies at float (s / 4)·256 + 4·l + s % 4
+    of the workgroup's block of (12 + 6·16 + 8 + 4)·64 floats."""
+    maxd = 8 if max_depth <= 8 else N.MAX_DEPTH
+    slots = 12 + 6 * N.MAX_DEPTH + N.MAX_DOFS // 4 + 4
+    w = fk_state.detach().cpu().numpy().view(np.uint32).reshape(-1, slots // 4, 64, 4)
+    w = np.ascontiguousarray(w.transpose(0, 2, 1, 3)).reshape(-1, slots)  # [lane, slot]
+    qc = 12 + 6 * maxd
+    return dict(tag=w[:, qc + N.MAX_DOFS // 4], qcheck=w[:, qc:qc + N.MAX_DOFS // 4],
+                pose=np.ascontiguousarray(w[:, :12]).view(np.float32))
+
+
+def kin_fk_cache_qcheck(pose):
+    """What the cache's q-check slots hold after a walk on the joint rows ``pose`` [E, D] (float32): [4·E, 8] uint32,
+    lane 4·e + f's slot u the bits of pose[e, f + 4·u], 0 past the row."""
+    pose = np.ascontiguousarray(pose.detach().cpu().numpy(), np.float32)
+    E, D = pose.shape
+    want = np.zeros((E, 4, N.MAX_DOFS // 4), np.uint32)
+    for f in range(4):
+        cols = np.arange(f, D, 4)
+        want[:, f, :len(cols)] = pose[:, cols].view(np.uint32)
+    return want.reshape(4 * E, -1)
+
+
 class _FusedLoop:
     """Device state of a fused Kin / SDF loop: the two prepared meshes, cdx_kin_cost's outputs (margin / normal
     in two alternating slots), the optimiser moments, the best iterate and the cdx_kin_step buffers.  Per

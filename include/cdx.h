@@ -292,6 +292,7 @@ int cdx_cloud_normals(const void* X, int32_t dtype, int64_t P, const int64_t* id
 #define CDX_MAX_BODIES 32
 #define CDX_MAX_TIPS 8
 #define CDX_MAX_DOFS 32
+#define CDX_MAX_DEPTH 16 /* longest root→tip path: bodies from the root's child down to a tip's body */
 
 typedef struct {
   float F[9];        /* fixed rotation (Rz(yaw)·Ry(pitch))·Rx(roll), row-major */
@@ -312,6 +313,10 @@ typedef struct {
   float tip_offset[CDX_MAX_TIPS][3];
   cdx_body bodies[CDX_MAX_BODIES];
 } cdx_chain;
+/* A chain is valid when its sizes fit the capacities above, every body's parent precedes it (body 0 is the root),
+ * every dof is below n_dofs, every tip_body is a body, and no tip lies more than CDX_MAX_DEPTH levels below the root
+ * (the FK keeps one pose per level in registers).  Every entry that takes a chain checks this on the host before it
+ * launches: a malformed or over-deep chain returns CDX_ECHAIN and writes nothing (cdx_closure_workspace: 0 bytes). */
 
 /* q [B*n_dofs] f32 → pos [B*3*n_tips] f32, quat [B*4*n_tips] f32 (xyzw, nullable). */
 int cdx_fk_forward(const cdx_chain* chain, const float* q, int64_t B, float* pos, float* quat,

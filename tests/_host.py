@@ -32,7 +32,8 @@ def fk_forward(chain: CdxChain, q):
     B = q.shape[0]
     pos = np.zeros((B, chain.n_tips * 3), np.float32)
     quat = np.zeros((B, chain.n_tips * 4), np.float32)
-    host().cdxh_fk_forward(C.byref(chain), p(q), C.c_int64(B), p(pos), p(quat))
+    rc = host().cdxh_fk_forward(C.byref(chain), p(q), C.c_int64(B), p(pos), p(quat))
+    assert rc == 0, rc
     return pos, quat
 
 
@@ -40,7 +41,8 @@ def fk_backward(chain: CdxChain, q, gpos):
     q = np.ascontiguousarray(q, dtype=np.float32)
     gpos = np.ascontiguousarray(gpos, dtype=np.float32)
     gq = np.zeros_like(q)
-    host().cdxh_fk_backward(C.byref(chain), p(q), C.c_int64(q.shape[0]), p(gpos), p(gq))
+    rc = host().cdxh_fk_backward(C.byref(chain), p(q), C.c_int64(q.shape[0]), p(gpos), p(gq))
+    assert rc == 0, rc
     return gq
 
 
@@ -50,7 +52,8 @@ def closure_queries(prob: CdxProblem, q, target, palm):
     X = np.zeros((Mq, 3))
     q, target = np.ascontiguousarray(q, np.float64), np.ascontiguousarray(target, np.float64)
     pp, po = np.ascontiguousarray(palm[:, :3]), np.ascontiguousarray(palm[:, 3:])
-    host().cdxh_closure_queries(C.byref(prob), C.c_int64(E), p(q), p(target), p(pp), p(po), p(X))
+    rc = host().cdxh_closure_queries(C.byref(prob), C.c_int64(E), p(q), p(target), p(pp), p(po), p(X))
+    assert rc == 0, rc
     return X
 
 
@@ -65,10 +68,11 @@ def closure_cost(prob: CdxProblem, q, comp, target, palm, noise, gp):
                grad_comp=np.zeros((E, T)), grad_target=np.zeros((E, T, 3)), grad_palm_pos=np.zeros((E, 3)),
                grad_palm_ori=np.zeros((E, 3)), flip=np.zeros(K * E, np.int32))
     arrs = [np.ascontiguousarray(gp[k], np.float64) for k in ("mean", "gmean", "normal", "std", "gstd")]
-    host().cdxh_closure_cost(C.byref(prob), C.c_int64(E), p(q), p(comp), p(target), p(pp), p(po), p(noise),
+    rc = host().cdxh_closure_cost(C.byref(prob), C.c_int64(E), p(q), p(comp), p(target), p(pp), p(po), p(noise),
                              *[p(a) for a in arrs],
                              *[p(out[k]) for k in ("total_loss", "total_margin", "grad_q", "grad_comp", "grad_target",
                                                    "grad_palm_pos", "grad_palm_ori", "flip")])
+    assert rc == 0, rc
     return out
 
 
@@ -95,7 +99,8 @@ def collision(desc, q, palm):
     E, D = q.shape
     cost, g_q = np.zeros(E), np.zeros((E, D))
     g_pp, g_po = np.zeros((E, 3)), np.zeros((E, 3))
-    host().cdxh_collision(C.byref(desc), C.c_int64(E), p(q), p(pp), p(po), p(cost), p(g_q), p(g_pp), p(g_po))
+    rc = host().cdxh_collision(C.byref(desc), C.c_int64(E), p(q), p(pp), p(po), p(cost), p(g_q), p(g_pp), p(g_po))
+    assert rc == 0, rc
     return cost, g_q, np.concatenate([g_pp, g_po], 1)
 
 

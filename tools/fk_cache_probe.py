@@ -24,28 +24,12 @@ def main():
     kin.optimize(*args, 1, banana_mesh(), verbose=False, trace_rows=True)
     torch.cuda.synchronize()
     st = kin.last_loop
-    fs = st.fk_state.view(torch.float32).cpu().numpy()
-    pose = st.pose.cpu().numpy().reshape(E, -1)
-    D = pose.shape[1]
-    blk = 120 * 64  # FKS_BLOCK: the 116-slot image + the tag chunk
-
-    def at(slot, lane):  # 16-byte units in lane order (cdx_kin.hip fks_at)
-        return (slot >> 2) * 256 + 4 * lane + (slot & 3)
-    tags = [int(fs[b * blk + at(116, l)].view(np.uint32)) for b in range(4 * E // 64) for l in range(64)]
-    ok, bad = 0, 0
-    for lane_g in range(4 * E):
-        b, l = divmod(lane_g, 64)
-        e, f = divmod(lane_g, 4)
-        for u in range(8):
-            i = f + 4 * u
-            if i >= D:
-                continue
-            v = fs[b * blk + at(12 + 6 * 16 + u, l)]
-            if v.view(np.uint32) == pose[e, i].view(np.uint32):
-                ok += 1
-            else:
-                bad += 1
-    R0 = np.array([fs[at(i, 0)] for i in range(9)])
+    from compliancedex_amd.optimizers import kin_fk_cache_qcheck, kin_fk_cache_view
+    view = kin_fk_cache_view(st.fk_state, 13)  # iiwa7_allegro's deepest fingertip path: the 16-level layout
+    same = view["qcheck"][:4 * E] == kin_fk_cache_qcheck(st.pose.view(E, -1))
+    ok, bad = int(same.sum()), int((~same).sum())
+    tags = view["tag"][:4 * E].tolist()
+    R0 = view["pose"][0, :9]
     print(json.dumps({"qcheck_ok": ok, "qcheck_bad": bad, "tags": sorted(set(tags)), "iterations": 3,
                       "R_lane0": R0.tolist()}))
 
