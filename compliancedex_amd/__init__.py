@@ -8,8 +8,12 @@ Drop-in operators (same names / arguments as the reference):
                                angles for E candidates in one launch, parity with PyBullet's solver unpinned
   compute_sdf                  torchsdf/sdf.py
   ProbabilisticGraspOptimizer  optimize_pregrasp.py:614-839
-  KinGraspOptimizer / SDFGraspOptimizer / GPISGraspOptimizer / KinGPISGraspOptimizer
-                               optimize_pregrasp.py:121-511
+  KinGraspOptimizer / SDFGraspOptimizer / GPISGraspOptimizer / KinGPISGraspOptimizer / WCKinGPISGraspOptimizer
+                               optimize_pregrasp.py:121-612
+  min_wrench / MinWrenchResult / solve_minimum_wrench / minimum_wrench_reward / compute_margin
+                               math_utils.py:6-57 (cvxpy / cvxpylayers there): minimum-wrench contact forces of E
+                               candidates in one launch with a duality-gap certificate per row, parity with SCS
+                               unpinned
   force_eq_reward              optimize_pregrasp.py:73-118
   farthest_point_down_sample   open3d's PointCloud.farthest_point_down_sample (optimize_pregrasp.py:904)
   cast_rays / occluded         open3d's RaycastingScene.cast_rays (concatenate_pcd.py:41-49)
@@ -34,7 +38,7 @@ from .optimizer import (EE_OFFSETS, FINGERTIP_LB, FINGERTIP_UB, WRIST_OFFSET,  #
 from .anneal import PregraspAnnealer  # noqa: F401
 from .force_eq import force_eq_reward  # noqa: F401
 from .optimizers import (GPISGraspOptimizer, KinGPISGraspOptimizer, KinGraspOptimizer,  # noqa: F401
-                         SDFGraspOptimizer, TriangleMesh)
+                         SDFGraspOptimizer, TriangleMesh, WCKinGPISGraspOptimizer)
 from .mesh import EdgeRefiner, mesh_face_vertices, refine_vertices, to_triangle_mesh  # noqa: F401
 from .pointcloud import (KnnGrid, completion_arrays, estimate_normals, farthest_point_down_sample,  # noqa: F401
                          farthest_point_sample, knn, orient_normals_towards_camera_location, point_cloud_distance,
@@ -45,6 +49,8 @@ from .sampling import (SurfaceSampler, sample_points_poisson_disk, sample_points
                        surface_sampler)
 from .robot_model import DifferentiableRobotModel  # noqa: F401
 from .ik import IKResult, solve_ik  # noqa: F401
+from .wrench import (MinWrenchResult, compute_margin, min_wrench, minimum_wrench_reward,  # noqa: F401
+                     solve_minimum_wrench)
 from .torchsdf import PreparedMesh, compute_sdf, compute_sdf_with_faces, index_vertices_by_faces  # noqa: F401
 
 __version__ = "0.1.0"

@@ -56,6 +56,12 @@ class CdxIkParams(C.Structure):
                 ("mu_max", C.c_double), ("nu", C.c_double), ("max_iters", C.c_int32), ("_pad", C.c_int32)]
 
 
+class CdxWrenchParams(C.Structure):
+    _fields_ = [("n_tips", C.c_int32), ("max_iters", C.c_int32), ("check_every", C.c_int32), ("_pad", C.c_int32),
+                ("mu", C.c_double), ("min_force", C.c_double), ("reg", C.c_double), ("rho", C.c_double),
+                ("tol", C.c_double)]
+
+
 class CdxProblem(C.Structure):
     _fields_ = [("chain", CdxChain), ("gpis", CdxGpis), ("n_levels", C.c_int32), ("n_query_levels", C.c_int32),
                 ("level_query", C.c_int32 * MAX_LEVELS), ("coeff", (C.c_float * MAX_TIPS) * MAX_LEVELS),
@@ -208,6 +214,9 @@ _SIGS = {
     "cdx_ik_abi_size": (C.c_size_t, []),
     "cdx_ik_solve": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxIkParams), _I64, _P, C.c_int32, _P, _P,
                                C.POINTER(C.c_double), _P, _P, _P, _P, _P, _P, _P]),
+    "cdx_min_wrench": (C.c_int, [C.POINTER(CdxWrenchParams), _I64] + [_P] * 11),
+    "cdx_wrench_rows_per_block": (C.c_int32, [C.c_int32]),
+    "cdx_wrench_abi_size": (C.c_size_t, []),
     "cdx_force_eq_forward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
                                        _P]),
     "cdx_force_eq_backward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
@@ -312,6 +321,9 @@ def load():
         if lib.cdx_ik_abi_size() != C.sizeof(CdxIkParams):
             raise ImportError(f"ABI struct size mismatch (IK): library {lib.cdx_ik_abi_size()} vs binding "
                               f"{C.sizeof(CdxIkParams)}")
+        if lib.cdx_wrench_abi_size() != C.sizeof(CdxWrenchParams):
+            raise ImportError(f"ABI struct size mismatch (wrench): library {lib.cdx_wrench_abi_size()} vs binding "
+                              f"{C.sizeof(CdxWrenchParams)}")
         info = build_info()
         if not info["matches"] and "CDX_LIB" not in os.environ:
             import warnings

@@ -1,5 +1,6 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
-// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h / cdx_sample.h / cdx_knn.h.
+// cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h / cdx_sample.h / cdx_knn.h /
+// cdx_wrench.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
@@ -21,6 +22,7 @@
 #include "cdx_ray.h"
 #include "cdx_sample.h"
 #include "cdx_sdf.h"
+#include "cdx_wrench.h"
 
 namespace {
 
@@ -394,6 +396,24 @@ int cdxh_ik_solve(const cdx_chain* c, const cdx_ik_params* params, int64_t E, co
     }
     status[e] = st;
   }
+  return CDX_OK;
+}
+
+// The minimum-wrench solve (cdx_wrench.h) row by row, with the device entry's argument checks.
+int cdxh_min_wrench(const cdx_wrench_params* params, int64_t E, const double* tips, const double* normals,
+                    double* forces, double* wrench, double* margin, double* dual, double* gap, int32_t* iters,
+                    int32_t* status, double* grad_tips) {
+  const int rc = cdx::wr_params_code(params);
+  if (rc) return rc;
+  if (E < 0) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (!tips || !normals || !forces || !wrench || !margin || !dual || !gap || !iters || !status) return CDX_EINVAL;
+  const int T = params->n_tips;
+  std::vector<double> mem(cdx::wr_mem_doubles(T));
+  const cdx::WrMem m = cdx::wr_mem_at(mem.data(), T, 0, 1);
+  for (int64_t e = 0; e < E; ++e)
+    status[e] = cdx::mw_row(*params, tips + e * T * 3, normals + e * T * 3, m, forces + e * T * 3, wrench + e,
+                            margin + e * T, dual + e * 6, gap + e, iters + e, grad_tips ? grad_tips + e * T * 3 : nullptr);
   return CDX_OK;
 }
 

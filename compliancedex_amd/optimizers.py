@@ -4,16 +4,16 @@
   SDFGraspOptimizer      :229-320  fingertip space, TorchSDF mesh distance, RMSprop, box clamps
   GPISGraspOptimizer     :322-406  fingertip space, GPIS distance / variance, RMSprop
   KinGPISGraspOptimizer  :408-511  joint space, GPIS distance / log-variance, RMSprop
+  WCKinGPISGraspOptimizer :513-612 joint space, minimum-wrench contact forces (wrench.py), RMSprop
 
 Each loop runs on the same gfx950 kernels as the prob-mode closure — GPIS mean/normal/std
-(cdx_gpis_*), FK (cdx_fk_*), TorchSDF (cdx_sdf_*) and the Kabsch/force-equilibrium reward
-(cdx_force_eq_*) — with the per-candidate cost glue as device tensor ops and torch's own
-RMSprop / Adam, as in the reference.  Differences in *how*: the best-iterate bookkeeping
+(cdx_gpis_*), FK (cdx_fk_*), TorchSDF (cdx_sdf_*), the Kabsch/force-equilibrium reward
+(cdx_force_eq_*) and, for the WC optimiser, the minimum-wrench solve (cdx_min_wrench) — with
+the per-candidate cost glue as device tensor ops and torch's own RMSprop / Adam, as in the reference.  Differences in *how*: the best-iterate bookkeeping
 (:215-224 etc.) is done with masked device updates instead of ``if update_flag.sum()`` host syncs
 (same result: ``opt_margin`` is the margin of the last iteration that improved any candidate);
 ``kabsch_noise`` (optional, one [E, 3, 3] tensor per iteration) replays the reference's
-``rand_like(H)`` draws.  WCKinGPISGraspOptimizer (:513-612) needs cvxpylayers (absent) and is out
-of scope.
+``rand_like(H)`` draws.
 """
 from __future__ import annotations
 
@@ -886,3 +886,89 @@ class KinGPISGraspOptimizer:
                 "cdx_fk_forward")
         st.tips.copy_(tips32.double() + self.palm_offset.to(torch.float64))
         return _gpis_mode_run(self, 1, chain, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step)
+
+
+class WCKinGPISGraspOptimizer:
+    """Joint-space optimiser on the minimum-wrench certificate (optimize_pregrasp.py:513-612): the cost of a candidate
+    is the smallest net force and torque its contacts can leave (wrench.min_wrench — the reference solves it through
+    cvxpylayers) instead of the Kabsch equilibrium of springs.  An eager loop like KinGPISGraspOptimizer.optimize, with
+    two deliberate differences from the reference: every candidate is its own force problem (the reference's solve
+    couples the candidates of a batch: it centres on the mean of all E·T tips and puts only the first four forces in
+    the objective, so it is only well-formed for E = 1, where the two coincide), and the forces are the unique
+    least-effort minimiser (csrc/cdx_wrench.h), not whichever one SCS lands on.  As in the reference, ``uncertainty``
+    is accepted and ignored (the variance weight is the literal 20), ``optimize_target`` is a dummy, the compliance
+    receives no gradient (it only scales the returned targets), and the loss reaches the joints through the explicit
+    partial ∂wrench/∂tips alone."""
+
+    def __init__(self, robot_urdf, ee_link_names, ee_link_offsets=EE_OFFSETS, palm_offset=WRIST_OFFSET, num_iters=1000,
+                 optimize_target=False, ref_q=None, tip_bounding_box=(FINGERTIP_LB, FINGERTIP_UB), min_force=5.0,
+                 mass=0.1, com=(0.0, 0.0, 0.0), gravity=True, uncertainty=0.0, device="cuda"):
+        self.device = torch.device(device)
+        self.loop_events = None  # optional (start, end) CUDA events recorded around the iterations
+        self.ref_q = torch.tensor(list(ref_q)).to(self.device)
+        self.robot_model = DifferentiableRobotModel(robot_urdf, device=device)
+        self.num_iters = num_iters
+        self.ee_link_names = list(ee_link_names)
+        self.ee_link_offsets = ee_link_offsets
+        self.palm_offset = torch.tensor(np.asarray(palm_offset)).double().to(self.device)
+        self.tip_bounding_box = [torch.tensor(tip_bounding_box[0]).to(self.device).view(-1, 3),
+                                 torch.tensor(tip_bounding_box[1]).to(self.device).view(-1, 3)]
+        self.min_force = min_force
+        self.mass, self.com, self.gravity = mass, list(com), gravity
+
+    def forward_kinematics(self, joint_angles):
+        tips = self.robot_model.compute_forward_kinematics(joint_angles, self.ee_link_names,
+                                                          offsets=self.ee_link_offsets, recursive=True)[0]
+        return (tips.view(-1, 3) + self.palm_offset).view(-1, 3)
+
+    def optimize(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose=True, trace_rows=False):
+        """→ (q, compliance, target, flag).  The returned target of a candidate is ``tip + forces / compliance`` of
+        its best iteration (:603): the springs that would exert the certified forces.  ``loss_rows`` (with
+        ``trace_rows``) keeps the per-candidate losses, ``wrench_rows`` the min_wrench result of every iteration."""
+        from .wrench import min_wrench
+        joint_angles = joint_angles.clone().requires_grad_(True)
+        compliance = compliance.clone().requires_grad_(True)
+        target_pose = target_pose.clone()
+        optim = torch.optim.RMSprop([{"params": joint_angles, "lr": 1e-2}, {"params": compliance, "lr": 0.2}])
+        E, T = target_pose.shape[0], target_pose.shape[1]
+        best = _Best(torch.float64, E, T, self.device, q=joint_angles, comp=compliance, target=target_pose)
+        self.loss_history, self.loss_rows, self.wrench_rows = [], [], []
+        if self.loop_events:
+            self.loop_events[0].record()
+        for _ in range(self.num_iters):
+            optim.zero_grad()
+            all_tip = self.forward_kinematics(joint_angles)
+            dist, var = gpis.pred(all_tip)
+            tar_dist, _ = gpis.pred(target_pose.reshape(-1, 3))
+            normal = gpis.compute_normal(all_tip)
+            tips = all_tip.view(target_pose.shape)
+            res = min_wrench(tips, normal.view(target_pose.shape), friction_mu, min_force=self.min_force)
+            margin, forces = res.margin, res.forces
+            force_norm = forces.norm(dim=2)
+            c = res.wrench * 5.0
+            center_cost = (tips.mean(dim=1) - target_pose.mean(dim=1)).norm(dim=1) * 10.0
+            ref_cost = (joint_angles - self.ref_q).norm(dim=1) * 20.0
+            variance_cost = 20 * torch.log(100 * var).view(E, T)  # (:587: the literal 20, not ``uncertainty``)
+            dist_cost = 1000 * torch.abs(dist).view(E, T).sum(dim=1)
+            tar_dist_cost = 10 * tar_dist.view(E, T).sum(dim=1)
+            l = (c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0) + ref_cost +
+                 variance_cost.max(dim=1)[0])
+            l.sum().backward()
+            self.loss_history.append(l.detach().sum())  # device scalar, no sync
+            if trace_rows:
+                self.loss_rows.append(l.detach().clone())
+                self.wrench_rows.append(res)
+            if verbose:
+                print("Loss:", float(l.sum()), res.wrench.detach())
+            best.update(l, margin, normal, q=joint_angles, comp=compliance,
+                        target=tips + forces / compliance.unsqueeze(2))
+            optim.step()
+            with torch.no_grad():  # (:606-608)
+                compliance.clamp_(min=40.0)
+                target_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
+        if self.loop_events:
+            self.loop_events[1].record()
+        if verbose:
+            print(best.margin, best.normal)
+        self.best_loss = best.value
+        return best.params["q"], best.params["comp"], best.params["target"], best.flag()

@@ -365,6 +365,39 @@ int cdx_ik_solve(const cdx_chain* chain, const cdx_ik_params* params, int64_t E,
 int32_t cdx_ik_rows_per_block(int32_t n_tips, int32_t n_dofs);
 size_t cdx_ik_abi_size(void);
 
+/* Batched minimum-wrench contact forces (what the reference asks of cvxpy in math_utils.py:6-57; the rule is
+ * csrc/cdx_wrench.h): per candidate row, the forces F [T][3] inside their friction cones (n̂·F ≤ −‖F‖/sqrt(1 + mu²))
+ * that press at least min_force along the normal (n̂·F ≤ −min_force) and minimise
+ * ½‖ΣF‖ + ½‖Σ r×F‖ + (reg/2)·Σ‖F‖², r = tip − mean of the row's tips.  E independent rows, the WHOLE solve (ADMM with
+ * penalty rho, a duality-gap certificate every check_every iterations) in one launch, float64, no workspace.
+ *   tips, normals [E*T*3] f64 (normals need not be unit).
+ * Outputs (f64 unless noted): forces [E*T*3]; wrench [E] = ‖ΣF‖ + ‖Σ r×F‖; margin [E*T] = (−F/‖F‖)·n̂ − 1/sqrt(1 + mu²);
+ *   dual [E*6] = (y_f, y_τ), each of norm ≤ ½; gap [E] = P(F) − D(y) ≥ ‖F − F*‖²·reg/2; iters [E] i32; status [E] i32:
+ *   0 = gap ≤ tol·max(1, |P|), 1 = max_iters used (the best pair checked is returned, finite and feasible), 2 = a
+ *   non-finite input or a zero normal in this row (every float output NaN, iters 0);
+ *   grad_tips [E*T*3] (nullable) = ∂wrench/∂tips with F held constant.
+ * CDX_EINVAL, with nothing launched: a null params or required pointer, E < 0, n_tips outside 1 … CDX_MAX_TIPS,
+ *   mu / reg / rho / tol not finite and positive, min_force negative or not finite, max_iters < 0, check_every < 1.
+ *   E = 0 is a no-op. */
+typedef struct {
+  int32_t n_tips;
+  int32_t max_iters;
+  int32_t check_every;
+  int32_t _pad;
+  double mu;
+  double min_force;
+  double reg;
+  double rho;
+  double tol;
+} cdx_wrench_params;
+int cdx_min_wrench(const cdx_wrench_params* params, int64_t E, const double* tips, const double* normals,
+                   double* forces, double* wrench, double* margin, double* dual, double* gap, int32_t* iters,
+                   int32_t* status, double* grad_tips, cdx_stream_t stream);
+/* Rows per workgroup of cdx_min_wrench (for tests of its seams; 0 for n_tips out of range), and
+ * sizeof(cdx_wrench_params). */
+int32_t cdx_wrench_rows_per_block(int32_t n_tips);
+size_t cdx_wrench_abi_size(void);
+
 /* ------------------------------------------------------ prob-mode closure -------
  * Replaces ProbabilisticGraspOptimizer.closure (optimize_pregrasp.py:741-769) —
  * forward AND backward for E candidates — plus its callees compute_loss (:713-739),
