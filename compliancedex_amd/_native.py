@@ -62,6 +62,21 @@ class CdxWrenchParams(C.Structure):
                 ("tol", C.c_double)]
 
 
+HAND_MAX_SPHERES, HAND_MAX_PAIRS, HAND_LANES = 256, 32768, 64  # CDX_MAX_SPHERES, CDX_HAND_MAX_PAIRS, CDX_HAND_LANES
+
+
+class CdxHand(C.Structure):
+    _fields_ = [("n_spheres", C.c_int32), ("n_pairs", C.c_int32), ("n_bodies", C.c_int32), ("_pad", C.c_int32),
+                ("radius", C.c_void_p), ("local", C.c_void_p), ("body", C.c_void_p), ("len", C.c_void_p),
+                ("pairs", C.c_void_p), ("entry", C.c_void_p), ("group_base", C.c_int32 * 4)]
+
+
+class CdxHandParams(C.Structure):
+    _fields_ = [("m_obj", C.c_double), ("m_self", C.c_double), ("m_floor", C.c_double), ("w_obj", C.c_double),
+                ("w_self", C.c_double), ("w_floor", C.c_double), ("floor_z", C.c_double), ("floor_on", C.c_int32),
+                ("_pad", C.c_int32)]
+
+
 class CdxProblem(C.Structure):
     _fields_ = [("chain", CdxChain), ("gpis", CdxGpis), ("n_levels", C.c_int32), ("n_query_levels", C.c_int32),
                 ("level_query", C.c_int32 * MAX_LEVELS), ("coeff", (C.c_float * MAX_TIPS) * MAX_LEVELS),
@@ -217,6 +232,12 @@ _SIGS = {
     "cdx_min_wrench": (C.c_int, [C.POINTER(CdxWrenchParams), _I64] + [_P] * 11),
     "cdx_wrench_rows_per_block": (C.c_int32, [C.c_int32]),
     "cdx_wrench_abi_size": (C.c_size_t, []),
+    "cdx_hand_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
+    "cdx_hand_abi_sizes": (None, [C.POINTER(C.c_size_t)]),
+    "cdx_hand_prepare": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.POINTER(CdxHand), _P]),
+    "cdx_hand_spheres": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxHand), _I64, _P, _P, _P, _P, _P, _P]),
+    "cdx_hand_cost": (C.c_int, [C.POINTER(CdxHand), C.POINTER(CdxHandParams), _I64] + [_P] * 8),
+    "cdx_hand_pullback": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxHand), _I64] + [_P] * 7),
     "cdx_force_eq_forward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
                                        _P]),
     "cdx_force_eq_backward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
@@ -324,6 +345,11 @@ def load():
         if lib.cdx_wrench_abi_size() != C.sizeof(CdxWrenchParams):
             raise ImportError(f"ABI struct size mismatch (wrench): library {lib.cdx_wrench_abi_size()} vs binding "
                               f"{C.sizeof(CdxWrenchParams)}")
+        sizes = (C.c_size_t * 2)()
+        lib.cdx_hand_abi_sizes(sizes)
+        mine = [C.sizeof(CdxHand), C.sizeof(CdxHandParams)]
+        if list(sizes) != mine:
+            raise ImportError(f"ABI struct size mismatch (hand): library {list(sizes)} vs binding {mine}")
         info = build_info()
         if not info["matches"] and "CDX_LIB" not in os.environ:
             import warnings

@@ -1,6 +1,6 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
 // cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h / cdx_sample.h / cdx_knn.h /
-// cdx_wrench.h.
+// cdx_wrench.h / cdx_hand.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
@@ -16,6 +16,7 @@
 #include "cdx_field.h"
 #include "cdx_fps.h"
 #include "cdx_gpis_mode.h"
+#include "cdx_hand.h"
 #include "cdx_ik.h"
 #include "cdx_knn.h"
 #include "cdx_mesh.h"
@@ -415,6 +416,69 @@ int cdxh_min_wrench(const cdx_wrench_params* params, int64_t E, const double* ti
     status[e] = cdx::mw_row(*params, tips + e * T * 3, normals + e * T * 3, m, forces + e * T * 3, wrench + e,
                             margin + e * T, dual + e * 6, gap + e, iters + e, grad_tips ? grad_tips + e * T * 3 : nullptr);
   return CDX_OK;
+}
+
+// The whole-hand sphere model (cdx_hand.h) row by row, with the device entries' argument checks; the tables of
+// cdxh_hand_prepare live in HOST memory (cdx::hand_bytes(S, P) bytes).
+int cdxh_hand_prepare(int32_t n_bodies, int32_t S, const float* local, const double* radius, const int32_t* body,
+                      int32_t P, const int32_t* pairs, void* tables, cdx_hand* out) {
+  if (!cdx::hand_bytes(S, P) || !tables || !out) return CDX_EINVAL;
+  return cdx::hand_fill(n_bodies, S, local, radius, body, P, pairs, static_cast<char*>(tables), out);
+}
+
+int cdxh_hand_spheres(const cdx_chain* c, const cdx_hand* h, int64_t E, const double* q, const double* pp,
+                      const double* po, float* poses, double* centers) {
+  int rc = cdx::hand_chain_code(c);
+  if (rc) return rc;
+  rc = cdx::hand_code(h);
+  if (rc) return rc;
+  if (h->n_bodies != c->n_bodies || E < 0) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if ((!q && c->n_dofs > 0) || !poses || !centers) return CDX_EINVAL;
+  const int64_t nb = c->n_bodies, S = h->n_spheres;
+  for (int64_t e = 0; e < E; ++e)
+    cdx::hand_spheres_row(*c, *h, q + e * c->n_dofs, pp ? pp + 3 * e : nullptr, po ? po + 3 * e : nullptr,
+                          poses + e * nb * 12, centers + e * S * 3);
+  return CDX_OK;
+}
+
+int cdxh_hand_cost(const cdx_hand* h, const cdx_hand_params* p, int64_t E, const double* centers, const double* dist,
+                   const double* gdist, double* cost, double* depth, int32_t* worst, double* g_centers) {
+  int rc = cdx::hand_code(h);
+  if (rc) return rc;
+  rc = cdx::hand_params_code(p);
+  if (rc) return rc;
+  if (E < 0 || E > 0x7fffffff || (dist == nullptr) != (gdist == nullptr)) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (!centers || !cost || !depth || !worst || !g_centers) return CDX_EINVAL;
+  const int64_t S = h->n_spheres;
+  for (int64_t e = 0; e < E; ++e)
+    cdx::hand_cost_row(*h, *p, centers + e * S * 3, dist ? dist + e * S : nullptr, gdist ? gdist + e * S * 3 : nullptr,
+                       cost + e, depth + 3 * e, worst + 3 * e, g_centers + e * S * 3);
+  return CDX_OK;
+}
+
+int cdxh_hand_pullback(const cdx_chain* c, const cdx_hand* h, int64_t E, const float* poses, const double* g_centers,
+                       const double* po, double* g_q, double* g_pp, double* g_po) {
+  int rc = cdx::hand_chain_code(c);
+  if (rc) return rc;
+  rc = cdx::hand_code(h);
+  if (rc) return rc;
+  if (h->n_bodies != c->n_bodies || E < 0 || E > 0x7fffffff) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (!poses || !g_centers || (!g_q && c->n_dofs > 0) || !g_pp || !g_po) return CDX_EINVAL;
+  const int64_t nb = c->n_bodies, S = h->n_spheres;
+  for (int64_t e = 0; e < E; ++e)
+    cdx::hand_pullback_row(*c, *h, poses + e * nb * 12, g_centers + e * S * 3, po ? po + 3 * e : nullptr,
+                           g_q + e * c->n_dofs, g_pp + 3 * e, g_po + 3 * e);
+  return CDX_OK;
+}
+
+size_t cdxh_hand_bytes(int32_t S, int32_t P) { return cdx::hand_bytes(S, P); }
+
+// cdx::hand_sincos on n angles.
+void cdxh_hand_sincos(const double* x, int64_t n, double* s, double* c) {
+  for (int64_t i = 0; i < n; ++i) cdx::hand_sincos(x[i], s + i, c + i);
 }
 
 int64_t cdxh_n_queries(const cdx_problem* P, int64_t E) { return cdx::n_queries(*P, E); }

@@ -759,6 +759,73 @@ int cdx_collision_loss(const cdx_collision* c, int64_t E, const double* q, const
                        const double* palm_ori, double* cost, double* g_q, double* g_palm_pos,
                        double* g_palm_ori, int32_t accumulate, cdx_stream_t stream);
 
+/* ------------------------------------------------------ whole-hand spheres -------
+ * The hand's volume as spheres fixed to its links, and the three kernels that turn it into a penetration cost, its
+ * gradient in joint space and a report (the reference leaves whole-hand checks to PyBullet, verify_pregrasp.py, and
+ * cuRobo's collision spheres, traj_gen.py).  The rule — every formula and the order of every sum — is csrc/cdx_hand.h.
+ *
+ * cdx_hand_prepare, once per model: checks the caller's HOST tables and copies them, with the per-sphere partner
+ *   lists, into `tables` (device, cdx_hand_bytes(S, P) caller-owned bytes; waits on `stream`), and fills *out, the
+ *   descriptor the other entries take (host struct of device pointers; valid while `tables` is).  local [S*3] f32 the
+ *   centres in their bodies' frames, radius [S] f64 finite and > 0, body [S] ascending in 0 … n_bodies − 1, pairs
+ *   [P*2] sphere indices with 0 ≤ a < b < S, no sphere in more than min(S − 1, P) of them.  1 ≤ S ≤ CDX_MAX_SPHERES, 0 ≤ P ≤ CDX_HAND_MAX_PAIRS.
+ * cdx_hand_spheres: q [E*n_dofs] f64 (rounded to float32 like every FK input), palm_pos, palm_ori [E*3] f64 (each
+ *   nullable: zero) → poses [E*n_bodies*12] f32 (R row-major, then t, in the hand frame; a body's pose has the bits of
+ *   cdx_fk_forward's walk to it) and centers [E*S*3] f64 in the world frame: Rp·(double)(R_b·c_local + t_b) + palm_pos.
+ *   h->n_bodies must be the chain's.
+ * cdx_hand_cost: centers [E*S*3]; dist [E*S], gdist [E*S*3] the object's signed distance (positive outside) and its
+ *   gradient at the centres (both or neither: NULL turns the object class off) → cost [E], depth [E*3] the largest
+ *   penetration at zero margin per class (object r − d, self r_a + r_b − ρ, floor r − (z − floor_z); positive =
+ *   intersecting; −inf for a class that is off or empty), worst [E*3] i32 the sphere (object, floor) or pair (self)
+ *   that attains it (first on ties, −1 for −inf), g_centers [E*S*3] = ∂cost/∂centers.  No atomics: the bits do not
+ *   depend on E, on the row's position or on the run.
+ * cdx_hand_pullback: poses (cdx_hand_spheres' own), g_centers [E*S*3], palm_ori [E*3] (nullable: zero; the palm
+ *   position does not enter) → g_q [E*n_dofs], g_palm_pos [E*3], g_palm_ori [E*3] f64: the true derivative of Σ
+ *   g_centers·centers (a sign-0 joint gets 0).
+ * A row with a non-finite input is NaN in its own float outputs (worst −1) and touches no other row.
+ * Return codes: a null or malformed chain, or a body more than CDX_MAX_DEPTH levels deep → CDX_ECHAIN; sizes over the
+ *   limits, a null required pointer, a model whose n_bodies is not the chain's, non-finite parameters, E < 0 →
+ *   CDX_EINVAL, with nothing launched; E = 0 is a no-op. */
+#define CDX_MAX_SPHERES 256
+#define CDX_HAND_MAX_PAIRS 32768
+#define CDX_HAND_LANES 64 /* lanes per candidate of the cost and pull-back kernels (fixes the order of their sums) */
+
+typedef struct {
+  int32_t n_spheres;
+  int32_t n_pairs;
+  int32_t n_bodies;
+  int32_t _pad;
+  const double* radius;    /* [S] */
+  const float* local;      /* [S*3] */
+  const int32_t* body;     /* [S] ascending */
+  const int32_t* len;      /* [S] length of every sphere's partner list */
+  const int32_t* pairs;    /* [P*2] */
+  const int32_t* entry;    /* partner lists: entry k of sphere s at group_base[s/64] + 64k + s%64 = partner | pair << 8, */
+                           /* in ascending pair index (a group of 64 spheres is as long as its longest list) */
+  int32_t group_base[4];
+} cdx_hand;
+
+typedef struct {
+  double m_obj, m_self, m_floor; /* margins, metres */
+  double w_obj, w_self, w_floor; /* weights */
+  double floor_z;
+  int32_t floor_on;
+  int32_t _pad;
+} cdx_hand_params;
+
+size_t cdx_hand_bytes(int32_t S, int32_t P);
+int cdx_hand_prepare(int32_t n_bodies, int32_t S, const float* local, const double* radius, const int32_t* body,
+                     int32_t P, const int32_t* pairs, void* tables, cdx_hand* out, cdx_stream_t stream);
+int cdx_hand_spheres(const cdx_chain* chain, const cdx_hand* h, int64_t E, const double* q, const double* palm_pos,
+                     const double* palm_ori, float* poses, double* centers, cdx_stream_t stream);
+int cdx_hand_cost(const cdx_hand* h, const cdx_hand_params* p, int64_t E, const double* centers, const double* dist,
+                  const double* gdist, double* cost, double* depth, int32_t* worst, double* g_centers,
+                  cdx_stream_t stream);
+int cdx_hand_pullback(const cdx_chain* chain, const cdx_hand* h, int64_t E, const float* poses, const double* g_centers,
+                      const double* palm_ori, double* g_q, double* g_palm_pos, double* g_palm_ori, cdx_stream_t stream);
+/* sizeof(cdx_hand), sizeof(cdx_hand_params). */
+void cdx_hand_abi_sizes(size_t* out2);
+
 /* ------------------------------------------------------- fused optimizer step ------
  * One launch per iteration of ProbabilisticGraspOptimizer.optimize (optimize_pregrasp.py:805-836)
  * after the closure: best-iterate update (:821-829, before the step, only when s > best_after),

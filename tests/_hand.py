@@ -1,0 +1,419 @@
+"""Shared inputs, a float64 statement and host loaders for the whole-hand sphere model (csrc/cdx_hand.h).
+
+The statement.  ``centers_of``, ``cost_of`` and ``pullback_of`` restate the three kernels in torch float64 on the all-bodies form of
+``_chains.statement``'s FK: centres c = Rp·(R_b·c_local + t_b) + palm_pos with Rp = Rx·Ry·Rz, the three quadratic hinges,
+the class maxima with their first index, and every gradient by autograd (the object's distance enters as
+d + ∇d·(c − c₀), whose derivative is the given ∇d) — an independent derivation of cdx_hand.h's closed forms.
+
+Families.  A family is (chain, S, pairs): seeded spheres (radii 0.01 – 0.03, centres within 0.02 of random bodies), a
+pair list (none, one, or every a < b), 257 rows of joint angles (float32 values) and palm poses, and the analytic test
+object — a sphere of radius 0.08 at the origin, evaluated HERE at the centres and handed over as dist / gdist.  Before
+a family is used ``family`` asserts that each class that is on has rows with active AND inactive terms in at least a
+quarter of the rows (with a single sphere or a single pair a row holds one term: then at least a quarter of the rows
+are active and a quarter inactive), and that every row's class maxima are unique by 1e-9, so ``worst`` is well defined.
+
+Tolerances (the issue's): centres rel ≤ _chains.TOL["pos"]; cost |Δ| ≤ 1e-12·Σ|term| and per sphere and component
+|Δg| ≤ 1e-12·Σ|contribution| — at most 256 + 256 + 32640 terms a row (8704 a lane at worst), n·2⁻⁵³ ≈ 1e-12 with under
+ten roundings a term; pull-back |Δg_q| ≤ TOL_JAC·Σ‖g_s‖₁, g_pp to 1e-12·Σ|g|, g_po to 2·δ·Σ‖g_s‖₁ with δ =
+TOL["pos"]·max|c_h|.
+"""
+import ctypes as C
+import functools
+import os
+
+import numpy as np
+import torch
+
+from compliancedex_amd import _native as N
+from compliancedex_amd.hand import HandSpheres
+from tests import _chains, _host
+
+PI = np.pi
+E_MAX = _chains.B_MAX
+BATCHES = _chains.BATCHES
+OBJ_RADIUS = 0.08
+# (m_self < 0: the synthetic chains keep 32 bodies within 0.06 m, so that with radii of 0.01 – 0.03 nearly every pair
+# overlaps; a negative margin leaves inactive pairs in every family)
+PARAMS = dict(m_obj=0.01, m_self=-0.01, m_floor=0.01, w_obj=1.5, w_self=0.7, w_floor=2.0, floor_z=-0.03)
+# (chain, S, pairs): every chain, S ∈ {1, 63, 65, 256} and pairs ∈ {0, 1, full} of the issue appears
+FAMILIES = (("hand8", 63, "full"), ("hand8", 1, "none"), ("tree8", 256, "full"), ("tree8", 65, "one"),
+            ("line16", 65, "full"), ("line16", 256, "none"), ("allegro", 65, "full"), ("allegro", 63, "one"),
+            ("iiwa7_allegro", 256, "one"), ("iiwa7_allegro", 63, "full"))
+SMALL = (("hand8", 63, "full"), ("tree8", 65, "one"), ("line16", 65, "full"), ("allegro", 63, "one"))
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "spheres_allegro.json")
+
+
+def robot_of(case):
+    return _chains.robot_dict(case) if case in _chains.CASES else case
+
+
+def params_struct(floor=True, **over):
+    v = dict(PARAMS, **over)
+    p = N.CdxHandParams()
+    for k in ("m_obj", "m_self", "m_floor", "w_obj", "w_self", "w_floor", "floor_z"):
+        setattr(p, k, float(v[k]))
+    p.floor_on = 1 if floor else 0
+    return p
+
+
+def random_spheres(robot, S, seed):
+    """{link: [(centre, radius)]}: S spheres, radii 0.01 – 0.03, centres within 0.02 of random bodies."""
+    from compliancedex_amd.urdf import load_robot
+    bodies = (robot if isinstance(robot, dict) else load_robot(robot))["bodies"]
+    rng = np.random.default_rng(seed)
+    out = {}
+    for _ in range(S):
+        b = bodies[int(rng.integers(len(bodies)))]["name"]
+        v = rng.standard_normal(3)
+        v *= 0.02 * rng.random() ** (1.0 / 3.0) / np.linalg.norm(v)
+        out.setdefault(b, []).append((tuple(v), float(rng.uniform(0.01, 0.03))))
+    return out
+
+
+def all_pairs(S):
+    a, b = np.triu_indices(S, 1)
+    return np.stack([a, b], 1).astype(np.int32)
+
+
+# ------------------------------------------------------------------ the float64 statement
+def all_poses(desc, qt):
+    """Poses of every body at qt [B, D] (torch float64) → R [B, n, 3, 3], t [B, n, 3] in the hand frame."""
+    B = qt.shape[0]
+    R = [torch.eye(3, dtype=torch.float64).expand(B, 3, 3)]
+    t = [torch.zeros(B, 3, dtype=torch.float64)]
+    for i in range(1, desc.n_bodies):
+        body = desc.bodies[i]
+        F = torch.tensor(list(body.F), dtype=torch.float64).view(3, 3)
+        t.append(t[body.parent] + R[body.parent] @ torch.tensor(list(body.t), dtype=torch.float64))
+        Rn = R[body.parent] @ F
+        if body.dof >= 0:
+            Rn = Rn @ _chains._axis_rot(body.axis, float(body.sign) * qt[:, body.dof])
+        R.append(Rn)
+    return torch.stack(R, 1), torch.stack(t, 1)
+
+
+def euler(ang):
+    """(Rx(a)·Ry(b))·Rz(c) for ang [B, 3]."""
+    return (_chains._axis_rot(0, ang[:, 0]) @ _chains._axis_rot(1, ang[:, 1])) @ _chains._axis_rot(2, ang[:, 2])
+
+
+def centers_of(hs, qt, palm_t):
+    """→ (centres [B, S, 3] in the world frame, c_h [B, S, 3] in the hand frame)."""
+    R, t = all_poses(hs.desc, qt)
+    body = torch.from_numpy(hs.body.astype(np.int64))
+    cl = torch.from_numpy(hs.local.astype(np.float64))
+    ch = (R[:, body] @ cl[None, :, :, None]).squeeze(-1) + t[:, body]
+    if palm_t is None:
+        return ch, ch
+    return (euler(palm_t[:, 3:])[:, None] @ ch[..., None]).squeeze(-1) + palm_t[:, None, :3], ch
+
+
+def object_sdf(c):
+    """The analytic test object at centres [..., 3] (numpy) → (d, ∇d)."""
+    n = np.linalg.norm(c, axis=-1)
+    return n - OBJ_RADIUS, c / n[..., None]
+
+
+def cost_of(hs, c, dist, gdist, floor=True, chunk=32, **over):
+    """The statement of cdx_hand_cost at centres c [B, S, 3] (numpy) → dict(cost, depth [B, 3], worst [B, 3],
+    g [B, S, 3] by autograd, abs_cost [B] = Σ|term|, abs_g [B, S, 3] = Σ|contribution|, active [B, 3, 2] = counts of
+    active / inactive terms per class, gap [B, 3] = the margin of each class maximum over the runner-up)."""
+    v = dict(PARAMS, **over)
+    r = torch.from_numpy(hs.radius)
+    pr = torch.from_numpy(hs.pairs.astype(np.int64))
+    B, S = c.shape[0], c.shape[1]
+    out = dict(cost=np.zeros(B), depth=np.full((B, 3), -np.inf), worst=np.full((B, 3), -1, np.int32),
+               g=np.zeros((B, S, 3)), abs_cost=np.zeros(B), abs_g=np.zeros((B, S, 3)),
+               active=np.zeros((B, 3, 2), np.int64), gap=np.full((B, 3), np.inf))
+
+    def top(pen, rows, k):
+        o = torch.sort(pen, dim=1, descending=True, stable=True)
+        out["depth"][rows, k] = o.values[:, 0].numpy()
+        out["worst"][rows, k] = o.indices[:, 0].numpy()
+        if pen.shape[1] > 1:
+            out["gap"][rows, k] = (o.values[:, 0] - o.values[:, 1]).numpy()
+
+    for lo in range(0, B, chunk):
+        rows = slice(lo, min(lo + chunk, B))
+        ct = torch.tensor(c[rows], requires_grad=True)
+        cost = torch.zeros(ct.shape[0], dtype=torch.float64)
+        absg = torch.zeros_like(ct)
+        absc = torch.zeros_like(cost)
+        if dist is not None:
+            d0, gd = torch.from_numpy(dist[rows]), torch.from_numpy(gdist[rows])
+            d = d0 + (gd * (ct - ct.detach())).sum(-1)
+            p = torch.clamp(r + v["m_obj"] - d, min=0.0)
+            term = v["w_obj"] * 0.5 * p ** 2
+            cost, absc = cost + term.sum(1), absc + term.detach().sum(1)
+            absg = absg + (v["w_obj"] * p.detach())[..., None] * gd.abs()
+            out["active"][rows, 0] = torch.stack([(p > 0).sum(1), (p <= 0).sum(1)], 1).numpy()
+            top((r - d0), rows, 0)
+        if len(pr):
+            diff = ct[:, pr[:, 0]] - ct[:, pr[:, 1]]
+            rho = torch.sqrt((diff ** 2).sum(-1))
+            rr = r[pr[:, 0]] + r[pr[:, 1]]
+            p = torch.clamp(rr + v["m_self"] - rho, min=0.0)
+            term = v["w_self"] * 0.5 * p ** 2
+            cost, absc = cost + term.sum(1), absc + term.detach().sum(1)
+            with torch.no_grad():
+                unit = torch.where(rho[..., None] > 0, diff.abs() / rho[..., None], torch.zeros_like(diff))
+                contrib = (v["w_self"] * p)[..., None] * unit
+                absg.index_add_(1, pr[:, 0], contrib)
+                absg.index_add_(1, pr[:, 1], contrib)
+            out["active"][rows, 1] = torch.stack([(p > 0).sum(1), (p <= 0).sum(1)], 1).numpy()
+            top((rr - rho).detach(), rows, 1)
+        if floor:
+            h = ct[:, :, 2] - v["floor_z"]
+            p = torch.clamp(r + v["m_floor"] - h, min=0.0)
+            term = v["w_floor"] * 0.5 * p ** 2
+            cost, absc = cost + term.sum(1), absc + term.detach().sum(1)
+            with torch.no_grad():
+                absg[:, :, 2] += v["w_floor"] * p
+            out["active"][rows, 2] = torch.stack([(p > 0).sum(1), (p <= 0).sum(1)], 1).numpy()
+            top((r - h).detach(), rows, 2)
+        if cost.requires_grad:
+            cost.sum().backward()
+            out["g"][rows] = ct.grad.numpy()
+        out["cost"][rows] = cost.detach().numpy()
+        out["abs_cost"][rows] = absc.numpy()
+        out["abs_g"][rows] = absg.detach().numpy()
+    return out
+
+
+def pullback_of(hs, q, palm, g):
+    """The statement of cdx_hand_pullback by autograd: cotangent g [B, S, 3] → (g_q, g_pp, g_po); palm None: identity."""
+    qt = torch.tensor(q, requires_grad=True)
+    pt = torch.tensor(palm, requires_grad=True) if palm is not None else None
+    c, _ = centers_of(hs, qt, pt)
+    (c * torch.tensor(g)).sum().backward()
+    gq = qt.grad.numpy() if qt.grad is not None else np.zeros_like(q)
+    if pt is None:
+        return gq, None, None
+    return gq, pt.grad[:, :3].numpy(), pt.grad[:, 3:].numpy()
+
+
+# ------------------------------------------------------------------ families
+def _rows(hs, case, seed):
+    """q [257, D] (float32 values) and palm [257, 6]: any orientation, the position such that the centroid of the row's
+    spheres lies 0.03 – 0.17 from the origin in a random direction — the hand straddles the object's surface and the
+    floor whatever the chain's size."""
+    rng = np.random.default_rng(seed)
+    D = hs.desc.n_dofs
+    lim = PI if case in _chains.CASES else 1.0
+    q = rng.uniform(-lim, lim, (E_MAX, D)).astype(np.float32).astype(np.float64)
+    ori = rng.uniform(-PI, PI, (E_MAX, 3))
+    off = rng.standard_normal((E_MAX, 3))
+    off *= rng.uniform(0.03, 0.17, (E_MAX, 1)) / np.linalg.norm(off, axis=1, keepdims=True)
+    with torch.no_grad():
+        ch = centers_of(hs, torch.from_numpy(q), None)[1].mean(1)
+        pos = off - (euler(torch.from_numpy(ori)) @ ch[..., None]).squeeze(-1).numpy()
+    return q, np.concatenate([pos, ori], 1)
+
+
+@functools.lru_cache(None)
+def family(case, S, pairs):
+    """dict(hs, q, palm, centers, dist, gdist, cost (cost_of's dict), g_q, g_pp, g_po) of a family at its 257 rows: the
+    statement computed once and shared (read-only), after the activity and uniqueness checks of the module docstring."""
+    seed = 7000 + 97 * FAMILIES.index((case, S, pairs)) if (case, S, pairs) in FAMILIES else 6999
+    robot = robot_of(case)
+    spheres = random_spheres(robot, S, seed)
+    hs = HandSpheres(robot, spheres, pairs=np.zeros((0, 2), np.int32))
+    q, palm = _rows(hs, case, seed + 1)
+    with torch.no_grad():
+        c = centers_of(hs, torch.from_numpy(q), torch.from_numpy(palm))[0].numpy()
+    if pairs == "full":
+        pl = all_pairs(S)
+    elif pairs == "one":  # the pair whose hinge is active in the share of rows nearest one half
+        ap = all_pairs(S)
+        rho = np.linalg.norm(c[:, ap[:, 0]] - c[:, ap[:, 1]], axis=2)
+        act = (hs.radius[ap[:, 0]] + hs.radius[ap[:, 1]] + PARAMS["m_self"] - rho > 0).mean(0)
+        pl = ap[[int(np.argmin(np.abs(act - 0.5)))]]
+    else:
+        pl = np.zeros((0, 2), np.int32)
+    hs = HandSpheres(robot, spheres, pairs=pl)
+    dist, gdist = object_sdf(c)
+    cost = cost_of(hs, c, dist, gdist)
+    on = [0, 2] + ([1] if len(pl) else [])
+    for k in on:
+        a = cost["active"][:, k]
+        if a.sum(1).max() > 1:
+            assert ((a[:, 0] > 0) & (a[:, 1] > 0)).mean() >= 0.25, (case, S, pairs, k, a[:4])
+        else:
+            assert (a[:, 0] > 0).mean() >= 0.25 and (a[:, 1] > 0).mean() >= 0.25, (case, S, pairs, k)
+        assert (cost["gap"][:, k] > 1e-9).all(), (case, S, pairs, k, cost["gap"][:, k].min())
+    g_q, g_pp, g_po = pullback_of(hs, q, palm, cost["g"])
+    out = dict(hs=hs, q=q, palm=palm, centers=c, dist=dist, gdist=gdist, cost=cost, g_q=g_q, g_pp=g_pp, g_po=g_po)
+    for v in list(out.values()) + list(cost.values()):
+        if isinstance(v, np.ndarray):
+            v.setflags(write=False)
+    return out
+
+
+# ------------------------------------------------------------------ the host build
+def host_lib():
+    lib = _host.host()
+    if not getattr(lib, "_hand_sigs", False):
+        P, I64 = C.c_void_p, C.c_int64
+        lib.cdxh_hand_bytes.restype = C.c_size_t
+        lib.cdxh_hand_bytes.argtypes = [C.c_int32, C.c_int32]
+        lib.cdxh_hand_prepare.argtypes = [C.c_int32, C.c_int32, P, P, P, C.c_int32, P, P, C.POINTER(N.CdxHand)]
+        lib.cdxh_hand_spheres.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxHand), I64, P, P, P, P, P]
+        lib.cdxh_hand_cost.argtypes = [C.POINTER(N.CdxHand), C.POINTER(N.CdxHandParams), I64] + [P] * 7
+        lib.cdxh_hand_pullback.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxHand), I64] + [P] * 6
+        lib.cdxh_hand_sincos.argtypes = [P, I64, P, P]
+        lib.cdxh_hand_sincos.restype = None
+        lib._hand_sigs = True
+    return lib
+
+
+def ptr(a):
+    return None if a is None else a.ctypes.data_as(C.c_void_p)
+
+
+def host_prepare_raw(n_bodies, local, radius, body, pairs):
+    """cdxh_hand_prepare on raw tables → (rc, cdx_hand, its host buffer)."""
+    lib = host_lib()
+    S, P = len(body), len(pairs)
+    buf = np.zeros(max(lib.cdxh_hand_bytes(S, P), 8), np.uint8)
+    h = N.CdxHand()
+    rc = lib.cdxh_hand_prepare(n_bodies, S, ptr(local), ptr(radius), ptr(body), P, ptr(pairs) if P else None, ptr(buf),
+                               C.byref(h))
+    return rc, h, buf
+
+
+def host_model(hs):
+    if getattr(hs, "_host_model", None) is None:
+        rc, h, buf = host_prepare_raw(hs.desc.n_bodies, hs.local, hs.radius, hs.body, hs.pairs)
+        assert rc == 0, rc
+        hs._host_model = (h, buf)
+    return hs._host_model[0]
+
+
+def f64(a):
+    return None if a is None else np.ascontiguousarray(a, np.float64)
+
+
+def host_spheres(hs, q, palm=None):
+    q = f64(q)
+    E = q.shape[0]
+    pp, po = (None, None) if palm is None else (f64(palm[:, :3]), f64(palm[:, 3:]))
+    poses = np.zeros((E, hs.desc.n_bodies, 12), np.float32)
+    centers = np.zeros((E, hs.n_spheres, 3))
+    rc = host_lib().cdxh_hand_spheres(C.byref(hs.desc), C.byref(host_model(hs)), E, ptr(q), ptr(pp), ptr(po), ptr(poses),
+                                      ptr(centers))
+    assert rc == 0, rc
+    return poses, centers
+
+
+def host_cost(hs, params, centers, dist=None, gdist=None):
+    centers, dist, gdist = f64(centers), f64(dist), f64(gdist)
+    E, S = centers.shape[0], hs.n_spheres
+    cost, depth, worst, g = np.zeros(E), np.zeros((E, 3)), np.zeros((E, 3), np.int32), np.zeros((E, S, 3))
+    rc = host_lib().cdxh_hand_cost(C.byref(host_model(hs)), C.byref(params), E, ptr(centers), ptr(dist), ptr(gdist),
+                                   ptr(cost), ptr(depth), ptr(worst), ptr(g))
+    assert rc == 0, rc
+    return cost, depth, worst, g
+
+
+def host_pullback(hs, poses, g, po=None):
+    poses, g, po = np.ascontiguousarray(poses, np.float32), f64(g), f64(po)
+    E = poses.shape[0]
+    g_q, g_pp, g_po = np.zeros((E, hs.desc.n_dofs)), np.zeros((E, 3)), np.zeros((E, 3))
+    rc = host_lib().cdxh_hand_pullback(C.byref(hs.desc), C.byref(host_model(hs)), E, ptr(poses), ptr(g), ptr(po),
+                                       ptr(g_q), ptr(g_pp), ptr(g_po))
+    assert rc == 0, rc
+    return g_q, g_pp, g_po
+
+
+# ------------------------------------------------------------------ the comparisons (shared with the device file)
+def same_bits(a, b):
+    a, b = np.ascontiguousarray(a), np.ascontiguousarray(b)
+    return a.shape == b.shape and a.dtype == b.dtype and a.tobytes() == b.tobytes()
+
+
+def check_centers(fam, centers, E):
+    e = _chains.rel(centers, fam["centers"][:E])
+    print("centres rel", f"{e:.2e}")
+    assert e < _chains.TOL["pos"], e
+
+
+def check_cost(fam, got, E):
+    """got = (cost, depth, worst, g) on the statement's own centres and distances."""
+    ref = fam["cost"]
+    cost, depth, worst, g = got
+    ec = np.abs(cost - ref["cost"][:E]) / np.maximum(ref["abs_cost"][:E], 1e-300)
+    eg = np.abs(g - ref["g"][:E])
+    bound = 1e-12 * ref["abs_g"][:E]
+    print("cost rel", f"{ec.max():.2e}", "g worst ratio", f"{(eg / np.maximum(bound, 1e-300)).max():.2e}")
+    assert (np.abs(cost - ref["cost"][:E]) <= 1e-12 * ref["abs_cost"][:E]).all(), ec.max()
+    assert (eg <= bound).all(), (eg / np.maximum(bound, 1e-300)).max()
+    assert np.array_equal(worst, ref["worst"][:E]), np.argwhere(worst != ref["worst"][:E])[:4]
+    fin = np.isfinite(ref["depth"][:E])
+    assert np.array_equal(np.isfinite(depth), fin)
+    assert np.abs(depth[fin] - ref["depth"][:E][fin]).max() <= 1e-14
+
+
+def check_pullback(fam, got, E, poses):
+    g_q, g_pp, g_po = got
+    g = fam["cost"]["g"][:E]
+    l1 = np.abs(g).sum((1, 2))
+    ch = (poses[:E, fam["hs"].body, :9].reshape(E, -1, 3, 3).astype(np.float64)
+          @ fam["hs"].local.astype(np.float64)[None, :, :, None]).squeeze(-1) + poses[:E, fam["hs"].body, 9:]
+    delta = _chains.TOL["pos"] * np.abs(ch).max()
+    e = (np.abs(g_q - fam["g_q"][:E]).max(1), np.abs(g_pp - fam["g_pp"][:E]).max(1), np.abs(g_po - fam["g_po"][:E]).max(1))
+    print("pull-back ratios", [f"{(x / np.maximum(b, 1e-300)).max():.2e}"
+                               for x, b in zip(e, (_chains.TOL_JAC * l1, 1e-12 * l1, 2 * delta * l1))])
+    assert (e[0] <= _chains.TOL_JAC * l1).all()
+    assert (e[1] <= 1e-12 * l1).all()
+    assert (e[2] <= 2.0 * delta * l1).all()
+
+
+def poisoned(fam, E=65):
+    """The family's first E rows shuffled into a batch of 2E + 1 rows whose other rows are non-finite (NaN, +inf, −inf in
+    turn, somewhere in the row) → (index of each good row, q, palm, centers, dist, gdist, g)."""
+    rng = np.random.default_rng(11)
+    n = 2 * E + 1
+    at = np.sort(rng.permutation(n)[:E])
+    src = rng.permutation(E)
+    out = []
+    for k, a in enumerate((fam["q"], fam["palm"], fam["centers"], fam["dist"], fam["gdist"], fam["cost"]["g"])):
+        b = np.array(a[rng.integers(0, E, n)])
+        flat = b.reshape(n, -1)
+        for r in range(n):
+            flat[r, rng.integers(flat.shape[1])] = (np.nan, np.inf, -np.inf)[r % 3]
+        b[at] = a[src]
+        out.append(b)
+    return (at, src, *out)
+
+
+def check_rows(fam, spheres, cost, pullback, E=65):
+    """Section 6, shared with the device file: a row's outputs do not depend on E, its position or non-finite
+    neighbours, bit for bit; a non-finite row is NaN in its own outputs."""
+    hs = fam["hs"]
+    par = params_struct()
+    poses0, cen0 = spheres(hs, fam["q"][:E], fam["palm"][:E])
+    cost0 = cost(hs, par, fam["centers"][:E], fam["dist"][:E], fam["gdist"][:E])
+    pull0 = pullback(hs, poses0, fam["cost"]["g"][:E], fam["palm"][:E, 3:])
+    at, src, q, palm, cen, dist, gdist, g = poisoned(fam, E)
+    poses1, cen1 = spheres(hs, q, palm)
+    assert same_bits(poses1[at], poses0[src]) and same_bits(cen1[at], cen0[src])
+    cost1 = cost(hs, par, cen, dist, gdist)
+    for a, b in zip(cost1, cost0):
+        assert same_bits(a[at], b[src])
+    bad = np.setdiff1d(np.arange(len(q)), at)
+    assert np.isnan(cost1[0][bad]).all() and np.isnan(cost1[1][bad]).all() and (cost1[2][bad] == -1).all()
+    assert np.isnan(cost1[3][bad]).all()
+    poses_in = np.array(poses0[np.random.default_rng(3).integers(0, E, len(q))])
+    poses_in[at] = poses0[src]
+    po = np.array(palm[:, 3:])
+    po[at] = fam["palm"][:E, 3:][src]
+    pull1 = pullback(hs, poses_in, g, po)
+    for a, b in zip(pull1, pull0):
+        assert same_bits(a[at], b[src])
+    g_bad = ~np.isfinite(g.reshape(len(g), -1)).all(1)
+    assert g_bad[bad].all()
+    for a in pull1:
+        assert np.isnan(a[g_bad]).all()
+    # a non-finite joint angle or palm reaches the centres of its own row only (checked above by the good rows' bits)
+    q_bad = ~np.isfinite(palm).all(1)
+    assert not np.isfinite(cen1[q_bad]).all()
