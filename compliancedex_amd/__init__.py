@@ -34,6 +34,7 @@ Drop-in operators (same names / arguments as the reference):
                                the whole hand as spheres on its links: penetration of the object, of itself and of
                                the floor for E candidates with the gradient in joint space (PyBullet in
                                verify_pregrasp.py and cuRobo's collision spheres in traj_gen.py there; parity unpinned)
+  HandTerm                     that cost as a term of the joint-space optimisers' loss: optimize(..., hand_term=…)
 All compute runs in libcdx.so (HIP, gfx950); importing works without a GPU, calling does not.
 """
 from .gpis import GPIS  # noqa: F401
@@ -55,7 +56,7 @@ from .robot_model import DifferentiableRobotModel  # noqa: F401
 from .ik import IKResult, solve_ik  # noqa: F401
 from .wrench import (MinWrenchResult, compute_margin, min_wrench, minimum_wrench_reward,  # noqa: F401
                      solve_minimum_wrench)
-from .hand import HandSpheres, hand_collision, penetration_report, spheres_from_urdf  # noqa: F401
+from .hand import HandSpheres, HandTerm, hand_collision, penetration_report, spheres_from_urdf  # noqa: F401
 from .torchsdf import PreparedMesh, compute_sdf, compute_sdf_with_faces, index_vertices_by_faces  # noqa: F401
 
 __version__ = "0.1.0"

@@ -238,6 +238,8 @@ _SIGS = {
     "cdx_hand_spheres": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxHand), _I64, _P, _P, _P, _P, _P, _P]),
     "cdx_hand_cost": (C.c_int, [C.POINTER(CdxHand), C.POINTER(CdxHandParams), _I64] + [_P] * 8),
     "cdx_hand_pullback": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxHand), _I64] + [_P] * 7),
+    "cdx_hand_term": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxHand), C.POINTER(CdxHandParams), _I64] + [_P] * 5 +
+                      [C.c_double, C.c_int32] + [_P] * 7),
     "cdx_force_eq_forward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
                                        _P]),
     "cdx_force_eq_backward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,

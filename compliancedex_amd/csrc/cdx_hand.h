@@ -451,6 +451,48 @@ inline void hand_pullback_row(const cdx_chain& c, const cdx_hand& H, const float
   }
 }
 
+// ------------------------------------------------------------------ the term (cdx_hand_term)
+// The cost and its pull-back as one weighted term of a caller's loss: x is what hand_cost_row and hand_pullback_row
+// give (g_centers never leaves the row's worker), and every output element is weight·x, or old + weight·x when the
+// term accumulates — two roundings, the product first (the file is compiled without contraction).  A bad row is NaN.
+CDX_HD double hand_term_out(double old, double x, double weight, bool accumulate, bool bad) {
+  if (bad) return (double)NAN;
+  const double wx = weight * x;
+  return accumulate ? old + wx : wx;
+}
+
+inline void hand_term_row(const cdx_chain& c, const cdx_hand& H, const cdx_hand_params& P, const float* poses,
+                          const double* centers, const double* dist, const double* gdist, const double* po,
+                          double weight, bool accumulate, double* loss, double* g_q, double* g_pp, double* g_po,
+                          double* depth, int32_t* worst) {
+  double gc[3 * CDX_MAX_SPHERES], cost, dp[3], gq[CDX_MAX_DOFS > 0 ? CDX_MAX_DOFS : 1], gpp[3], gpo[3];
+  int32_t wi[3];
+  hand_cost_row(H, P, centers, dist, gdist, &cost, dp, wi, gc);
+  hand_pullback_row(c, H, poses, gc, po, gq, gpp, gpo);
+  *loss = hand_term_out(accumulate ? *loss : 0.0, cost, weight, accumulate, !(cost == cost));
+  for (int k = 0; k < 3; ++k) {
+    if (depth) depth[k] = dp[k];
+    if (worst) worst[k] = wi[k];
+  }
+  for (int d = 0; d < c.n_dofs && g_q; ++d)
+    g_q[d] = hand_term_out(accumulate ? g_q[d] : 0.0, gq[d], weight, accumulate, !(gq[d] == gq[d]));
+  for (int i = 0; i < 3; ++i) {
+    if (g_pp) g_pp[i] = hand_term_out(accumulate ? g_pp[i] : 0.0, gpp[i], weight, accumulate, !(gpp[i] == gpp[i]));
+    if (g_po) g_po[i] = hand_term_out(accumulate ? g_po[i] : 0.0, gpo[i], weight, accumulate, !(gpo[i] == gpo[i]));
+  }
+}
+
+// Argument checks of cdx_hand_term after the chain, model and parameter codes (0 ≤ E checked by the caller).
+CDX_HD int hand_term_code(const cdx_chain* c, const cdx_hand* h, int64_t E, const float* poses, const double* centers,
+                          const double* dist, const double* gdist, double weight, int32_t accumulate,
+                          const double* loss, const double* g_q) {
+  if (h->n_bodies != c->n_bodies || E < 0 || E > 0x7fffffff || (dist == nullptr) != (gdist == nullptr)) return CDX_EINVAL;
+  if (!hand_finite(weight) || (accumulate != 0 && accumulate != 1)) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (!poses || !centers || !loss || (!g_q && c->n_dofs > 0)) return CDX_EINVAL;
+  return CDX_OK;
+}
+
 // Argument checks shared by the device entries and the host build (after the chain / model codes).
 CDX_HD int hand_params_code(const cdx_hand_params* p) {
   if (!p) return CDX_EINVAL;

@@ -17,6 +17,8 @@
 //                         a bit test on the body's path mask; masks and the spheres' bodies are kept in LDS and the lanes
 //                         walk the spheres together, each reading the same address).  No trigonometric library call: the palm's
 //                         sines and cosines are hand_sincos.
+//   hand_term_kernel      one wave per candidate: the two kernels above back to back with g_centers in LDS, every output
+//                         weight·x or old + weight·x (the optimisers' loops add the term into their own buffers).
 #include <hip/hip_runtime.h>
 
 #include <vector>
@@ -144,6 +146,107 @@ __global__ __launch_bounds__(CDX_HAND_LANES) void hand_pullback_kernel(cdx_chain
   }
 }
 
+// hand_cost_kernel, then hand_pullback_kernel, in one wave per candidate with g_centers kept in LDS (hand_term_kernel
+// in the head comment of cdx_hand.h's term section).  LDS: g_centers (6 KB), then one region the two phases use in
+// turn — the cost's centres, radii and tree (10.75 KB), the pull-back's c_h / Rpᵀ·g and tree (15 KB) — and the
+// pull-back's small tables: 22.5 KB.  The same cdx_hand.h pieces run in the same order as in the two kernels above, so
+// x has their bits; lane 0 owns loss (and depth / worst), lane d < n_dofs g_q[d], lane i < 3 g_palm_pos[i] and
+// g_palm_ori[i].
+constexpr int TERM_COST_WORDS = 3 * CDX_MAX_SPHERES + CDX_MAX_SPHERES + 4 * CDX_HAND_LANES + 2 * CDX_HAND_LANES;
+constexpr int TERM_PULL_WORDS = 6 * CDX_MAX_SPHERES + 6 * CDX_HAND_LANES;
+constexpr int TERM_WORDS = TERM_COST_WORDS > TERM_PULL_WORDS ? TERM_COST_WORDS : TERM_PULL_WORDS;
+
+__global__ __launch_bounds__(CDX_HAND_LANES) void hand_term_kernel(
+    cdx_chain c, cdx_hand H, cdx_hand_params P, const float* __restrict__ poses, const double* __restrict__ centers,
+    const double* __restrict__ dist, const double* __restrict__ gdist, const double* __restrict__ po, double weight,
+    int accumulate, double* loss, double* g_q, double* g_pp, double* g_po, double* __restrict__ depth,
+    int32_t* __restrict__ worst) {
+  __shared__ double gc[3 * CDX_MAX_SPHERES];
+  __shared__ double work[TERM_WORDS];
+  __shared__ double rot[36];
+  __shared__ uint32_t mask[CDX_MAX_BODIES];
+  __shared__ int32_t sb[CDX_MAX_SPHERES];
+  __shared__ int bad;
+  const int l = (int)threadIdx.x, S = H.n_spheres;
+  const int64_t e = blockIdx.x;
+  // ---- the cost (hand_cost_kernel)
+  double* cen = work;
+  double* rad = cen + 3 * CDX_MAX_SPHERES;
+  double* rv = rad + CDX_MAX_SPHERES;
+  int32_t* ri = reinterpret_cast<int32_t*>(rv + 4 * CDX_HAND_LANES);  // [3][64] in 2·64 doubles
+  for (int i = l; i < 3 * S; i += CDX_HAND_LANES) cen[i] = centers[e * S * 3 + i];
+  for (int i = l; i < S; i += CDX_HAND_LANES) rad[i] = H.radius[i];
+  if (l == 0) bad = 0;
+  __syncthreads();
+  const bool okc = cdx::hand_cost_lane(H, P, l, cen, rad, dist ? dist + e * S : nullptr,
+                                       gdist ? gdist + e * S * 3 : nullptr, gc, rv, ri);
+  if (!okc) bad = 1;
+  __syncthreads();
+  for (int off = CDX_HAND_LANES / 2; off; off >>= 1) {
+    if (l < off) cdx::hand_cost_join(rv, ri, l, off);
+    __syncthreads();
+  }
+  const bool cost_bad = bad != 0;
+  if (l == 0) {
+    double cost, dp[3];
+    int32_t wi[3];
+    cdx::hand_cost_finish(cost_bad, rv, ri, &cost, dp, wi);
+    loss[e] = cdx::hand_term_out(accumulate ? loss[e] : 0.0, cost, weight, accumulate != 0, cost_bad);
+    for (int k = 0; k < 3; ++k) {
+      if (depth) depth[3 * e + k] = dp[k];
+      if (worst) worst[3 * e + k] = wi[k];
+    }
+  }
+  if (cost_bad)
+    for (int i = l; i < 3 * S; i += CDX_HAND_LANES) gc[i] = (double)NAN;
+  // ---- the pull-back (hand_pullback_kernel)
+  const float* pe = poses + e * c.n_bodies * 12;
+  if (l == 0) {
+    const double ang[3] = {po ? po[3 * e] : 0.0, po ? po[3 * e + 1] : 0.0, po ? po[3 * e + 2] : 0.0};
+    double Rp[9], dRa[9], dRb[9], dRc[9];
+    cdx::hand_euler(ang, Rp, dRa, dRb, dRc);
+    bool ok = true;
+    for (int i = 0; i < 9; ++i) {
+      ok = ok && cdx::hand_finite(Rp[i]);
+      rot[i] = Rp[i];
+      rot[9 + i] = dRa[i];
+      rot[18 + i] = dRb[i];
+      rot[27 + i] = dRc[i];
+    }
+    if (!ok) bad = 1;
+  }
+  if (l < c.n_bodies) mask[l] = cdx::chain_path_mask(c, l);
+  __syncthreads();  // (the cost's region is free: its tree was read before this barrier)
+  double* st = work;
+  double* pv = st + 6 * CDX_MAX_SPHERES;
+  bool ok = cdx::hand_pull_lane(H, l, pe, gc, rot, rot + 9, rot + 18, rot + 27, st, sb, pv);
+  __syncthreads();
+  double gq = 0.0;
+  if (l < c.n_dofs) gq = cdx::hand_pull_dof(c, H, l, pe, mask, st, sb, &ok);
+  if (!ok) bad = 1;
+  for (int off = CDX_HAND_LANES / 2; off; off >>= 1) {
+    if (l < off)
+      for (int k = 0; k < 6; ++k) pv[k * CDX_HAND_LANES + l] += pv[k * CDX_HAND_LANES + l + off];
+    __syncthreads();
+  }
+  const bool row_bad = bad != 0;
+  const bool acc = accumulate != 0;
+  if (l < c.n_dofs && g_q) {
+    double* o = g_q + e * c.n_dofs + l;
+    *o = cdx::hand_term_out(acc ? *o : 0.0, gq, weight, acc, row_bad);
+  }
+  if (l < 3) {
+    if (g_pp) {
+      double* o = g_pp + 3 * e + l;
+      *o = cdx::hand_term_out(acc ? *o : 0.0, pv[l * CDX_HAND_LANES], weight, acc, row_bad);
+    }
+    if (g_po) {
+      double* o = g_po + 3 * e + l;
+      *o = cdx::hand_term_out(acc ? *o : 0.0, pv[(3 + l) * CDX_HAND_LANES], weight, acc, row_bad);
+    }
+  }
+}
+
 int launched() { return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH; }
 
 }  // namespace
@@ -216,6 +319,24 @@ int cdx_hand_pullback(const cdx_chain* chain, const cdx_hand* h, int64_t E, cons
   hipLaunchKernelGGL(hand_pullback_kernel, dim3((unsigned)E), dim3(CDX_HAND_LANES), 0,
                      reinterpret_cast<hipStream_t>(stream), *chain, *h, poses, g_centers, palm_ori, g_q, g_palm_pos,
                      g_palm_ori);
+  return launched();
+}
+
+int cdx_hand_term(const cdx_chain* chain, const cdx_hand* h, const cdx_hand_params* p, int64_t E, const float* poses,
+                  const double* centers, const double* dist, const double* gdist, const double* palm_ori, double weight,
+                  int32_t accumulate, double* loss, double* g_q, double* g_palm_pos, double* g_palm_ori, double* depth,
+                  int32_t* worst, cdx_stream_t stream) {
+  int rc = cdx::hand_chain_code(chain);
+  if (rc) return rc;
+  rc = cdx::hand_code(h);
+  if (rc) return rc;
+  rc = cdx::hand_params_code(p);
+  if (rc) return rc;
+  rc = cdx::hand_term_code(chain, h, E, poses, centers, dist, gdist, weight, accumulate, loss, g_q);
+  if (rc || E == 0) return rc;
+  hipLaunchKernelGGL(hand_term_kernel, dim3((unsigned)E), dim3(CDX_HAND_LANES), 0, reinterpret_cast<hipStream_t>(stream),
+                     *chain, *h, *p, poses, centers, dist, gdist, palm_ori, weight, (int)accumulate, loss, g_q,
+                     g_palm_pos, g_palm_ori, depth, worst);
   return launched();
 }
 

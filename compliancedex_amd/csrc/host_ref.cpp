@@ -474,6 +474,27 @@ int cdxh_hand_pullback(const cdx_chain* c, const cdx_hand* h, int64_t E, const f
   return CDX_OK;
 }
 
+int cdxh_hand_term(const cdx_chain* c, const cdx_hand* h, const cdx_hand_params* p, int64_t E, const float* poses,
+                   const double* centers, const double* dist, const double* gdist, const double* po, double weight,
+                   int32_t accumulate, double* loss, double* g_q, double* g_pp, double* g_po, double* depth,
+                   int32_t* worst) {
+  int rc = cdx::hand_chain_code(c);
+  if (rc) return rc;
+  rc = cdx::hand_code(h);
+  if (rc) return rc;
+  rc = cdx::hand_params_code(p);
+  if (rc) return rc;
+  rc = cdx::hand_term_code(c, h, E, poses, centers, dist, gdist, weight, accumulate, loss, g_q);
+  if (rc || E == 0) return rc;
+  const int64_t nb = c->n_bodies, S = h->n_spheres, D = c->n_dofs;
+  for (int64_t e = 0; e < E; ++e)
+    cdx::hand_term_row(*c, *h, *p, poses + e * nb * 12, centers + e * S * 3, dist ? dist + e * S : nullptr,
+                       gdist ? gdist + e * S * 3 : nullptr, po ? po + 3 * e : nullptr, weight, accumulate != 0, loss + e,
+                       g_q ? g_q + e * D : nullptr, g_pp ? g_pp + 3 * e : nullptr, g_po ? g_po + 3 * e : nullptr,
+                       depth ? depth + 3 * e : nullptr, worst ? worst + 3 * e : nullptr);
+  return CDX_OK;
+}
+
 size_t cdxh_hand_bytes(int32_t S, int32_t P) { return cdx::hand_bytes(S, P); }
 
 // cdx::hand_sincos on n angles.

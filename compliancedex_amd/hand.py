@@ -6,7 +6,9 @@ in a URDF's ``<collision>`` primitives), ``hand_collision`` scores their penetra
 signed-distance callable), of each other and of a floor for E candidates, with the gradient in joint space and palm
 pose, and ``penetration_report`` turns the same launch into a filter next to ``inverse_kinematics`` and ``min_wrench``.
 The reference leaves this to PyBullet (verify_pregrasp.py) and cuRobo's collision spheres (traj_gen.py); parity with
-either is not attempted.  Nothing in the optimisers calls it: the cost is a term a caller adds to a loss.
+either is not attempted.  ``HandTerm`` makes the cost a term of the joint-space optimisers' loss
+(``optimize(..., hand_term=…)``): through autograd in the eager loops, through cdx_hand_term — the cost and its pull-back
+in one accumulating launch — in the fused ones.
 """
 from __future__ import annotations
 
@@ -409,6 +411,119 @@ def hand_collision(hs, q, palm_pose=None, obj=None, floor_z=None, **margins_weig
         dist, gdist = dist.reshape(E, S), gdist.reshape(E, S, 3)
     cost, depth, worst = hs.cost(centers, dist, gdist, floor_z=floor_z, **margins_weights)
     return cost, dict(depth=depth, worst=worst, centers=centers.detach(), dist=dist)
+
+
+# ------------------------------------------------------------------ the term of the optimisers' losses
+class HandTerm:
+    """The whole-hand collision term of an optimiser's loss (``optimize(..., hand_term=HandTerm(hand, …))`` of
+    ProbabilisticGraspOptimizer, KinGPISGraspOptimizer, KinGraspOptimizer and WCKinGPISGraspOptimizer): per iteration
+    and candidate ``loss += weight · hand_collision(hand, q, palm_pose, obj, floor_z, margins and weights)``, formed
+    before the best-iterate comparison and the step, its gradient into the joint angles (and, in prob mode, the palm).
+    ``obj`` None: the optimiser's own object (its GPIS; KinGraspOptimizer's mesh).  A value type: the optimisers read
+    it and keep nothing in it."""
+
+    def __init__(self, hand, weight=1.0, m_obj=0.0, m_self=0.0, m_floor=0.0, w_obj=1.0, w_self=1.0, w_floor=1.0,
+                 floor_z=None, obj=None):
+        if not isinstance(hand, HandSpheres):
+            raise TypeError("HandTerm: hand must be a HandSpheres")
+        self.hand, self.weight = hand, float(weight)
+        self.m_obj, self.m_self, self.m_floor = float(m_obj), float(m_self), float(m_floor)
+        self.w_obj, self.w_self, self.w_floor = float(w_obj), float(w_self), float(w_floor)
+        self.floor_z = None if floor_z is None else float(floor_z)
+        self.obj = obj
+        if not all(math.isfinite(v) for v in (self.weight, *self.kwargs().values(), self.floor_z or 0.0)):
+            raise ValueError("HandTerm: weight, margins, weights and floor_z must be finite")
+
+    def key(self, own=None):
+        """What a captured loop depends on: the model, the numbers and the object's fitted state (``own``: the
+        optimiser's object, taken when ``obj`` is None)."""
+        obj = self.object(own)
+        st = obj.native_state() if hasattr(obj, "native_state") else obj
+        return (id(self.hand), self.weight, self.m_obj, self.m_self, self.m_floor, self.w_obj, self.w_self,
+                self.w_floor, self.floor_z, id(st))
+
+    def kwargs(self):
+        """hand_collision's margins and weights."""
+        return dict(m_obj=self.m_obj, m_self=self.m_self, m_floor=self.m_floor, w_obj=self.w_obj, w_self=self.w_self,
+                    w_floor=self.w_floor)
+
+    def params(self):
+        p = N.CdxHandParams()
+        p.m_obj, p.m_self, p.m_floor = self.m_obj, self.m_self, self.m_floor
+        p.w_obj, p.w_self, p.w_floor = self.w_obj, self.w_self, self.w_floor
+        p.floor_on = 0 if self.floor_z is None else 1
+        p.floor_z = 0.0 if self.floor_z is None else self.floor_z
+        return p
+
+    def object(self, own):
+        return own if self.obj is None else self.obj
+
+    def check(self, n_dofs, device):
+        if self.hand.desc.n_dofs != n_dofs:
+            raise ValueError(f"hand_term: the sphere model has {self.hand.desc.n_dofs} joints, the optimiser {n_dofs}")
+        if torch.device(self.hand.device).type != torch.device(device).type:
+            raise ValueError("hand_term: the sphere model and the optimiser must be on the same device")
+
+    def cost(self, q, palm_pose, own_obj):
+        """weight · hand_collision(...) [E] through autograd (the eager loops' term)."""
+        cost, _ = hand_collision(self.hand, q, palm_pose, self.object(own_obj), floor_z=self.floor_z, **self.kwargs())
+        return self.weight * cost
+
+    def report(self, q, palm_pose, own_obj):
+        """penetration_report at the returned joint angles and palm (device tensors, nothing read back)."""
+        return penetration_report(self.hand, q.detach().double(), None if palm_pose is None else palm_pose.detach().double(),
+                                  self.object(own_obj), floor_z=self.floor_z)
+
+
+def palm_rows(palm_offset, E):
+    """The palm pose [E, 6] float64 a Kin-style optimiser's forward_kinematics applies: its 3-entry ``palm_offset`` is a
+    position, the angles are zero."""
+    off = palm_offset.detach().to(torch.float64).reshape(-1)
+    if off.numel() != 3:
+        raise ValueError("hand_term needs a 3-entry palm_offset (the position forward_kinematics adds to the fingertips)")
+    return torch.cat([off, torch.zeros(3, dtype=torch.float64, device=off.device)]).expand(E, 6).contiguous()
+
+
+class TermLoop:
+    """The term inside a fused loop: its buffers, allocated once with the loop state, and per iteration
+    ``launch`` = cdx_hand_spheres on the current joint angles and palm, the GPIS mean and ∇mean at the S·E centres
+    (``query``; a loop whose own cdx_gpis_mean launch carries the centres passes ``dist`` / ``gdist`` views instead)
+    and cdx_hand_term with accumulate = 1 into the loop's loss and gradient buffers.  No allocation, no host sync."""
+
+    def __init__(self, term, E, gpis, device, centers=None):
+        from .gpis import GPIS
+        hs = term.hand
+        self.term, self.hs, self.E = term, hs, E
+        self.params = term.params()
+        f64 = dict(dtype=torch.float64, device=device)
+        S = hs.n_spheres
+        self.poses = torch.empty(E, hs.desc.n_bodies, 12, dtype=torch.float32, device=device)
+        self.centers = torch.empty(E * S, 3, **f64) if centers is None else centers
+        self.depth = torch.empty(E, 3, **f64)
+        self.worst = torch.empty(E, 3, dtype=torch.int32, device=device)
+        self.state = None
+        if centers is None:
+            obj = term.object(gpis)
+            if not isinstance(obj, GPIS):
+                raise ValueError("hand_term: a fused loop takes a GPIS object (use fused=False for a mesh or a callable)")
+            self.state = obj.native_state()
+            self.dist, self.gdist = torch.empty(E * S, **f64), torch.empty(E * S, 3, **f64)
+        hs.native()  # (the tables are built before any capture)
+
+    def place(self, lib, q, pp, po, stream):
+        N.check(lib.cdx_hand_spheres(C.byref(self.hs.desc), C.byref(self.hs.native()), self.E, N.ptr(q), N.ptr(pp),
+                                     N.ptr(po), N.ptr(self.poses), N.ptr(self.centers), stream), "cdx_hand_spheres")
+
+    def query(self, lib, stream):
+        N.check(lib.cdx_gpis_mean(self.state.desc, N.ptr(self.centers), self.E * self.hs.n_spheres, N.ptr(self.dist),
+                                  N.ptr(self.gdist), None, stream), "cdx_gpis_mean")
+
+    def add(self, lib, po, loss, g_q, g_pp, g_po, stream, dist=None, gdist=None):
+        N.check(lib.cdx_hand_term(C.byref(self.hs.desc), C.byref(self.hs.native()), C.byref(self.params), self.E,
+                                  N.ptr(self.poses), N.ptr(self.centers), N.ptr(self.dist if dist is None else dist),
+                                  N.ptr(self.gdist if gdist is None else gdist), N.ptr(po), self.term.weight, 1,
+                                  N.ptr(loss), N.ptr(g_q), N.ptr(g_pp), N.ptr(g_po), N.ptr(self.depth),
+                                  N.ptr(self.worst), stream), "cdx_hand_term")
 
 
 class _Report(dict):

@@ -258,7 +258,7 @@ class ProbabilisticGraspOptimizer:
 
     # -------------------------------------------------------------- optimize
     def optimize(self, init_joint_angles, target_pose, compliance, friction_mu, gpis, verbose=True,
-                 noise_tape=None, fused=True, init_palm=None, graph=False, step_hook=None):
+                 noise_tape=None, fused=True, init_palm=None, graph=False, step_hook=None, hand_term=None):
         """The reference's optimisation loop (:771-839).  ``fused=True`` (default): per iteration
         one cdx_closure + one cdx_optimizer_step (Adam, best iterate, clamps on device, no host
         sync); ``fused=False``: the same loop with torch.optim.Adam.  ``noise_tape``: optional
@@ -266,18 +266,29 @@ class ProbabilisticGraspOptimizer:
         palm poses instead of ``palm_offset`` (the annealing outer loop's proposals).  ``graph=True``
         (fused only): capture the whole loop once per (E, problem) as a hipGraph and replay it.
         ``step_hook(s, out, state)`` (fused, eager only): called after closure s with its output
-        buffers and the parameter buffers / Kabsch noise it ran on (tests: per-step checks)."""
+        buffers and the parameter buffers / Kabsch noise it ran on (tests: per-step checks).
+        ``hand_term`` (a ``HandTerm``): per iteration ``total_loss += weight · hand_collision(hand, q, [palm_poses,
+        palm_oris], obj or gpis, …)`` after the closure, before the best-iterate comparison and the step, its gradient
+        added to the joint angles' and the palm's; fused: cdx_hand_spheres, cdx_gpis_mean at the sphere centres and
+        cdx_hand_term (accumulating) between cdx_closure and cdx_optimizer_step, captured with the loop when
+        ``graph=True``.  ``last_hand_report`` is then ``penetration_report`` of the returned joints and palm."""
         if init_palm is not None:
             saved = self.palm_offset
             self.palm_offset = init_palm.detach().to(torch.float64)
             try:
                 return self.optimize(init_joint_angles, target_pose, compliance, friction_mu, gpis, verbose,
-                                     noise_tape, fused, graph=graph, step_hook=step_hook)
+                                     noise_tape, fused, graph=graph, step_hook=step_hook, hand_term=hand_term)
             finally:
                 self.palm_offset = saved
+        self.last_hand_report = None
+        if hand_term is not None:
+            hand_term.check(self._chain_desc.n_dofs, init_joint_angles.device)
         if fused:
-            return self._optimize_fused(init_joint_angles, target_pose, compliance, friction_mu, gpis, verbose,
-                                        noise_tape, graph, step_hook)
+            res = self._optimize_fused(init_joint_angles, target_pose, compliance, friction_mu, gpis, verbose,
+                                       noise_tape, graph, step_hook, hand_term)
+            if hand_term is not None:
+                self.last_hand_report = hand_term.report(res[0], res[3], gpis)
+            return res
         joint_angles = init_joint_angles.clone().requires_grad_(True)
         compliance = compliance.clone().requires_grad_(True)
         params_list = [{"params": joint_angles, "lr": 1e-3}, {"params": compliance, "lr": 0.2}]
@@ -304,6 +315,10 @@ class ProbabilisticGraspOptimizer:
             noise = noise_tape[s] if noise_tape is not None else None
             self.closure(joint_angles, compliance, target_pose, palm_poses, palm_oris, friction_mu, gpis, num_envs,
                          kabsch_noise=noise)
+            if hand_term is not None:  # one more term, into total_loss and the leaf gradients
+                term = hand_term.cost(joint_angles, torch.cat([palm_poses, palm_oris], 1), gpis)
+                term.sum().backward()
+                self.total_loss = self.total_loss + term.detach()
             with torch.no_grad():
                 update_flag = self.total_loss < opt_value
                 if s > 20:  # (:823) — masked updates need no host sync
@@ -322,6 +337,8 @@ class ProbabilisticGraspOptimizer:
         if verbose:
             print("Margin:", opt_margin)
         self.last_screen_report = self.screen_report(gpis, num_envs, friction_mu) if self.num_iters else None
+        if hand_term is not None:
+            self.last_hand_report = hand_term.report(opt_joint_angle, opt_palm_poses, gpis)
         return opt_joint_angle, opt_compliance, opt_target_pose, opt_palm_poses, opt_margin
 
     def adam_config(self):
@@ -342,7 +359,7 @@ class ProbabilisticGraspOptimizer:
         return cfg
 
     def _optimize_fused(self, init_joint_angles, target_pose, compliance, friction_mu, gpis, verbose, noise_tape,
-                        graph=False, step_hook=None):
+                        graph=False, step_hook=None, hand_term=None):
         """Device-resident loop: per iteration one cdx_closure + one cdx_optimizer_step, with the
         Kabsch-noise key and Adam's step count in device loop counters (cdx_loop), so the loop is
         the same whether launched eagerly or replayed from a captured hipGraph (``graph=True``;
@@ -353,7 +370,7 @@ class ProbabilisticGraspOptimizer:
         fp64 path's; the loop's cumulative record is read once at the end (one host sync) into
         ``last_screen_report``, and ``screen_repairs`` counts the repaired closures."""
         res = self._optimize_fused_once(init_joint_angles, target_pose, compliance, friction_mu, gpis, verbose,
-                                        noise_tape, graph, step_hook)
+                                        noise_tape, graph, step_hook, hand_term)
         rep = self.screen_report(gpis, init_joint_angles.shape[0], friction_mu)
         self.last_screen_report = rep
         if rep is not None and rep["cum_repairs"]:
@@ -363,7 +380,7 @@ class ProbabilisticGraspOptimizer:
         return res
 
     def _optimize_fused_once(self, init_joint_angles, target_pose, compliance, friction_mu, gpis, verbose,
-                             noise_tape, graph=False, step_hook=None):
+                             noise_tape, graph=False, step_hook=None, hand_term=None):
         lib = N.load()
         p = self.problem(gpis, friction_mu)
         E = init_joint_angles.shape[0]
@@ -378,6 +395,8 @@ class ProbabilisticGraspOptimizer:
         # holds the GPIS state it captured (so neither is freed or reused while the entry lives;
         # the id() in the key cannot be recycled while the entry references the object).
         key = (E, id(self._problem_state), float(friction_mu), self.num_iters)
+        if hand_term is not None:  # (the entry's TermLoop holds the term, its model and its object's state)
+            key += hand_term.key(gpis)
         cache = self._graphs.get(key) if graph else None
         if cache is None:
             z = torch.zeros
@@ -394,6 +413,9 @@ class ProbabilisticGraspOptimizer:
                 cache[k] = z(E, 3, **f64)
             cache.update(opt_value=z(E, **f64), opt_q=z(E, D, **f64), opt_comp=z(E, T, **f64),
                          opt_target=z(E, T, 3, **f64), opt_palm=z(E, 6, **f64))
+            if hand_term is not None:
+                from .hand import TermLoop
+                cache["term"] = TermLoop(hand_term, E, gpis, dev)
             if graph:
                 cache["ws"] = torch.empty(lib.cdx_closure_workspace(p, E), dtype=torch.uint8, device=dev)
                 cache["state"], cache["problem"] = self._problem_state, p
@@ -431,6 +453,7 @@ class ProbabilisticGraspOptimizer:
                                total_loss=out["total_loss"].data_ptr(), total_margin=out["total_margin"].data_ptr(),
                                loop=c["loop"].data_ptr(), **{k: v.data_ptr() for k, v in st.items()})
         cfg = self.adam_config()
+        term = c.get("term")
 
         def run_loop():
             stream = N.stream_ptr(dev)
@@ -442,6 +465,11 @@ class ProbabilisticGraspOptimizer:
                         noise = noise_tape[s].to(**f64).contiguous()
                     self._closure_into(p, c["q"], c["comp"], c["target"], c["pp"], c["po"], noise, out, seed=0,
                                        ws=c.get("ws"))
+                    if term is not None:  # total_loss, g_q and the palm gradients += weight · the hand's term
+                        term.place(lib, c["q"], c["pp"], c["po"], stream)
+                        term.query(lib, stream)
+                        term.add(lib, c["po"], out["total_loss"], out["g_q"], out["g_palm_pos"], out["g_palm_ori"],
+                                 stream)
                     if step_hook is not None:
                         step_hook(s, out, dict(q=c["q"], comp=c["comp"], target=c["target"], pp=c["pp"],
                                                po=c["po"], noise=noise))

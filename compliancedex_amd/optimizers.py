@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import _native as N
+from . import hand as _hand
 from .force_eq import force_eq_descriptor, force_eq_reward
 from .optimizer import EE_OFFSETS, FINGERTIP_LB, FINGERTIP_UB, WRIST_OFFSET
 from .robot_model import DifferentiableRobotModel
@@ -303,17 +304,28 @@ class KinGraspOptimizer:
         return (tips.view(-1, 3) + self.palm_offset).view(-1, 3)
 
     def optimize(self, joint_angles, target_pose, compliance, friction_mu, object_mesh, verbose=True,
-                 kabsch_noise=None, trace_rows=False, fused=True):
+                 kabsch_noise=None, trace_rows=False, fused=True, hand_term=None):
         """``trace_rows``: also keep every iteration's per-candidate loss in ``loss_rows`` (device).
+        ``hand_term`` (a ``HandTerm``, ``fused=False`` only: the fused loop has no mesh query at the sphere centres):
+        per iteration ``l += weight · hand_collision(hand, q, palm, obj or the mesh, …)`` with the palm at
+        ``palm_offset`` and zero angles; ``last_hand_report`` is ``penetration_report`` of the returned joints.
         ``fused`` (default): per iteration the three TorchSDF queries on prepared meshes, ONE cost-and-backward
         kernel (cdx_kin_cost: force_eq_reward, the six cost terms and the backward through them, TorchSDF and
         the FK chain) and ONE step kernel (cdx_kin_step: Adam, the best iterate, the next fingertips' FK) — no
         autograd graph, no host sync; ``fused=False``: the same loop through the autograd drop-ins
         (compute_sdf, force_eq_reward, the FK module), torch tensor ops and torch.optim.Adam, as the reference
         writes it."""
+        if fused and hand_term is not None:
+            raise ValueError("KinGraspOptimizer: hand_term needs fused=False (the fused loop has no mesh query at the "
+                             "sphere centres)")
         self.loss_history = []
         self.loss_rows = []
+        self.last_hand_report = None
         faces = _face_vertices(object_mesh, self.device)
+        if hand_term is not None:
+            hand_term.check(joint_angles.shape[1], self.device)
+            palm = _hand.palm_rows(self.palm_offset, joint_angles.shape[0])
+            term_obj = PreparedMesh(faces) if hand_term.obj is None else None
         object_mesh.scale(0.9, center=[0, 0, 0])
         faces_deflate = _face_vertices(object_mesh, self.device)
         E, T = target_pose.shape[0], target_pose.shape[1]
@@ -346,6 +358,8 @@ class KinGraspOptimizer:
             # for E = 1; the [E, T] sign is what that line means and what it computes at E = 1
             tar_dist_cost = 10 * (tar_sign.view(E, T) * torch.sqrt(tar_dist).view(E, T)).sum(dim=1)
             l = c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0) + ref_cost
+            if hand_term is not None:
+                l = l + hand_term.cost(joint_angles, palm, term_obj).to(l.dtype)
             l.sum().backward()
             self.loss_history.append(l.detach().sum())  # device scalar, no sync
             if trace_rows:
@@ -357,6 +371,8 @@ class KinGraspOptimizer:
         if verbose:
             print(best.margin, best.normal)
         self.best_loss = best.value
+        if hand_term is not None:
+            self.last_hand_report = hand_term.report(best.params["q"], palm, term_obj)
         return best.params["q"], best.params["comp"], best.params["target"], best.flag()
 
     def _optimize_fused(self, joint_angles, target_pose, compliance, friction_mu, faces, faces_deflate, lrs, verbose,
@@ -641,6 +657,7 @@ def _gpis_mode_run(self, mode, chain, prm, cfg, st, verbose, kabsch_noise, trace
     E, T = st.E, st.T
     stream = N.stream_ptr(dev)
     loss = None
+    term = getattr(st, "term", None)  # (KinGPIS with a hand term: cost, term, step)
     if self.loop_events:
         self.loop_events[0].record()
     for s in range(self.num_iters):
@@ -649,12 +666,16 @@ def _gpis_mode_run(self, mode, chain, prm, cfg, st, verbose, kabsch_noise, trace
         self._seed += 1
         loss = st.loss_slot(s, self.num_iters)
         st.queries(lib, stream)
-        if not verbose and not split_step:  # cost, backward and step in one launch (four fingertips)
+        if not verbose and not split_step and term is None:  # cost, backward and step in one launch (four fingertips)
             N.check(lib.cdx_gpis_mode_iteration(chain, prm, cfg, st.buffers, E, T, N.ptr(nz), self._seed, s, stream),
                     "cdx_gpis_mode_iteration")
         else:
             N.check(lib.cdx_gpis_mode_cost(chain, prm, st.buffers, E, T, N.ptr(nz), self._seed, s, stream),
                     "cdx_gpis_mode_cost")
+            if term is not None:  # loss and g_q += weight · the hand's term at the current joints
+                term.place(lib, st.pose, st.term_palm, None, stream)
+                term.query(lib, stream)
+                term.add(lib, None, loss, st.g[0], None, None, stream)
             if verbose:
                 print("Loss:", float(loss.sum()))
             N.check(lib.cdx_gpis_mode_step(chain, prm, cfg, st.buffers, E, T, s, 0, stream), "cdx_gpis_mode_step")
@@ -806,17 +827,28 @@ class KinGPISGraspOptimizer:
         return (tips.view(-1, 3) + self.palm_offset).view(-1, 3)
 
     def optimize(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose=True, kabsch_noise=None,
-                 fused=False, trace_rows=False, split_step=False):
+                 fused=False, trace_rows=False, split_step=False, hand_term=None):
         """``fused`` / ``trace_rows`` / ``split_step``: as GPISGraspOptimizer.optimize; the fused step also clamps the
         targets (optimised or not, :505-507) and computes the next iteration's fingertips, so the loop has one FK
-        launch in all (iteration 0's)."""
+        launch in all (iteration 0's).  ``hand_term`` (a ``HandTerm``): per iteration ``l += weight ·
+        hand_collision(hand, q, palm, obj or gpis, …)`` with the palm at ``palm_offset`` and zero angles, before the
+        best-iterate comparison and the step; fused: cdx_gpis_mode_cost, then cdx_hand_spheres, cdx_gpis_mean at the
+        sphere centres and cdx_hand_term (accumulating into the loss and the joint gradient), then cdx_gpis_mode_step.
+        ``last_hand_report`` is then ``penetration_report`` of the returned joints."""
         self.loss_rows = []
+        self.last_hand_report = None
+        if hand_term is not None:
+            hand_term.check(joint_angles.shape[1], self.device)
+            palm = _hand.palm_rows(self.palm_offset, joint_angles.shape[0])
         if fused:
             self.loss_history = []
             _gpis_mode_inputs("KinGPISGraspOptimizer", self.device, joint_angles=joint_angles, target_pose=target_pose,
                               compliance=compliance)
-            return self._optimize_fused(joint_angles, target_pose, compliance, friction_mu, gpis, verbose, kabsch_noise,
-                                        trace_rows, split_step)
+            res = self._optimize_fused(joint_angles, target_pose, compliance, friction_mu, gpis, verbose, kabsch_noise,
+                                       trace_rows, split_step, hand_term)
+            if hand_term is not None:
+                self.last_hand_report = hand_term.report(res[0], palm, gpis)
+            return res
         joint_angles = joint_angles.clone().requires_grad_(True)
         self.loss_history = []
         compliance = compliance.clone().requires_grad_(True)
@@ -847,6 +879,8 @@ class KinGPISGraspOptimizer:
             tar_dist_cost = 10 * tar_dist.view(E, T).sum(dim=1)
             l = (c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0) + ref_cost +
                  variance_cost.max(dim=1)[0])
+            if hand_term is not None:
+                l = l + hand_term.cost(joint_angles, palm, gpis).to(l.dtype)
             l.sum().backward()
             self.loss_history.append(l.detach().sum())  # device scalar, no sync
             if trace_rows:
@@ -863,10 +897,12 @@ class KinGPISGraspOptimizer:
         if verbose:
             print(best.margin, best.normal)
         self.best_loss = best.value
+        if hand_term is not None:
+            self.last_hand_report = hand_term.report(best.params["q"], palm, gpis)
         return best.params["q"], best.params["comp"], best.params["target"], best.flag()
 
     def _optimize_fused(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose, kabsch_noise,
-                        trace_rows, split_step):
+                        trace_rows, split_step, hand_term=None):
         lib = N.load()
         dev = self.device
         E, T = target_pose.shape[0], target_pose.shape[1]
@@ -885,6 +921,9 @@ class KinGPISGraspOptimizer:
         N.check(lib.cdx_fk_forward(chain, N.ptr(st.pose.float().contiguous()), E, N.ptr(tips32), None, N.stream_ptr(dev)),
                 "cdx_fk_forward")
         st.tips.copy_(tips32.double() + self.palm_offset.to(torch.float64))
+        if hand_term is not None:  # the term's buffers, with the loop state; the palm: palm_offset, no rotation
+            st.term = _hand.TermLoop(hand_term, E, gpis, dev)
+            st.term_palm = _hand.palm_rows(self.palm_offset, E)[:, :3].contiguous()
         return _gpis_mode_run(self, 1, chain, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step)
 
 
@@ -921,11 +960,17 @@ class WCKinGPISGraspOptimizer:
                                                           offsets=self.ee_link_offsets, recursive=True)[0]
         return (tips.view(-1, 3) + self.palm_offset).view(-1, 3)
 
-    def optimize(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose=True, trace_rows=False):
+    def optimize(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose=True, trace_rows=False,
+                 hand_term=None):
         """→ (q, compliance, target, flag).  The returned target of a candidate is ``tip + forces / compliance`` of
         its best iteration (:603): the springs that would exert the certified forces.  ``loss_rows`` (with
-        ``trace_rows``) keeps the per-candidate losses, ``wrench_rows`` the min_wrench result of every iteration."""
+        ``trace_rows``) keeps the per-candidate losses, ``wrench_rows`` the min_wrench result of every iteration.
+        ``hand_term`` (a ``HandTerm``): as KinGPISGraspOptimizer.optimize's, through autograd."""
         from .wrench import min_wrench
+        self.last_hand_report = None
+        if hand_term is not None:
+            hand_term.check(joint_angles.shape[1], self.device)
+            palm = _hand.palm_rows(self.palm_offset, joint_angles.shape[0])
         joint_angles = joint_angles.clone().requires_grad_(True)
         compliance = compliance.clone().requires_grad_(True)
         target_pose = target_pose.clone()
@@ -953,6 +998,8 @@ class WCKinGPISGraspOptimizer:
             tar_dist_cost = 10 * tar_dist.view(E, T).sum(dim=1)
             l = (c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0) + ref_cost +
                  variance_cost.max(dim=1)[0])
+            if hand_term is not None:
+                l = l + hand_term.cost(joint_angles, palm, gpis).to(l.dtype)
             l.sum().backward()
             self.loss_history.append(l.detach().sum())  # device scalar, no sync
             if trace_rows:
@@ -971,4 +1018,6 @@ class WCKinGPISGraspOptimizer:
         if verbose:
             print(best.margin, best.normal)
         self.best_loss = best.value
+        if hand_term is not None:
+            self.last_hand_report = hand_term.report(best.params["q"], palm, gpis)
         return best.params["q"], best.params["comp"], best.params["target"], best.flag()

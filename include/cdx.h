@@ -782,6 +782,13 @@ int cdx_collision_loss(const cdx_collision* c, int64_t E, const double* q, const
  * cdx_hand_pullback: poses (cdx_hand_spheres' own), g_centers [E*S*3], palm_ori [E*3] (nullable: zero; the palm
  *   position does not enter) → g_q [E*n_dofs], g_palm_pos [E*3], g_palm_ori [E*3] f64: the true derivative of Σ
  *   g_centers·centers (a sign-0 joint gets 0).
+ * cdx_hand_term: cdx_hand_cost then cdx_hand_pullback in one launch, as a weighted term of a caller's loss (one wave
+ *   per candidate, g_centers stays in LDS): poses and centers as cdx_hand_spheres wrote them, dist / gdist (both or
+ *   neither), palm_ori (nullable: zero) → loss [E], g_q [E*n_dofs], g_palm_pos [E*3], g_palm_ori [E*3] (each of the two
+ *   nullable: not wanted), every element weight·x with accumulate = 0 and old + weight·x with accumulate = 1, x being
+ *   the bits the two entries give (the product and the sum round separately; one lane owns each element, no atomics);
+ *   depth [E*3], worst [E*3] (each nullable) as cdx_hand_cost's, neither weighted nor accumulated.  weight finite,
+ *   accumulate 0 or 1.  Nothing is allocated or read back.
  * A row with a non-finite input is NaN in its own float outputs (worst −1) and touches no other row.
  * Return codes: a null or malformed chain, or a body more than CDX_MAX_DEPTH levels deep → CDX_ECHAIN; sizes over the
  *   limits, a null required pointer, a model whose n_bodies is not the chain's, non-finite parameters, E < 0 →
@@ -823,6 +830,10 @@ int cdx_hand_cost(const cdx_hand* h, const cdx_hand_params* p, int64_t E, const 
                   cdx_stream_t stream);
 int cdx_hand_pullback(const cdx_chain* chain, const cdx_hand* h, int64_t E, const float* poses, const double* g_centers,
                       const double* palm_ori, double* g_q, double* g_palm_pos, double* g_palm_ori, cdx_stream_t stream);
+int cdx_hand_term(const cdx_chain* chain, const cdx_hand* h, const cdx_hand_params* p, int64_t E, const float* poses,
+                  const double* centers, const double* dist, const double* gdist, const double* palm_ori, double weight,
+                  int32_t accumulate, double* loss, double* g_q, double* g_palm_pos, double* g_palm_ori, double* depth,
+                  int32_t* worst, cdx_stream_t stream);
 /* sizeof(cdx_hand), sizeof(cdx_hand_params). */
 void cdx_hand_abi_sizes(size_t* out2);
 
