@@ -17,8 +17,6 @@ the per-candidate cost glue as device tensor ops and torch's own RMSprop / Adam,
 """
 from __future__ import annotations
 
-import os
-
 import numpy as np
 import torch
 
@@ -92,7 +90,7 @@ def _sdf_normal(points, faces, faces_deflate):
 
 
 class _Best:
-    """Best-iterate tracking of the four loops without host syncs."""
+    """Best-iterate tracking of the eager loops without host syncs."""
 
     def __init__(self, l0_dtype, E, T, device, **params):
         self.value = torch.full((E,), float("inf"), dtype=l0_dtype, device=device)
@@ -117,6 +115,119 @@ class _Best:
 
 def _noise(tape, s):
     return None if tape is None else tape[s]
+
+
+def _tip_box(tip_bounding_box, device):
+    """The fingertip box (lower, upper) as two [·, 3] device tensors."""
+    return [torch.tensor(tip_bounding_box[0]).to(device).view(-1, 3),
+            torch.tensor(tip_bounding_box[1]).to(device).view(-1, 3)]
+
+
+def _set_box(cfg, box, T, dtype):
+    """Copy the fingertip box into a native optimiser struct's ``box_lb`` / ``box_ub`` (3·T values each)."""
+    lb = box[0].to(dtype).expand(T, 3).reshape(-1).cpu().tolist()
+    ub = box[1].to(dtype).expand(T, 3).reshape(-1).cpu().tolist()
+    for i in range(3 * T):
+        cfg.box_lb[i], cfg.box_ub[i] = lb[i], ub[i]
+
+
+def _set_ref_palm(ref_dst, palm_dst, ref_q, palm_offset, dtype):
+    """Copy ``ref_q`` into ``ref_dst.ref_q`` and ``palm_offset`` into ``palm_dst.palm_offset`` (native structs),
+    rounded to ``dtype`` first."""
+    for i, v in enumerate(ref_q.to(dtype).tolist()):
+        ref_dst.ref_q[i] = v
+    off = palm_offset.to(dtype).cpu().tolist()
+    for i in range(3):
+        palm_dst.palm_offset[i] = off[i]
+
+
+def _eager_loop(opt, optim_cls, best_dtype, pose, target, comp, lrs, optimize_target, cost, clamp=None, hand=None,
+                verbose=True, trace_rows=False):
+    """The autograd loop of the five optimisers, as the reference writes it, on clones of ``pose`` and ``comp`` (and
+    of ``target`` when it is optimised: a frozen target is no param group and stays the caller's tensor).  ``lrs``:
+    the learning rates of pose, target and compliance.  Per iteration ``cost(s, pose, target, comp)`` →
+    ``(l, margin, normal, best_target, extras)``: the per-candidate loss, what ``_Best`` keeps with it, the target to
+    store for an improved candidate, and a callable giving what ``verbose`` prints after the loss (evaluated only
+    then: nothing syncs with ``verbose=False``).  ``hand``: ``(term, palm, field)`` — ``l += term.cost(pose, palm,
+    field)`` before the backward, and ``last_hand_report`` from the returned pose.  ``clamp(pose, target, comp)`` runs
+    under no_grad after every step.  ``loop_events``, when set, are recorded around the iterations."""
+    pose = pose.clone().requires_grad_(True)
+    comp = comp.clone().requires_grad_(True)
+    groups = [{"params": pose, "lr": lrs[0]}, {"params": comp, "lr": lrs[2]}]
+    if optimize_target:
+        target = target.clone().requires_grad_(True)
+        groups.insert(1, {"params": target, "lr": lrs[1]})
+    optim = optim_cls(groups)
+    best = _Best(best_dtype, target.shape[0], target.shape[1], opt.device, pose=pose, comp=comp, target=target)
+    if opt.loop_events:
+        opt.loop_events[0].record()
+    for s in range(opt.num_iters):
+        optim.zero_grad()
+        l, margin, normal, best_target, extras = cost(s, pose, target, comp)
+        if hand is not None:
+            l = l + hand[0].cost(pose, hand[1], hand[2]).to(l.dtype)
+        l.sum().backward()
+        opt.loss_history.append(l.detach().sum())  # device scalar, no sync
+        if trace_rows:
+            opt.loss_rows.append(l.detach().clone())
+        if verbose:
+            print("Loss:", float(l.sum()), *extras())
+        best.update(l, margin, normal, pose=pose, comp=comp, target=best_target)
+        optim.step()
+        if clamp is not None:
+            with torch.no_grad():
+                clamp(pose, target, comp)
+    if opt.loop_events:
+        opt.loop_events[1].record()
+    if verbose:
+        print(best.margin, best.normal)
+    opt.best_loss = best.value
+    if hand is not None:
+        opt.last_hand_report = hand[0].report(best.params["pose"], hand[1], hand[2])
+    return best.params["pose"], best.params["comp"], best.params["target"], best.flag()
+
+
+def _fused_loop(opt, st, queries, iterate, cost, step, split_step=False, term=None, verbose=True, kabsch_noise=None,
+                trace_rows=False, extras=()):
+    """The fused loops' driver on the loop state ``st``: no autograd graph and, without ``verbose``, no host sync.
+    Per iteration ``qr = queries()`` (the distance queries' launches), then ONE launch ``iterate(qr, noise, seed, s)``
+    (cost, backward and step) or — with ``split_step`` True, ``verbose`` (the loss printed before the step, with
+    ``extras`` after it, as the reference prints) or a ``term`` — ``cost(qr, noise, seed, s, loss)``, ``term(loss)``
+    and ``step(s, 0)``; ``split_step="alt"``: even iterations take the two launches, odd ones the one.  ``step(iters,
+    1)`` finalises.  → the last iteration's loss row (None without iterations)."""
+    dev, iters = opt.device, opt.num_iters
+    alt = split_step == "alt"
+    two = bool(verbose or term is not None or (split_step and not alt))
+    loss = None
+    if opt.loop_events:
+        opt.loop_events[0].record()
+    for s in range(iters):
+        nz = _noise(kabsch_noise, s)
+        nz = None if nz is None else nz.detach().to(device=dev, dtype=torch.float64).contiguous()
+        opt._seed += 1
+        loss = st.loss_slot(s, iters)
+        qr = queries()
+        if two or (alt and s % 2 == 0):
+            cost(qr, N.ptr(nz), opt._seed, s, loss)
+            if term is not None:
+                term(loss)
+            if verbose:
+                print("Loss:", float(loss.sum()), *extras)
+            step(s, 0)
+        else:
+            iterate(qr, N.ptr(nz), opt._seed, s)
+        if st.hist is None:
+            opt.loss_history.append(loss.sum())  # device scalar, no sync
+        if trace_rows:
+            opt.loss_rows.append(loss.clone())
+    step(iters, 1)
+    st.loss_sums(opt.loss_history)
+    if opt.loop_events:
+        opt.loop_events[1].record()
+    if verbose:
+        print(st.opt_margin, st.opt_normal)
+    opt.best_loss = st.opt_value
+    return loss
 
 
 def kin_fk_cache_view(fk_state, max_depth):
@@ -148,33 +259,67 @@ def kin_fk_cache_qcheck(pose):
     return want.reshape(4 * E, -1)
 
 
-class _FusedLoop:
+class _LoopState:
+    """What the fused loops' device states share: the native buffer struct, the per-call loss history and the best
+    iterate's return tuple."""
+
+    hist = None
+
+    def fill(self, b, pairs):
+        """Set the native buffer struct ``b``'s fields from (name, tensor or None) pairs; it becomes ``buffers``."""
+        for name, t in pairs:
+            setattr(b, name, N.ptr(t))
+        self.buffers = b
+
+    def loss_slot(self, s, iters):
+        """Iteration s's loss vector: a row of a per-call [iters, E] history (the per-iteration sums are taken in one
+        reduction after the loop, not one per iteration), or the single buffer when the history would pass 1 GiB."""
+        E = self.loss.shape[0]
+        if s == 0:
+            self.hist = (torch.empty(iters, E, dtype=torch.float64, device=self.loss.device)
+                         if iters * E * 8 <= (1 << 30) else None)
+        row = self.hist[s] if self.hist is not None else self.loss
+        self.buffers.loss = N.ptr(row)
+        return row
+
+    def loss_sums(self, history):
+        """Append the loop's per-iteration loss sums (device scalars) to ``history``."""
+        if self.hist is not None:
+            history.extend(self.hist.sum(dim=1).unbind(0))
+
+    def best(self):
+        return self.opt[0], self.opt[2], self.opt[1], (self.opt_margin > 0.0).all()
+
+
+class _FusedLoop(_LoopState):
     """Device state of a fused Kin / SDF loop: the two prepared meshes, cdx_kin_cost's outputs (margin / normal
     in two alternating slots), the optimiser moments, the best iterate and the cdx_kin_step buffers.  Per
     iteration the loop is three TorchSDF queries, cdx_kin_cost and cdx_kin_step (optimiser, best iterate,
     clamps and — Kin — the next fingertips' FK): no autograd graph, no host sync."""
 
-    def __init__(self, E, T, pose, target, comp, faces, faces_deflate, dev):
+    def __init__(self, E, T, pose, target, comp, faces, faces_deflate, dev, concurrent=3, resort=16):
+        """``concurrent``: how the iteration's three queries are launched — 3 (default) in one launch
+        (cdx_sdf_query_batch), 1 on three streams (also what 3 falls back to for a mesh with NaN-capable faces), 0 one
+        after the other on the caller's stream (the sequential oracle of the tests).  ``resort``: iterations per
+        point sort."""
+        if concurrent not in (0, 1, 3):
+            raise ValueError(f"_FusedLoop: concurrent must be 0, 1 or 3, got {concurrent!r}")
         f32 = dict(dtype=torch.float32, device=dev)
         self.mesh, self.mesh_def = PreparedMesh(faces), PreparedMesh(faces_deflate)
         self.ws_tips, self.ws_tgt = QueryWorkspace(), QueryWorkspace()
         # the batched launch's schedule (heaviest point groups of the last iteration first; CDX_SDF_SCHED=0: none)
         self.sched = BatchSchedule()
         self.iteration = 0
-        self.hist = None
         # iterations per point sort: 16 (A/B with the batched launch's schedule, profiles/r05ba_config4_resort_sched_ab.jsonl:
         # 4 / 8 / 16 / never = 0.327 / 0.316 / 0.316 / 0.311 ms around the mesh, 0.461 / 0.445 / 0.442 / 0.469 far)
-        self.resort = max(1, int(os.environ.get("CDX_SDF_RESORT", "16")))
-        # the three queries' outputs (dist, sign, normals, clst), and the two side streams the second and third
-        # query run on beside the first (CDX_SDF_CONCURRENT=0: all three on the caller's stream)
+        self.resort = max(1, int(resort))
+        # the three queries' outputs (dist, sign, normals, clst)
         self.q_out = [(torch.empty(E * T, **f32), torch.empty(E * T, dtype=torch.int32, device=dev),
                        torch.empty(E * T, 3, **f32), torch.empty(E * T, 3, **f32)) for _ in range(3)]
-        # 3 (default): the three queries in one launch (cdx_sdf_query_batch); 1: on three streams; 2: the targets' on
-        # a side stream only; 0: one after the other (A/B switch CDX_SDF_CONCURRENT)
-        self.concurrent = int(os.environ.get("CDX_SDF_CONCURRENT", "3"))
+        self.concurrent = concurrent
         if self.concurrent == 3 and not (self.mesh.kind == N.SDF_MESH_CULLED and self.mesh_def.kind == N.SDF_MESH_CULLED):
             self.concurrent = 1  # (a mesh with NaN-capable faces: the batch launch has no exact path)
-        if self.concurrent in (1, 2):
+        if self.concurrent == 1:  # the two side streams the second and third query run on beside the first
             self.side = [torch.cuda.Stream(device=dev) for _ in range(2)]
             self.ev = [torch.cuda.Event() for _ in range(4)]
         self.pose, self.target, self.comp = pose, target, comp
@@ -191,16 +336,14 @@ class _FusedLoop:
         self.any = torch.zeros(3, dtype=torch.int32, device=dev)
         self.tips = torch.empty(E * T, 3, **f32)
         b = N.CdxKinOptBuffers()
-        for name, t in (("pose", pose), ("target", target), ("comp", comp), ("g_pose", self.g[0]),
-                        ("g_target", self.g[1]), ("g_comp", self.g[2]), ("m_pose", self.m[0]), ("v_pose", self.v[0]),
-                        ("m_target", self.m[1]), ("v_target", self.v[1]), ("m_comp", self.m[2]), ("v_comp", self.v[2]),
-                        ("loss", self.loss), ("opt_value", self.opt_value), ("opt_margin", self.opt_margin),
-                        ("opt_normal", self.opt_normal), ("opt_pose", self.opt[0]), ("opt_target", self.opt[1]),
-                        ("opt_comp", self.opt[2]), ("any", self.any)):
-            setattr(b, name, N.ptr(t))
+        self.fill(b, (("pose", pose), ("target", target), ("comp", comp), ("g_pose", self.g[0]),
+                      ("g_target", self.g[1]), ("g_comp", self.g[2]), ("m_pose", self.m[0]), ("v_pose", self.v[0]),
+                      ("m_target", self.m[1]), ("v_target", self.v[1]), ("m_comp", self.m[2]), ("v_comp", self.v[2]),
+                      ("loss", self.loss), ("opt_value", self.opt_value), ("opt_margin", self.opt_margin),
+                      ("opt_normal", self.opt_normal), ("opt_pose", self.opt[0]), ("opt_target", self.opt[1]),
+                      ("opt_comp", self.opt[2]), ("any", self.any)))
         for i in range(2):
             b.margin[i], b.normal[i] = N.ptr(self.margin[i]), N.ptr(self.normal[i])
-        self.buffers = b
 
     def queries(self, tips, target):
         """The iteration's three TorchSDF calls (:186-188).  The fingertips are sorted once for both meshes, and the
@@ -243,41 +386,82 @@ class _FusedLoop:
             ev_tgt.record(s2)
             if fresh:
                 self.ws_tips.sort(tips)
-            if self.concurrent == 1:
-                ev_tips.record(main)
-                s1.wait_event(ev_tips)
-                with torch.cuda.stream(s1):
-                    self.mesh.query(tips, workspace=self.ws_tips, reuse_order=True, out=o[1])
-                ev_full.record(s1)
-            self.mesh_def.query(tips, workspace=self.ws_tips, reuse_order=True, out=o[0])
-            if self.concurrent == 1:
-                main.wait_event(ev_full)
-            else:  # (A/B: the full mesh's fingertip query on the caller's stream too)
+            ev_tips.record(main)
+            s1.wait_event(ev_tips)
+            with torch.cuda.stream(s1):
                 self.mesh.query(tips, workspace=self.ws_tips, reuse_order=True, out=o[1])
+            ev_full.record(s1)
+            self.mesh_def.query(tips, workspace=self.ws_tips, reuse_order=True, out=o[0])
+            main.wait_event(ev_full)
             main.wait_event(ev_tgt)
         return o[0][1], o[0][2], o[1][0], o[1][1], o[1][2], o[1][3], o[2][0], o[2][1], o[2][3]
 
-    def loss_slot(self, s, iters):
-        """Iteration s's loss vector: a row of a per-call [iters, E] history (the per-iteration sums are taken in one
-        reduction after the loop, not one per iteration), or the single buffer when the history would pass 1 GiB."""
-        E = self.loss.shape[0]
-        if s == 0:
-            self.hist = (torch.empty(iters, E, dtype=torch.float64, device=self.loss.device)
-                         if iters * E * 8 <= (1 << 30) else None)
-        row = self.hist[s] if self.hist is not None else self.loss
-        self.buffers.loss = N.ptr(row)
-        return row
 
-    def loss_sums(self, history):
-        """Append the loop's per-iteration loss sums (device scalars) to ``history``."""
-        if getattr(self, "hist", None) is not None:
-            history.extend(self.hist.sum(dim=1).unbind(0))
+def _kin_mode_run(self, chain, prm, cfg, st, q, pts, verbose, kabsch_noise, trace_rows, split_step, extras=()):
+    """The fused loop of the Kin (``chain``, joints ``q``) and SDF (neither) optimisers on the loop state ``st``;
+    ``pts``: the [E·T, 3] fingertips the queries and the cost read.  → the last iteration's loss row."""
+    lib = N.load()
+    tgt, comp = st.target, st.comp
+    E, T = tgt.shape[0], tgt.shape[1]
+    stream = N.stream_ptr(self.device)
+    # cdx_kin_cost's gradient outputs: joints, targets, compliances, fingertips
+    grads = (st.g[0], st.g[1], st.g[2], None) if chain is not None else (None, st.g[1], st.g[2], st.g[0])
 
-    def best(self):
-        return self.opt[0], self.opt[2], self.opt[1], (self.opt_margin > 0.0).all()
+    def queries():
+        return [N.ptr(t) for t in st.queries(pts, tgt)]
+
+    def iterate(qr, nz, seed, s):  # cost, backward and step in one launch (cdx_kin_iteration)
+        N.check(lib.cdx_kin_iteration(chain, prm, cfg, st.buffers, E, T, *qr, nz, seed, s, stream), "cdx_kin_iteration")
+
+    def cost(qr, nz, seed, s, loss):
+        N.check(lib.cdx_kin_cost(chain, prm, E, N.ptr(q), N.ptr(pts), N.ptr(tgt), N.ptr(comp), *qr, nz, seed,
+                                 N.ptr(loss), N.ptr(st.margin[s & 1]), N.ptr(st.normal[s & 1]), N.ptr(grads[0]),
+                                 N.ptr(grads[1]), N.ptr(grads[2]), N.ptr(grads[3]), stream), "cdx_kin_cost")
+
+    def step(s, finalize):
+        N.check(lib.cdx_kin_step(chain, cfg, st.buffers, E, T, s, finalize, stream), "cdx_kin_step")
+
+    return _fused_loop(self, st, queries, iterate, cost, step, split_step, None, verbose, kabsch_noise, trace_rows,
+                       extras)
 
 
-class KinGraspOptimizer:
+def _fe_kwargs(opt):
+    """force_eq_reward's keyword arguments from an optimiser's mass, centre of mass and gravity switch."""
+    return dict(mass=opt.mass, COM=opt.com, gravity=10.0 if opt.gravity else None)
+
+
+class _JointSpace:
+    """What the three joint-space optimisers share: the robot model, the fingertip links, ``ref_q``, FK and the hand
+    term's set-up."""
+
+    def _init_chain(self, robot_urdf, ee_link_names, ee_link_offsets, ref_q, device):
+        self.ref_q = torch.tensor(list(ref_q)).to(self.device)
+        self.robot_model = DifferentiableRobotModel(robot_urdf, device=device)
+        self.ee_link_names = list(ee_link_names)
+        self.ee_link_offsets = ee_link_offsets
+
+    def forward_kinematics(self, joint_angles):
+        """[E·T, 3] fingertips: FK (recursive=True, :148) + palm offset."""
+        tips = self.robot_model.compute_forward_kinematics(joint_angles, self.ee_link_names,
+                                                          offsets=self.ee_link_offsets, recursive=True)[0]
+        return (tips.view(-1, 3) + self.palm_offset).view(-1, 3)
+
+    def _hand_palm(self, hand_term, joint_angles):
+        """Clear ``last_hand_report``, check ``hand_term`` against the joint rows and → the term's palm rows (the palm
+        at ``palm_offset``, zero angles), or None without a term."""
+        self.last_hand_report = None
+        if hand_term is None:
+            return None
+        hand_term.check(joint_angles.shape[1], self.device)
+        return _hand.palm_rows(self.palm_offset, joint_angles.shape[0])
+
+    def _clamp_comp_target(self, joint_angles, target_pose, compliance):
+        """KinGPIS's and WC's clamps after a step (:503-505 / :606-608)."""
+        compliance.clamp_(min=40.0)
+        target_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
+
+
+class KinGraspOptimizer(_JointSpace):
     """Joint-space optimiser on the TorchSDF mesh distance (optimize_pregrasp.py:121-227)."""
 
     def __init__(self, robot_urdf, ee_link_names, ee_link_offsets=EE_OFFSETS, palm_offset=(-0.01, 0.015, 0.12),
@@ -287,69 +471,49 @@ class KinGraspOptimizer:
         iteration k of this optimiser's n-th fused call draws with key seed + (iterations before it) + k + 1."""
         self.device = torch.device(device)
         self._seed = int(seed)
-        self.loop_events = None  # optional (start, end) CUDA events around a fused loop's iterations
-        self.ref_q = torch.tensor(list(ref_q)).to(self.device)
-        self.robot_model = DifferentiableRobotModel(robot_urdf, device=device)
+        self.loop_events = None  # optional (start, end) CUDA events recorded around the iterations, eager or fused
+        self._init_chain(robot_urdf, ee_link_names, ee_link_offsets, ref_q, device)
         self.num_iters = num_iters
-        self.ee_link_names = list(ee_link_names)
-        self.ee_link_offsets = ee_link_offsets
         self.palm_offset = torch.tensor(palm_offset).to(self.device)
         self.optimize_target = optimize_target
         self.gravity, self.mass, self.com = gravity, mass, list(com)
 
-    def forward_kinematics(self, joint_angles):
-        """[E·T, 3] fingertips: FK (recursive=True, :148) + palm offset."""
-        tips = self.robot_model.compute_forward_kinematics(joint_angles, self.ee_link_names,
-                                                          offsets=self.ee_link_offsets, recursive=True)[0]
-        return (tips.view(-1, 3) + self.palm_offset).view(-1, 3)
-
     def optimize(self, joint_angles, target_pose, compliance, friction_mu, object_mesh, verbose=True,
-                 kabsch_noise=None, trace_rows=False, fused=True, hand_term=None):
+                 kabsch_noise=None, trace_rows=False, fused=True, hand_term=None, split_step=False, fk_cache=True):
         """``trace_rows``: also keep every iteration's per-candidate loss in ``loss_rows`` (device).
         ``hand_term`` (a ``HandTerm``, ``fused=False`` only: the fused loop has no mesh query at the sphere centres):
         per iteration ``l += weight · hand_collision(hand, q, palm, obj or the mesh, …)`` with the palm at
         ``palm_offset`` and zero angles; ``last_hand_report`` is ``penetration_report`` of the returned joints.
-        ``fused`` (default): per iteration the three TorchSDF queries on prepared meshes, ONE cost-and-backward
-        kernel (cdx_kin_cost: force_eq_reward, the six cost terms and the backward through them, TorchSDF and
-        the FK chain) and ONE step kernel (cdx_kin_step: Adam, the best iterate, the next fingertips' FK) — no
-        autograd graph, no host sync; ``fused=False``: the same loop through the autograd drop-ins
-        (compute_sdf, force_eq_reward, the FK module), torch tensor ops and torch.optim.Adam, as the reference
-        writes it."""
+        ``fused`` (default): per iteration the three TorchSDF queries on prepared meshes and ONE cost, backward and
+        step kernel (cdx_kin_iteration: force_eq_reward, the six cost terms and the backward through them, TorchSDF
+        and the FK chain, then Adam, the best iterate and the next fingertips' FK) — no autograd graph, no host sync;
+        with ``split_step`` or ``verbose`` cdx_kin_cost then cdx_kin_step (``split_step="alt"``, a test hook: the two
+        forms alternating, even iterations two launches, so that the one-launch iterations find the FK-walk cache one
+        step stale and must walk).  ``fk_cache=False``: the one-launch iteration keeps no FK-walk cache, every
+        iteration walks.  ``fused=False``: the same loop through the autograd drop-ins (compute_sdf, force_eq_reward,
+        the FK module), torch tensor ops and torch.optim.Adam, as the reference writes it."""
         if fused and hand_term is not None:
             raise ValueError("KinGraspOptimizer: hand_term needs fused=False (the fused loop has no mesh query at the "
                              "sphere centres)")
-        self.loss_history = []
-        self.loss_rows = []
-        self.last_hand_report = None
+        self.loss_history, self.loss_rows = [], []
         faces = _face_vertices(object_mesh, self.device)
-        if hand_term is not None:
-            hand_term.check(joint_angles.shape[1], self.device)
-            palm = _hand.palm_rows(self.palm_offset, joint_angles.shape[0])
-            term_obj = PreparedMesh(faces) if hand_term.obj is None else None
+        palm = self._hand_palm(hand_term, joint_angles)
+        hand = None if palm is None else (hand_term, palm, PreparedMesh(faces) if hand_term.obj is None else None)
         object_mesh.scale(0.9, center=[0, 0, 0])
         faces_deflate = _face_vertices(object_mesh, self.device)
         E, T = target_pose.shape[0], target_pose.shape[1]
         lrs = (2e-3, 1e-5, 0.2) if self.optimize_target else (1e-2, 0.0, 0.2)  # q, target, compliance (:168-176)
         if fused:
             return self._optimize_fused(joint_angles, target_pose, compliance, friction_mu, faces, faces_deflate, lrs,
-                                        verbose, kabsch_noise, trace_rows)
-        joint_angles = joint_angles.clone().requires_grad_(True)
-        compliance = compliance.clone().requires_grad_(True)
-        if self.optimize_target:
-            target_pose = target_pose.clone().requires_grad_(True)
-            optim = torch.optim.Adam([{"params": joint_angles, "lr": lrs[0]}, {"params": target_pose, "lr": lrs[1]},
-                                      {"params": compliance, "lr": lrs[2]}])
-        else:
-            optim = torch.optim.Adam([{"params": joint_angles, "lr": lrs[0]}, {"params": compliance, "lr": lrs[2]}])
-        best = _Best(torch.float32, E, T, self.device, q=joint_angles, comp=compliance, target=target_pose)
-        for s in range(self.num_iters):
-            optim.zero_grad()
+                                        verbose, kabsch_noise, trace_rows, split_step, fk_cache)
+
+        def cost(s, joint_angles, target_pose, compliance):
             all_tip = self.forward_kinematics(joint_angles)
             dist, normal = _sdf_normal(all_tip, faces, faces_deflate)
             tar_dist, tar_sign, _, _ = compute_sdf(target_pose.reshape(-1, 3), faces)
             reward, margin, force_norm = force_eq_reward(
                 all_tip.view(target_pose.shape), target_pose, compliance, friction_mu, normal.view(target_pose.shape),
-                mass=self.mass, COM=self.com, gravity=10.0 if self.gravity else None, kabsch_noise=_noise(kabsch_noise, s))
+                kabsch_noise=_noise(kabsch_noise, s), **_fe_kwargs(self))
             c = -reward * 5.0
             center_cost = (all_tip.view(target_pose.shape).mean(dim=1) - target_pose.mean(dim=1)).norm(dim=1) * 10.0
             ref_cost = (joint_angles - self.ref_q).norm(dim=1) * 10.0
@@ -358,25 +522,13 @@ class KinGraspOptimizer:
             # for E = 1; the [E, T] sign is what that line means and what it computes at E = 1
             tar_dist_cost = 10 * (tar_sign.view(E, T) * torch.sqrt(tar_dist).view(E, T)).sum(dim=1)
             l = c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0) + ref_cost
-            if hand_term is not None:
-                l = l + hand_term.cost(joint_angles, palm, term_obj).to(l.dtype)
-            l.sum().backward()
-            self.loss_history.append(l.detach().sum())  # device scalar, no sync
-            if trace_rows:
-                self.loss_rows.append(l.detach().clone())
-            if verbose:
-                print("Loss:", float(l.sum()), compliance)
-            best.update(l, margin, normal, q=joint_angles, comp=compliance, target=target_pose)
-            optim.step()
-        if verbose:
-            print(best.margin, best.normal)
-        self.best_loss = best.value
-        if hand_term is not None:
-            self.last_hand_report = hand_term.report(best.params["q"], palm, term_obj)
-        return best.params["q"], best.params["comp"], best.params["target"], best.flag()
+            return l, margin, normal, target_pose, lambda: (compliance,)
+
+        return _eager_loop(self, torch.optim.Adam, torch.float32, joint_angles, target_pose, compliance, lrs,
+                           self.optimize_target, cost, None, hand, verbose, trace_rows)
 
     def _optimize_fused(self, joint_angles, target_pose, compliance, friction_mu, faces, faces_deflate, lrs, verbose,
-                        kabsch_noise, trace_rows):
+                        kabsch_noise, trace_rows, split_step, fk_cache):
         lib = N.load()
         dev = self.device
         E, T = target_pose.shape[0], target_pose.shape[1]
@@ -387,63 +539,26 @@ class KinGraspOptimizer:
         chain = self.robot_model._descriptor(self.ee_link_names, self.ee_link_offsets)
         prm = N.CdxKinParams()
         prm.fe = force_eq_descriptor(T, friction_mu, self.mass, 10.0 if self.gravity else None, 2.0, self.com)
-        for i, v in enumerate(self.ref_q.float().tolist()):
-            prm.ref_q[i] = v
         cfg = N.CdxKinOpt()
         cfg.rule, cfg.clamp_box = 0, 0
         cfg.lr[0], cfg.lr[1], cfg.lr[2] = lrs
         cfg.beta1, cfg.beta2, cfg.eps = 0.9, 0.999, 1e-8  # torch.optim.Adam defaults (:171)
-        off = self.palm_offset.float().cpu().tolist()
-        for i in range(3):
-            cfg.palm_offset[i] = off[i]
+        _set_ref_palm(prm, cfg, self.ref_q, self.palm_offset, torch.float32)
         st = _FusedLoop(E, T, q, tgt, comp, faces, faces_deflate, dev)
         st.buffers.tips = N.ptr(st.tips)
-        # (A/B: "0" cdx_kin_cost + cdx_kin_step; "alt" the two forms alternating, even iterations two launches — a
-        # test hook: the one-launch iterations then find the FK-walk cache one step stale and must walk)
-        fused_step = os.environ.get("CDX_KIN_FUSED_STEP", "1")
-        one_launch = fused_step != "0"
         nb = int(lib.cdx_kin_fk_state_bytes(E, T))
-        if one_launch and nb and os.environ.get("CDX_KIN_FK_CACHE", "1") != "0":  # (A/B: every iteration walks)
+        if (split_step == "alt" or not split_step) and nb and fk_cache:
             # the step's FK walk kept for the next iteration's FK backward (any contents: the kernel tags what it wrote)
             st.fk_state = torch.full((nb // 4,), -1, dtype=torch.int32, device=dev)
             st.buffers.fk_state = N.ptr(st.fk_state)
-        stream = N.stream_ptr(dev)
-        N.check(lib.cdx_fk_forward(chain, N.ptr(q), E, N.ptr(st.tips), None, stream), "cdx_fk_forward")
+        N.check(lib.cdx_fk_forward(chain, N.ptr(q), E, N.ptr(st.tips), None, N.stream_ptr(dev)), "cdx_fk_forward")
         st.tips.add_(self.palm_offset.float())  # FK + palm offset (:148); later iterations: cdx_kin_step
-        if self.loop_events:
-            self.loop_events[0].record()
-        for s in range(self.num_iters):
-            nz = _noise(kabsch_noise, s)
-            nz = None if nz is None else nz.detach().to(device=dev, dtype=torch.float64).contiguous()
-            self._seed += 1
-            loss = st.loss_slot(s, self.num_iters)
-            qr = [N.ptr(t) for t in st.queries(st.tips, tgt)]
-            if not verbose and one_launch and not (fused_step == "alt" and s % 2 == 0):
-                # cost, backward and step in one launch (cdx_kin_iteration)
-                N.check(lib.cdx_kin_iteration(chain, prm, cfg, st.buffers, E, T, *qr, N.ptr(nz), self._seed, s, stream),
-                        "cdx_kin_iteration")
-            else:  # two launches (verbose: the compliances printed before the step, as the reference prints them)
-                N.check(lib.cdx_kin_cost(chain, prm, E, N.ptr(q), N.ptr(st.tips), N.ptr(tgt), N.ptr(comp), *qr,
-                                         N.ptr(nz), self._seed, N.ptr(loss), N.ptr(st.margin[s & 1]),
-                                         N.ptr(st.normal[s & 1]), N.ptr(st.g[0]), N.ptr(st.g[1]), N.ptr(st.g[2]), None,
-                                         stream), "cdx_kin_cost")
-                if verbose:
-                    print("Loss:", float(loss.sum()), comp)
-                N.check(lib.cdx_kin_step(chain, cfg, st.buffers, E, T, s, 0, stream), "cdx_kin_step")
-            if st.hist is None:
-                self.loss_history.append(loss.sum())  # device scalar, no sync
-            if trace_rows:
-                self.loss_rows.append(loss.clone())
-        N.check(lib.cdx_kin_step(chain, cfg, st.buffers, E, T, self.num_iters, 1, stream), "cdx_kin_step")
-        st.loss_sums(self.loss_history)
-        if self.loop_events:
-            self.loop_events[1].record()
-        if verbose:
-            print(st.opt_margin, st.opt_normal)
-        self.best_loss = st.opt_value
+        # (verbose: the compliances printed before the step, as the reference prints them)
+        loss = _kin_mode_run(self, chain, prm, cfg, st, q, st.tips, verbose, kabsch_noise, trace_rows, split_step,
+                             (comp,))
         # the last iteration's per-candidate loss and fingertips (device, no copy; the reference prints the
         # non-finite case at :212-213)
-        self.last_loss, self.last_tips = (loss if self.num_iters else None), st.tips
+        self.last_loss, self.last_tips = loss, st.tips
         self.last_params = (q, tgt, comp)  # the parameters after the last step (device, updated in place)
         # (trace_rows: the loop's device state too — moments, best iterate — for state-injection checks)
         self.last_loop = st if trace_rows else None
@@ -458,21 +573,19 @@ class SDFGraspOptimizer:
         """``seed``: key of the fused loop's on-device Kabsch noise (as KinGraspOptimizer's)."""
         self.device = torch.device(device)
         self._seed = int(seed)
-        self.loop_events = None  # optional (start, end) CUDA events around a fused loop's iterations
-        self.tip_bounding_box = [torch.tensor(tip_bounding_box[0]).to(self.device).view(-1, 3),
-                                 torch.tensor(tip_bounding_box[1]).to(self.device).view(-1, 3)]
+        self.loop_events = None  # optional (start, end) CUDA events recorded around the iterations, eager or fused
+        self.tip_bounding_box = _tip_box(tip_bounding_box, self.device)
         self.num_iters = num_iters
         self.optimize_target = optimize_target
         self.mass, self.com, self.gravity = mass, list(com), gravity
 
     def optimize(self, tip_pose, target_pose, compliance, friction_mu, object_mesh, verbose=True, kabsch_noise=None,
-                 trace_rows=False, fused=True):
+                 trace_rows=False, fused=True, split_step=False):
         """``trace_rows``: also keep every iteration's per-candidate loss in ``loss_rows`` (device).
-        ``fused`` (default): per iteration the three TorchSDF queries on prepared meshes, ONE cost-and-backward
-        kernel (cdx_kin_cost without a chain) and ONE step kernel (cdx_kin_step: RMSprop, the best iterate, the
-        box clamps); ``fused=False``: the autograd loop with torch.optim.RMSprop."""
-        self.loss_history = []
-        self.loss_rows = []
+        ``fused`` (default): per iteration the three TorchSDF queries on prepared meshes and ONE cost, backward and
+        step kernel (cdx_kin_iteration without a chain: RMSprop, the best iterate, the box clamps; with ``split_step``
+        or ``verbose`` cdx_kin_cost then cdx_kin_step); ``fused=False``: the autograd loop with torch.optim.RMSprop."""
+        self.loss_history, self.loss_rows = [], []
         faces = _face_vertices(object_mesh, self.device)
         object_mesh.scale(0.9, center=[0, 0, 0])
         faces_deflate = _face_vertices(object_mesh, self.device)
@@ -480,49 +593,31 @@ class SDFGraspOptimizer:
         lrs = (1e-3, 1e-3 if self.optimize_target else 0.0, 0.2)  # tips, target, compliance (:250-259)
         if fused:
             return self._optimize_fused(tip_pose, target_pose, compliance, friction_mu, faces, faces_deflate, lrs,
-                                        verbose, kabsch_noise, trace_rows)
-        tip_pose = tip_pose.clone().requires_grad_(True)
-        compliance = compliance.clone().requires_grad_(True)
-        if self.optimize_target:
-            target_pose = target_pose.clone().requires_grad_(True)
-            optim = torch.optim.RMSprop([{"params": tip_pose, "lr": lrs[0]}, {"params": target_pose, "lr": lrs[1]},
-                                         {"params": compliance, "lr": lrs[2]}])
-        else:
-            optim = torch.optim.RMSprop([{"params": tip_pose, "lr": lrs[0]}, {"params": compliance, "lr": lrs[2]}])
-        best = _Best(torch.float32, E, T, self.device, tip=tip_pose, comp=compliance, target=target_pose)
-        for s in range(self.num_iters):
-            optim.zero_grad()
+                                        verbose, kabsch_noise, trace_rows, split_step)
+
+        def cost(s, tip_pose, target_pose, compliance):
             all_tip = tip_pose.view(-1, 3)
             dist, normal = _sdf_normal(all_tip, faces, faces_deflate)
             tar_dist, tar_sign, _, _ = compute_sdf(target_pose.reshape(-1, 3), faces)
             reward, margin, force_norm = force_eq_reward(
-                tip_pose, target_pose, compliance, friction_mu, normal.view(tip_pose.shape), mass=self.mass,
-                COM=self.com, gravity=10.0 if self.gravity else None, kabsch_noise=_noise(kabsch_noise, s))
+                tip_pose, target_pose, compliance, friction_mu, normal.view(tip_pose.shape),
+                kabsch_noise=_noise(kabsch_noise, s), **_fe_kwargs(self))
             c = -reward * 5.0
             center_cost = (tip_pose.mean(dim=1) - target_pose.mean(dim=1)).norm(dim=1) * 10.0
             dist_cost = 1000 * torch.sqrt(dist).view(E, T).sum(dim=1)
             tar_dist_cost = 10 * (torch.sqrt(tar_dist).view(E, T) * tar_sign.view(E, T)).sum(dim=1)  # see :297
             l = c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0)
-            l.sum().backward()
-            self.loss_history.append(l.detach().sum())  # device scalar, no sync
-            if trace_rows:
-                self.loss_rows.append(l.detach().clone())
-            if verbose:
-                print("Loss:", float(l.sum()), float(dist_cost.sum()), float(tar_dist_cost.sum()))
-            best.update(l, margin, normal, tip=tip_pose, comp=compliance, target=target_pose)
-            optim.step()
-            with torch.no_grad():  # bounding-box constraints (:312-314)
-                tip_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
-                target_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
-        if verbose:
-            print(best.margin, best.normal)
-        self.best_loss = best.value
-        return best.params["tip"], best.params["comp"], best.params["target"], best.flag()
+            return l, margin, normal, target_pose, lambda: (float(dist_cost.sum()), float(tar_dist_cost.sum()))
+
+        def clamp(tip_pose, target_pose, compliance):  # bounding-box constraints (:312-314)
+            tip_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
+            target_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
+
+        return _eager_loop(self, torch.optim.RMSprop, torch.float32, tip_pose, target_pose, compliance, lrs,
+                           self.optimize_target, cost, clamp, None, verbose, trace_rows)
 
     def _optimize_fused(self, tip_pose, target_pose, compliance, friction_mu, faces, faces_deflate, lrs, verbose,
-                        kabsch_noise, trace_rows):
-        lib = N.load()
-        dev = self.device
+                        kabsch_noise, trace_rows, split_step):
         E, T = tip_pose.shape[0], tip_pose.shape[1]
         tips, tgt, comp = (x.detach().clone().contiguous() for x in (tip_pose, target_pose, compliance))
         if any(x.dtype != torch.float32 for x in (tips, tgt, comp)):
@@ -533,65 +628,30 @@ class SDFGraspOptimizer:
         cfg.rule, cfg.clamp_box = 1, 1
         cfg.lr[0], cfg.lr[1], cfg.lr[2] = lrs
         cfg.alpha, cfg.eps = 0.99, 1e-8  # torch.optim.RMSprop defaults (:253)
-        lb = self.tip_bounding_box[0].float().expand(T, 3).reshape(-1).cpu().tolist()
-        ub = self.tip_bounding_box[1].float().expand(T, 3).reshape(-1).cpu().tolist()
-        for i in range(3 * T):
-            cfg.box_lb[i], cfg.box_ub[i] = lb[i], ub[i]
-        st = _FusedLoop(E, T, tips, tgt, comp, faces, faces_deflate, dev)
-        stream = N.stream_ptr(dev)
-        one_launch = os.environ.get("CDX_KIN_FUSED_STEP", "1") != "0"  # (A/B: cdx_kin_cost + cdx_kin_step)
-        if self.loop_events:
-            self.loop_events[0].record()
-        for s in range(self.num_iters):
-            nz = _noise(kabsch_noise, s)
-            nz = None if nz is None else nz.detach().to(device=dev, dtype=torch.float64).contiguous()
-            self._seed += 1
-            pts = tips.view(-1, 3)
-            loss = st.loss_slot(s, self.num_iters)
-            qr = [N.ptr(t) for t in st.queries(pts, tgt)]
-            if not verbose and one_launch:  # cost, backward and step in one launch (cdx_kin_iteration)
-                N.check(lib.cdx_kin_iteration(None, prm, cfg, st.buffers, E, T, *qr, N.ptr(nz), self._seed, s, stream),
-                        "cdx_kin_iteration")
-            else:
-                N.check(lib.cdx_kin_cost(None, prm, E, None, N.ptr(pts), N.ptr(tgt), N.ptr(comp), *qr, N.ptr(nz),
-                                         self._seed, N.ptr(loss), N.ptr(st.margin[s & 1]), N.ptr(st.normal[s & 1]),
-                                         None, N.ptr(st.g[1]), N.ptr(st.g[2]), N.ptr(st.g[0]), stream), "cdx_kin_cost")
-                if verbose:
-                    print("Loss:", float(loss.sum()))
-                N.check(lib.cdx_kin_step(None, cfg, st.buffers, E, T, s, 0, stream), "cdx_kin_step")
-            if st.hist is None:
-                self.loss_history.append(loss.sum())  # device scalar, no sync
-            if trace_rows:
-                self.loss_rows.append(loss.clone())
-        N.check(lib.cdx_kin_step(None, cfg, st.buffers, E, T, self.num_iters, 1, stream), "cdx_kin_step")
-        st.loss_sums(self.loss_history)
-        if self.loop_events:
-            self.loop_events[1].record()
-        if verbose:
-            print(st.opt_margin, st.opt_normal)
-        self.best_loss = st.opt_value
+        _set_box(cfg, self.tip_bounding_box, T, torch.float32)
+        st = _FusedLoop(E, T, tips, tgt, comp, faces, faces_deflate, self.device)
+        _kin_mode_run(self, None, prm, cfg, st, None, tips.view(-1, 3), verbose, kabsch_noise, trace_rows,
+                      bool(split_step))
         return st.best()
 
 
 _MEAN_TILE = 32  # queries per workgroup of cdx_gpis_mean
 
 
-class _GpisModeLoop:
+class _GpisModeLoop(_LoopState):
     """Device state of a fused GPIS / KinGPIS loop (cdx_gpis_mode_*): the query points [tips; targets] in one
     buffer, the per-point GPIS outputs, the gradients, RMSprop's square averages, the two margin / normal slots and
     the best iterate.  Per iteration the loop is ONE cdx_gpis_mean launch over the 2·E·T points (mean, ∇mean, normal),
     ONE cdx_gpis_std launch over the E·T fingertips (the reference's variance of the targets is never used) and
     cdx_gpis_mode_iteration: no autograd graph, no host sync."""
 
-    loss_slot = _FusedLoop.loss_slot
-    loss_sums = _FusedLoop.loss_sums
+    term = None  # KinGPIS with a hand term: its hand.TermLoop, with ``term_palm``
 
     def __init__(self, mode, pose, target, comp, gpis, dev):
         f64 = dict(dtype=torch.float64, device=dev)
         E, T = target.shape[0], target.shape[1]
         self.E, self.T, self.mode = E, T, mode
         self.state = gpis.native_state()
-        self.hist = None
         # the iteration's query points in one buffer: the fingertips, then — from the next multiple of the mean
         # kernel's 32-query workgroup on, so that every row is computed exactly as by a launch of its own — the
         # targets; the rows between hold a finite filler point.  (A non-finite query stays in its own row of
@@ -625,18 +685,16 @@ class _GpisModeLoop:
         self.opt = [x.clone() for x in params]
         self.any = torch.zeros(3, dtype=torch.int32, device=dev)
         b = N.CdxGpisModeBuffers()
-        for name, t in (("pose", self.pose), ("target", self.target), ("comp", self.comp),
-                        ("tips", self.tips if mode == 1 else None), ("mean", self.mean[:M]), ("gmean", self.gmean[:M]),
-                        ("normal", self.nrm[:M]), ("std", self.std), ("gstd", self.gstd), ("tmean", self.mean[Mp:]),
-                        ("tgmean", self.gmean[Mp:]), ("g_pose", self.g[0]), ("g_target", self.g[1]),
-                        ("g_comp", self.g[2]), ("g_tip", self.g_tip), ("v_pose", self.v[0]), ("v_target", self.v[1]),
-                        ("v_comp", self.v[2]), ("loss", self.loss), ("opt_value", self.opt_value),
-                        ("opt_margin", self.opt_margin), ("opt_normal", self.opt_normal), ("opt_pose", self.opt[0]),
-                        ("opt_target", self.opt[1]), ("opt_comp", self.opt[2]), ("any", self.any)):
-            setattr(b, name, N.ptr(t))
+        self.fill(b, (("pose", self.pose), ("target", self.target), ("comp", self.comp),
+                      ("tips", self.tips if mode == 1 else None), ("mean", self.mean[:M]), ("gmean", self.gmean[:M]),
+                      ("normal", self.nrm[:M]), ("std", self.std), ("gstd", self.gstd), ("tmean", self.mean[Mp:]),
+                      ("tgmean", self.gmean[Mp:]), ("g_pose", self.g[0]), ("g_target", self.g[1]),
+                      ("g_comp", self.g[2]), ("g_tip", self.g_tip), ("v_pose", self.v[0]), ("v_target", self.v[1]),
+                      ("v_comp", self.v[2]), ("loss", self.loss), ("opt_value", self.opt_value),
+                      ("opt_margin", self.opt_margin), ("opt_normal", self.opt_normal), ("opt_pose", self.opt[0]),
+                      ("opt_target", self.opt[1]), ("opt_comp", self.opt[2]), ("any", self.any)))
         for i in range(2):
             b.margin[i], b.normal_slot[i] = N.ptr(self.margin[i]), N.ptr(self.normal[i])
-        self.buffers = b
 
     def queries(self, lib, stream):
         """The iteration's two GPIS launches: mean / ∇mean / normal at [tips; targets], std / ∇std at the tips."""
@@ -646,50 +704,33 @@ class _GpisModeLoop:
         N.check(lib.cdx_gpis_std(self.state.desc, N.ptr(self.X), M, N.ptr(self.std), N.ptr(self.gstd), N.ptr(self.ws),
                                  stream), "cdx_gpis_std")
 
-    def best(self):
-        return self.opt[0], self.opt[2], self.opt[1], (self.opt_margin > 0.0).all()
 
-
-def _gpis_mode_run(self, mode, chain, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step):
+def _gpis_mode_run(self, chain, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step):
     """The fused loop of the two GPIS-mode optimisers on the loop state ``st``."""
     lib = N.load()
-    dev = self.device
     E, T = st.E, st.T
-    stream = N.stream_ptr(dev)
-    loss = None
-    term = getattr(st, "term", None)  # (KinGPIS with a hand term: cost, term, step)
-    if self.loop_events:
-        self.loop_events[0].record()
-    for s in range(self.num_iters):
-        nz = _noise(kabsch_noise, s)
-        nz = None if nz is None else nz.detach().to(device=dev, dtype=torch.float64).contiguous()
-        self._seed += 1
-        loss = st.loss_slot(s, self.num_iters)
+    stream = N.stream_ptr(self.device)
+
+    def queries():
         st.queries(lib, stream)
-        if not verbose and not split_step and term is None:  # cost, backward and step in one launch (four fingertips)
-            N.check(lib.cdx_gpis_mode_iteration(chain, prm, cfg, st.buffers, E, T, N.ptr(nz), self._seed, s, stream),
-                    "cdx_gpis_mode_iteration")
-        else:
-            N.check(lib.cdx_gpis_mode_cost(chain, prm, st.buffers, E, T, N.ptr(nz), self._seed, s, stream),
-                    "cdx_gpis_mode_cost")
-            if term is not None:  # loss and g_q += weight · the hand's term at the current joints
-                term.place(lib, st.pose, st.term_palm, None, stream)
-                term.query(lib, stream)
-                term.add(lib, None, loss, st.g[0], None, None, stream)
-            if verbose:
-                print("Loss:", float(loss.sum()))
-            N.check(lib.cdx_gpis_mode_step(chain, prm, cfg, st.buffers, E, T, s, 0, stream), "cdx_gpis_mode_step")
-        if st.hist is None:
-            self.loss_history.append(loss.sum())  # device scalar, no sync
-        if trace_rows:
-            self.loss_rows.append(loss.clone())
-    N.check(lib.cdx_gpis_mode_step(chain, prm, cfg, st.buffers, E, T, self.num_iters, 1, stream), "cdx_gpis_mode_step")
-    st.loss_sums(self.loss_history)
-    if self.loop_events:
-        self.loop_events[1].record()
-    if verbose:
-        print(st.opt_margin, st.opt_normal)
-    self.best_loss = st.opt_value
+
+    def iterate(_, nz, seed, s):  # cost, backward and step in one launch (four fingertips)
+        N.check(lib.cdx_gpis_mode_iteration(chain, prm, cfg, st.buffers, E, T, nz, seed, s, stream),
+                "cdx_gpis_mode_iteration")
+
+    def cost(_, nz, seed, s, loss):
+        N.check(lib.cdx_gpis_mode_cost(chain, prm, st.buffers, E, T, nz, seed, s, stream), "cdx_gpis_mode_cost")
+
+    def step(s, finalize):
+        N.check(lib.cdx_gpis_mode_step(chain, prm, cfg, st.buffers, E, T, s, finalize, stream), "cdx_gpis_mode_step")
+
+    def term(loss):  # (KinGPIS with a hand term) loss and g_q += weight · the hand's term at the current joints
+        st.term.place(lib, st.pose, st.term_palm, None, stream)
+        st.term.query(lib, stream)
+        st.term.add(lib, None, loss, st.g[0], None, None, stream)
+
+    _fused_loop(self, st, queries, iterate, cost, step, bool(split_step), term if st.term is not None else None,
+                verbose, kabsch_noise, trace_rows)
     self._loop_state = st if self._keep_loop_state else None
     return st.best()
 
@@ -711,10 +752,7 @@ def _gpis_mode_setup(self, mode, T, friction_mu, lrs):
     cfg = N.CdxGpisModeOpt()
     cfg.lr[0], cfg.lr[1], cfg.lr[2] = lrs
     cfg.alpha, cfg.eps, cfg.comp_min = 0.99, 1e-8, 40.0  # torch.optim.RMSprop defaults (:348 / :454); :401 / :506
-    lb = self.tip_bounding_box[0].to(torch.float64).expand(T, 3).reshape(-1).cpu().tolist()
-    ub = self.tip_bounding_box[1].to(torch.float64).expand(T, 3).reshape(-1).cpu().tolist()
-    for i in range(3 * T):
-        cfg.box_lb[i], cfg.box_ub[i] = lb[i], ub[i]
+    _set_box(cfg, self.tip_bounding_box, T, torch.float64)
     return prm, cfg
 
 
@@ -728,8 +766,7 @@ class GPISGraspOptimizer:
         self._seed = int(seed)
         self.loop_events = None  # optional (start, end) CUDA events recorded around the iterations, eager or fused
         self._keep_loop_state = False  # tests: keep the fused loop's device state in ``_loop_state`` after the call
-        self.tip_bounding_box = [torch.tensor(tip_bounding_box[0]).to(self.device).view(-1, 3),
-                                 torch.tensor(tip_bounding_box[1]).to(self.device).view(-1, 3)]
+        self.tip_bounding_box = _tip_box(tip_bounding_box, self.device)
         self.num_iters = num_iters
         self.optimize_target = optimize_target
         self.mass, self.com, self.gravity, self.uncertainty = mass, list(com), gravity, uncertainty
@@ -742,64 +779,41 @@ class GPISGraspOptimizer:
         float64 device inputs, the caller's tensors untouched; ``fused=False`` (default): the autograd loop with
         torch.optim.RMSprop, as the reference writes it.  ``trace_rows``: also keep every iteration's per-candidate
         loss in ``loss_rows`` (device)."""
-        self.loss_rows = []
+        self.loss_history, self.loss_rows = [], []
+        E, T = tip_pose.shape[0], tip_pose.shape[1]
+        lrs = (1e-3, 1e-3 if self.optimize_target else 0.0, 0.2)  # tips, target, compliance (:348-355)
         if fused:
-            self.loss_history = []
             _gpis_mode_inputs("GPISGraspOptimizer", self.device, tip_pose=tip_pose, target_pose=target_pose,
                               compliance=compliance)
-            T = tip_pose.shape[1]
-            lrs = (1e-3, 1e-3 if self.optimize_target else 0.0, 0.2)  # tips, target, compliance (:348-355)
             prm, cfg = _gpis_mode_setup(self, 0, T, friction_mu, lrs)
             st = _GpisModeLoop(0, tip_pose.detach(), target_pose.detach(), compliance, gpis, self.device)
-            return _gpis_mode_run(self, 0, None, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step)
-        tip_pose = tip_pose.clone().requires_grad_(True)
-        self.loss_history = []
-        compliance = compliance.clone().requires_grad_(True)
-        if self.optimize_target:
-            target_pose = target_pose.clone().requires_grad_(True)
-            optim = torch.optim.RMSprop([{"params": tip_pose, "lr": 1e-3}, {"params": target_pose, "lr": 1e-3},
-                                         {"params": compliance, "lr": 0.2}])
-        else:
-            optim = torch.optim.RMSprop([{"params": tip_pose, "lr": 1e-3}, {"params": compliance, "lr": 0.2}])
-        E, T = tip_pose.shape[0], tip_pose.shape[1]
-        best = _Best(torch.float64, E, T, self.device, tip=tip_pose, comp=compliance, target=target_pose)
-        if self.loop_events:
-            self.loop_events[0].record()
-        for s in range(self.num_iters):
-            optim.zero_grad()
+            return _gpis_mode_run(self, None, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step)
+
+        def cost(s, tip_pose, target_pose, compliance):
             all_tip = tip_pose.view(-1, 3)
             dist, var = gpis.pred(all_tip)
             tar_dist, _ = gpis.pred(target_pose.reshape(-1, 3))
             normal = gpis.compute_normal(all_tip)
             reward, margin, force_norm = force_eq_reward(
-                tip_pose, target_pose, compliance, friction_mu, normal.view(tip_pose.shape), mass=self.mass,
-                COM=self.com, gravity=10.0 if self.gravity else None, kabsch_noise=_noise(kabsch_noise, s))
+                tip_pose, target_pose, compliance, friction_mu, normal.view(tip_pose.shape),
+                kabsch_noise=_noise(kabsch_noise, s), **_fe_kwargs(self))
             c = -reward * 25.0
             center_cost = (tip_pose.mean(dim=1) - target_pose.mean(dim=1)).norm(dim=1) * 10.0
             dist_cost = 1000 * torch.abs(dist).view(E, T).sum(dim=1)
             tar_dist_cost = 10 * tar_dist.view(E, T).sum(dim=1)
             variance_cost = self.uncertainty * var.view(E, T).sum(dim=1)
             l = c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0) + variance_cost
-            l.sum().backward()
-            self.loss_history.append(l.detach().sum())  # device scalar, no sync
-            if trace_rows:
-                self.loss_rows.append(l.detach().clone())
-            if verbose:
-                print("Loss:", float(l.sum()), float(dist_cost.sum()), float(variance_cost.sum()))
-            best.update(l, margin, normal, tip=tip_pose, comp=compliance, target=target_pose)
-            optim.step()
-            with torch.no_grad():  # (:399-401)
-                tip_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
-                compliance.clamp_(min=40.0)
-        if self.loop_events:
-            self.loop_events[1].record()
-        if verbose:
-            print(best.margin, best.normal)
-        self.best_loss = best.value
-        return best.params["tip"], best.params["comp"], best.params["target"], best.flag()
+            return l, margin, normal, target_pose, lambda: (float(dist_cost.sum()), float(variance_cost.sum()))
+
+        def clamp(tip_pose, target_pose, compliance):  # (:399-401)
+            tip_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
+            compliance.clamp_(min=40.0)
+
+        return _eager_loop(self, torch.optim.RMSprop, torch.float64, tip_pose, target_pose, compliance, lrs,
+                           self.optimize_target, cost, clamp, None, verbose, trace_rows)
 
 
-class KinGPISGraspOptimizer:
+class KinGPISGraspOptimizer(_JointSpace):
     """Joint-space optimiser on the GPIS distance and log-variance (optimize_pregrasp.py:408-511)."""
 
     def __init__(self, robot_urdf, ee_link_names, ee_link_offsets=EE_OFFSETS, palm_offset=WRIST_OFFSET, num_iters=1000,
@@ -810,21 +824,12 @@ class KinGPISGraspOptimizer:
         self._seed = int(seed)
         self.loop_events = None  # optional (start, end) CUDA events recorded around the iterations, eager or fused
         self._keep_loop_state = False  # tests: keep the fused loop's device state in ``_loop_state`` after the call
-        self.ref_q = torch.tensor(list(ref_q)).to(self.device)
-        self.robot_model = DifferentiableRobotModel(robot_urdf, device=device)
+        self._init_chain(robot_urdf, ee_link_names, ee_link_offsets, ref_q, device)
         self.num_iters = num_iters
-        self.ee_link_names = list(ee_link_names)
-        self.ee_link_offsets = ee_link_offsets
         self.palm_offset = torch.tensor(np.asarray(palm_offset)).double().to(self.device)
         self.optimize_target = optimize_target
-        self.tip_bounding_box = [torch.tensor(tip_bounding_box[0]).to(self.device).view(-1, 3),
-                                 torch.tensor(tip_bounding_box[1]).to(self.device).view(-1, 3)]
+        self.tip_bounding_box = _tip_box(tip_bounding_box, self.device)
         self.mass, self.com, self.gravity, self.uncertainty = mass, list(com), gravity, uncertainty
-
-    def forward_kinematics(self, joint_angles):
-        tips = self.robot_model.compute_forward_kinematics(joint_angles, self.ee_link_names,
-                                                          offsets=self.ee_link_offsets, recursive=True)[0]
-        return (tips.view(-1, 3) + self.palm_offset).view(-1, 3)
 
     def optimize(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose=True, kabsch_noise=None,
                  fused=False, trace_rows=False, split_step=False, hand_term=None):
@@ -835,42 +840,28 @@ class KinGPISGraspOptimizer:
         best-iterate comparison and the step; fused: cdx_gpis_mode_cost, then cdx_hand_spheres, cdx_gpis_mean at the
         sphere centres and cdx_hand_term (accumulating into the loss and the joint gradient), then cdx_gpis_mode_step.
         ``last_hand_report`` is then ``penetration_report`` of the returned joints."""
-        self.loss_rows = []
-        self.last_hand_report = None
-        if hand_term is not None:
-            hand_term.check(joint_angles.shape[1], self.device)
-            palm = _hand.palm_rows(self.palm_offset, joint_angles.shape[0])
+        self.loss_history, self.loss_rows = [], []
+        palm = self._hand_palm(hand_term, joint_angles)
+        lrs = (2e-3, 1e-3, 0.2) if self.optimize_target else (1e-2, 0.0, 0.2)  # q, target, compliance (:454-460)
         if fused:
-            self.loss_history = []
             _gpis_mode_inputs("KinGPISGraspOptimizer", self.device, joint_angles=joint_angles, target_pose=target_pose,
                               compliance=compliance)
-            res = self._optimize_fused(joint_angles, target_pose, compliance, friction_mu, gpis, verbose, kabsch_noise,
-                                       trace_rows, split_step, hand_term)
+            res = self._optimize_fused(joint_angles, target_pose, compliance, friction_mu, gpis, lrs, verbose,
+                                       kabsch_noise, trace_rows, split_step, hand_term)
             if hand_term is not None:
                 self.last_hand_report = hand_term.report(res[0], palm, gpis)
             return res
-        joint_angles = joint_angles.clone().requires_grad_(True)
-        self.loss_history = []
-        compliance = compliance.clone().requires_grad_(True)
-        if self.optimize_target:
-            target_pose = target_pose.clone().requires_grad_(True)
-            optim = torch.optim.RMSprop([{"params": joint_angles, "lr": 2e-3}, {"params": target_pose, "lr": 1e-3},
-                                         {"params": compliance, "lr": 0.2}])
-        else:
-            optim = torch.optim.RMSprop([{"params": joint_angles, "lr": 1e-2}, {"params": compliance, "lr": 0.2}])
+
         E, T = target_pose.shape[0], target_pose.shape[1]
-        best = _Best(torch.float64, E, T, self.device, q=joint_angles, comp=compliance, target=target_pose)
-        if self.loop_events:
-            self.loop_events[0].record()
-        for s in range(self.num_iters):
-            optim.zero_grad()
+
+        def cost(s, joint_angles, target_pose, compliance):
             all_tip = self.forward_kinematics(joint_angles)
             dist, var = gpis.pred(all_tip)
             tar_dist, _ = gpis.pred(target_pose.reshape(-1, 3))
             normal = gpis.compute_normal(all_tip)
             reward, margin, force_norm = force_eq_reward(
                 all_tip.view(target_pose.shape), target_pose, compliance, friction_mu, normal.view(target_pose.shape),
-                mass=self.mass, COM=self.com, gravity=10.0 if self.gravity else None, kabsch_noise=_noise(kabsch_noise, s))
+                kabsch_noise=_noise(kabsch_noise, s), **_fe_kwargs(self))
             c = -reward * 5.0
             center_cost = (all_tip.view(target_pose.shape).mean(dim=1) - target_pose.mean(dim=1)).norm(dim=1) * 10.0
             ref_cost = (joint_angles - self.ref_q).norm(dim=1) * 20.0
@@ -879,41 +870,19 @@ class KinGPISGraspOptimizer:
             tar_dist_cost = 10 * tar_dist.view(E, T).sum(dim=1)
             l = (c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0) + ref_cost +
                  variance_cost.max(dim=1)[0])
-            if hand_term is not None:
-                l = l + hand_term.cost(joint_angles, palm, gpis).to(l.dtype)
-            l.sum().backward()
-            self.loss_history.append(l.detach().sum())  # device scalar, no sync
-            if trace_rows:
-                self.loss_rows.append(l.detach().clone())
-            if verbose:
-                print("Loss:", float(l.sum()), variance_cost.detach())
-            best.update(l, margin, normal, q=joint_angles, comp=compliance, target=target_pose)
-            optim.step()
-            with torch.no_grad():  # (:503-505)
-                compliance.clamp_(min=40.0)
-                target_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
-        if self.loop_events:
-            self.loop_events[1].record()
-        if verbose:
-            print(best.margin, best.normal)
-        self.best_loss = best.value
-        if hand_term is not None:
-            self.last_hand_report = hand_term.report(best.params["q"], palm, gpis)
-        return best.params["q"], best.params["comp"], best.params["target"], best.flag()
+            return l, margin, normal, target_pose, lambda: (variance_cost.detach(),)
 
-    def _optimize_fused(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose, kabsch_noise,
+        return _eager_loop(self, torch.optim.RMSprop, torch.float64, joint_angles, target_pose, compliance, lrs,
+                           self.optimize_target, cost, self._clamp_comp_target,
+                           None if palm is None else (hand_term, palm, gpis), verbose, trace_rows)
+
+    def _optimize_fused(self, joint_angles, target_pose, compliance, friction_mu, gpis, lrs, verbose, kabsch_noise,
                         trace_rows, split_step, hand_term=None):
         lib = N.load()
         dev = self.device
         E, T = target_pose.shape[0], target_pose.shape[1]
-        # q, target, compliance (:454-460)
-        lrs = (2e-3, 1e-3, 0.2) if self.optimize_target else (1e-2, 0.0, 0.2)
         prm, cfg = _gpis_mode_setup(self, 1, T, friction_mu, lrs)
-        for i, v in enumerate(self.ref_q.to(torch.float64).tolist()):
-            prm.ref_q[i] = v
-        off = self.palm_offset.to(torch.float64).cpu().tolist()
-        for i in range(3):
-            prm.palm_offset[i] = off[i]
+        _set_ref_palm(prm, prm, self.ref_q, self.palm_offset, torch.float64)
         chain = self.robot_model._descriptor(self.ee_link_names, self.ee_link_offsets)
         st = _GpisModeLoop(1, joint_angles.detach(), target_pose.detach(), compliance, gpis, dev)
         # iteration 0's fingertips: double(FK_f32(float(q))) + palm offset (:462); later ones: cdx_gpis_mode_step
@@ -924,10 +893,10 @@ class KinGPISGraspOptimizer:
         if hand_term is not None:  # the term's buffers, with the loop state; the palm: palm_offset, no rotation
             st.term = _hand.TermLoop(hand_term, E, gpis, dev)
             st.term_palm = _hand.palm_rows(self.palm_offset, E)[:, :3].contiguous()
-        return _gpis_mode_run(self, 1, chain, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step)
+        return _gpis_mode_run(self, chain, prm, cfg, st, verbose, kabsch_noise, trace_rows, split_step)
 
 
-class WCKinGPISGraspOptimizer:
+class WCKinGPISGraspOptimizer(_JointSpace):
     """Joint-space optimiser on the minimum-wrench certificate (optimize_pregrasp.py:513-612): the cost of a candidate
     is the smallest net force and torque its contacts can leave (wrench.min_wrench — the reference solves it through
     cvxpylayers) instead of the Kabsch equilibrium of springs.  An eager loop like KinGPISGraspOptimizer.optimize, with
@@ -944,21 +913,12 @@ class WCKinGPISGraspOptimizer:
                  mass=0.1, com=(0.0, 0.0, 0.0), gravity=True, uncertainty=0.0, device="cuda"):
         self.device = torch.device(device)
         self.loop_events = None  # optional (start, end) CUDA events recorded around the iterations
-        self.ref_q = torch.tensor(list(ref_q)).to(self.device)
-        self.robot_model = DifferentiableRobotModel(robot_urdf, device=device)
+        self._init_chain(robot_urdf, ee_link_names, ee_link_offsets, ref_q, device)
         self.num_iters = num_iters
-        self.ee_link_names = list(ee_link_names)
-        self.ee_link_offsets = ee_link_offsets
         self.palm_offset = torch.tensor(np.asarray(palm_offset)).double().to(self.device)
-        self.tip_bounding_box = [torch.tensor(tip_bounding_box[0]).to(self.device).view(-1, 3),
-                                 torch.tensor(tip_bounding_box[1]).to(self.device).view(-1, 3)]
+        self.tip_bounding_box = _tip_box(tip_bounding_box, self.device)
         self.min_force = min_force
         self.mass, self.com, self.gravity = mass, list(com), gravity
-
-    def forward_kinematics(self, joint_angles):
-        tips = self.robot_model.compute_forward_kinematics(joint_angles, self.ee_link_names,
-                                                          offsets=self.ee_link_offsets, recursive=True)[0]
-        return (tips.view(-1, 3) + self.palm_offset).view(-1, 3)
 
     def optimize(self, joint_angles, target_pose, compliance, friction_mu, gpis, verbose=True, trace_rows=False,
                  hand_term=None):
@@ -967,27 +927,20 @@ class WCKinGPISGraspOptimizer:
         ``trace_rows``) keeps the per-candidate losses, ``wrench_rows`` the min_wrench result of every iteration.
         ``hand_term`` (a ``HandTerm``): as KinGPISGraspOptimizer.optimize's, through autograd."""
         from .wrench import min_wrench
-        self.last_hand_report = None
-        if hand_term is not None:
-            hand_term.check(joint_angles.shape[1], self.device)
-            palm = _hand.palm_rows(self.palm_offset, joint_angles.shape[0])
-        joint_angles = joint_angles.clone().requires_grad_(True)
-        compliance = compliance.clone().requires_grad_(True)
-        target_pose = target_pose.clone()
-        optim = torch.optim.RMSprop([{"params": joint_angles, "lr": 1e-2}, {"params": compliance, "lr": 0.2}])
-        E, T = target_pose.shape[0], target_pose.shape[1]
-        best = _Best(torch.float64, E, T, self.device, q=joint_angles, comp=compliance, target=target_pose)
         self.loss_history, self.loss_rows, self.wrench_rows = [], [], []
-        if self.loop_events:
-            self.loop_events[0].record()
-        for _ in range(self.num_iters):
-            optim.zero_grad()
+        palm = self._hand_palm(hand_term, joint_angles)
+
+        E, T = target_pose.shape[0], target_pose.shape[1]
+
+        def cost(s, joint_angles, target_pose, compliance):
             all_tip = self.forward_kinematics(joint_angles)
             dist, var = gpis.pred(all_tip)
             tar_dist, _ = gpis.pred(target_pose.reshape(-1, 3))
             normal = gpis.compute_normal(all_tip)
             tips = all_tip.view(target_pose.shape)
             res = min_wrench(tips, normal.view(target_pose.shape), friction_mu, min_force=self.min_force)
+            if trace_rows:
+                self.wrench_rows.append(res)
             margin, forces = res.margin, res.forces
             force_norm = forces.norm(dim=2)
             c = res.wrench * 5.0
@@ -998,26 +951,10 @@ class WCKinGPISGraspOptimizer:
             tar_dist_cost = 10 * tar_dist.view(E, T).sum(dim=1)
             l = (c + dist_cost + tar_dist_cost + center_cost + _force_cost(force_norm, 1.0) + ref_cost +
                  variance_cost.max(dim=1)[0])
-            if hand_term is not None:
-                l = l + hand_term.cost(joint_angles, palm, gpis).to(l.dtype)
-            l.sum().backward()
-            self.loss_history.append(l.detach().sum())  # device scalar, no sync
-            if trace_rows:
-                self.loss_rows.append(l.detach().clone())
-                self.wrench_rows.append(res)
-            if verbose:
-                print("Loss:", float(l.sum()), res.wrench.detach())
-            best.update(l, margin, normal, q=joint_angles, comp=compliance,
-                        target=tips + forces / compliance.unsqueeze(2))
-            optim.step()
-            with torch.no_grad():  # (:606-608)
-                compliance.clamp_(min=40.0)
-                target_pose.clamp_(min=self.tip_bounding_box[0], max=self.tip_bounding_box[1])
-        if self.loop_events:
-            self.loop_events[1].record()
-        if verbose:
-            print(best.margin, best.normal)
-        self.best_loss = best.value
-        if hand_term is not None:
-            self.last_hand_report = hand_term.report(best.params["q"], palm, gpis)
-        return best.params["q"], best.params["comp"], best.params["target"], best.flag()
+            # the target kept for an improved candidate: the springs that would exert the certified forces (:603)
+            return l, margin, normal, tips + forces / compliance.unsqueeze(2), lambda: (res.wrench.detach(),)
+
+        # q and compliance at 1e-2 and 0.2 (:553-556); the target is a frozen copy, clamped but never optimised
+        return _eager_loop(self, torch.optim.RMSprop, torch.float64, joint_angles, target_pose.clone(), compliance,
+                           (1e-2, 0.0, 0.2), False, cost, self._clamp_comp_target,
+                           None if palm is None else (hand_term, palm, gpis), verbose, trace_rows)

@@ -200,16 +200,14 @@ def test_collision_vs_oracle(E):
 KIN_E = 67
 
 
-def _kin_run(case, path, env, monkeypatch, iters=4, fused=True, noise=None, q_scale=0.3, seed=5):
+def _kin_run(case, path, iters=4, fused=True, noise=None, q_scale=0.3, seed=5, **loop_path):
     from compliancedex_amd import KinGraspOptimizer
     from compliancedex_amd.workloads import banana_mesh
     links, offs, palm, q, target, comp = ch.hand_kin_inputs(case, KIN_E, q_scale=q_scale)
-    for k, v in env.items():
-        monkeypatch.setenv(k, v)
     kin = KinGraspOptimizer(path, links, offs, palm_offset=palm.tolist(), num_iters=iters, optimize_target=True,
                             ref_q=[0.0] * q.shape[1], seed=seed)
     res = kin.optimize(*[_dev(a) for a in (q, target, comp)], 1.0, banana_mesh(), verbose=False, trace_rows=True,
-                       kabsch_noise=noise, fused=fused)
+                       kabsch_noise=noise, fused=fused, **loop_path)
     torch.cuda.synchronize()
     return kin, res
 
@@ -223,17 +221,17 @@ def _bits_equal(a, b):
 
 
 @pytest.mark.parametrize("case", ["hand9", "hand16"])
-def test_kin_loop_forms_agree(case, tmp_path, monkeypatch):
+def test_kin_loop_forms_agree(case, tmp_path):
     """test_kin_one_launch_iteration_equals_two_launches and _kin_fk_walk_cache ("alt", "nocache") on the synthetic deep
     hands, E = 67 (a partial last workgroup), 4 iterations: the cached one-launch loop, the loop whose cache is always
     one step stale, the one-launch loop without the cache and the two-launch loop give the same bits."""
     path = ch.write_json(case, tmp_path)
     outs = {}
-    for name, env in (("cached", {"CDX_KIN_FUSED_STEP": "1", "CDX_KIN_FK_CACHE": "1"}),
-                      ("alt", {"CDX_KIN_FUSED_STEP": "alt", "CDX_KIN_FK_CACHE": "1"}),
-                      ("nocache", {"CDX_KIN_FUSED_STEP": "1", "CDX_KIN_FK_CACHE": "0"}),
-                      ("two", {"CDX_KIN_FUSED_STEP": "0", "CDX_KIN_FK_CACHE": "1"})):
-        kin, res = _kin_run(case, path, env, monkeypatch)
+    for name, loop_path in (("cached", dict(split_step=False, fk_cache=True)),
+                            ("alt", dict(split_step="alt", fk_cache=True)),
+                            ("nocache", dict(split_step=False, fk_cache=False)),
+                            ("two", dict(split_step=True, fk_cache=True))):
+        kin, res = _kin_run(case, path, **loop_path)
         outs[name] = ([t.cpu().numpy() for t in res[:3]] + [bool(res[3])] + [kin.best_loss.cpu().numpy()] +
                       [r.cpu().numpy() for r in kin.loss_rows] + [kin.last_tips.cpu().numpy()])
     assert np.isfinite(outs["two"][5]).sum() > KIN_E // 2  # the rows are live
@@ -244,7 +242,7 @@ def test_kin_loop_forms_agree(case, tmp_path, monkeypatch):
 
 
 @pytest.mark.parametrize("case", ["hand9", "hand16"])
-def test_kin_fused_equals_autograd(case, tmp_path, monkeypatch):
+def test_kin_fused_equals_autograd(case, tmp_path):
     """test_kin_optimiser_fused_equals_autograd_at_size's comparison (1e-4 of the largest loss per iteration, the same
     non-finite candidates, final parameters at 1e-4) on the synthetic deep hands with replayed Kabsch noise."""
     path = ch.write_json(case, tmp_path)
@@ -252,7 +250,7 @@ def test_kin_fused_equals_autograd(case, tmp_path, monkeypatch):
     noise = [torch.rand(KIN_E, 3, 3, generator=g, device=DEV, dtype=torch.float64) for _ in range(4)]
     res = {}
     for fused in (True, False):
-        o, out = _kin_run(case, path, {}, monkeypatch, fused=fused, noise=noise, q_scale=0.1)
+        o, out = _kin_run(case, path, fused=fused, noise=noise, q_scale=0.1)
         res[fused] = ([r.double().cpu().numpy() for r in o.loss_rows], [x.detach().double().cpu().numpy() for x in out[:3]])
     (ra, oa), (rb, ob) = res[True], res[False]
     for s, (a, b) in enumerate(zip(ra, rb)):
@@ -267,7 +265,7 @@ def test_kin_fused_equals_autograd(case, tmp_path, monkeypatch):
 
 # ------------------------------------------------------------------ the FK-walk cache must be seen to hit
 @pytest.mark.parametrize("robot", ["iiwa7_allegro", "hand16"])
-def test_fk_walk_cache_hits(robot, tmp_path, monkeypatch):
+def test_fk_walk_cache_hits(robot, tmp_path):
     """After a cached one-launch Kin loop (E = 67, 3 iterations) every lane's tag is the iteration count and every
     q-check slot holds the bits of the final joint row: the next iteration's check would pass.  (A tag or a slot that
     never matches passes every equality test of the cache — walking gives the same bits — and only loses the speed.)"""
@@ -275,8 +273,6 @@ def test_fk_walk_cache_hits(robot, tmp_path, monkeypatch):
     from compliancedex_amd.optimizers import kin_fk_cache_qcheck, kin_fk_cache_view
     from compliancedex_amd.workloads import banana_mesh, config4_kin_inputs
     E, iters = KIN_E, 3
-    monkeypatch.setenv("CDX_KIN_FUSED_STEP", "1")
-    monkeypatch.setenv("CDX_KIN_FK_CACHE", "1")
     if robot == "iiwa7_allegro":
         links, offs, palm, q, target, comp = config4_kin_inputs(E, device=DEV, q_scale=0.05)
         path, depth = robot, 13

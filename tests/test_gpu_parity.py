@@ -510,7 +510,7 @@ def test_sdf_prepared_mesh_equals_one_shot_and_owns_its_faces():
     assert torch.equal(g, 2 * (pts - c))
 
 
-def test_fused_loop_concurrent_queries_equal_sequential(monkeypatch):
+def test_fused_loop_concurrent_queries_equal_sequential():
     """The fused Kin / SDF loop's three TorchSDF queries in one launch (cdx_sdf_query_batch) and on three streams
     (points sorted once by QueryWorkspace.sort) give the same bits as the three run one after the other, over
     several iterations (fresh and reused orders, moved points)."""
@@ -523,25 +523,26 @@ def test_fused_loop_concurrent_queries_equal_sequential(monkeypatch):
     tgt = (lo + (hi - lo) * torch.from_numpy(rng.random((E, T, 3))).to(DEV).float()).contiguous()
     z = torch.zeros(E, 3, device=DEV)
     outs = {}
-    for conc in ("3", "1", "0"):
-        monkeypatch.setenv("CDX_SDF_CONCURRENT", conc)
-        loop = _FusedLoop(E, T, z, tgt.clone(), torch.zeros(E, T, device=DEV), faces, faces * 0.9, DEV)
+    for conc in (3, 1, 0):
+        loop = _FusedLoop(E, T, z, tgt.clone(), torch.zeros(E, T, device=DEV), faces, faces * 0.9, DEV,
+                          concurrent=conc)
+        assert loop.concurrent == conc
         res = []
         for it in range(6):
             moved = (tips + 1e-3 * it).contiguous()
             res.append([t.clone().cpu().numpy() for t in loop.queries(moved, tgt + 1e-3 * it)])
         torch.cuda.synchronize()
         outs[conc] = res
-    for conc in ("3", "1"):
-        for a_it, b_it in zip(outs[conc], outs["0"]):
+    for conc in (3, 1):
+        for a_it, b_it in zip(outs[conc], outs[0]):
             for a, b in zip(a_it, b_it):
                 assert _bitwise_equal_nan_aware(a, b)
 
 
 @pytest.mark.parametrize("robot", ["iiwa7_allegro", "allegro"])
-def test_kin_one_launch_iteration_equals_two_launches(monkeypatch, robot):
+def test_kin_one_launch_iteration_equals_two_launches(robot):
     """cdx_kin_iteration's one-launch Kin iteration (cost, backward, best iterate, Adam and the next fingertips in
-    kin_cost4_kernel<…, STEP>) against cdx_kin_cost + cdx_kin_step (CDX_KIN_FUSED_STEP=0): the per-iteration losses,
+    kin_cost4_kernel<…, STEP>) against cdx_kin_cost + cdx_kin_step (``split_step=True``): the per-iteration losses,
     the best iterate, its loss, margins and normals and the final parameters are the same bits — on the deep
     iiwa7_allegro chain (MAXD 16) and the shallow Allegro hand (MAXD 8)."""
     from compliancedex_amd import KinGraspOptimizer
@@ -556,11 +557,10 @@ def test_kin_one_launch_iteration_equals_two_launches(monkeypatch, robot):
     D = q.shape[1]
     outs = {}
     for one in ("1", "0"):
-        monkeypatch.setenv("CDX_KIN_FUSED_STEP", one)
         kin = KinGraspOptimizer(robot, links, offs, palm_offset=palm.tolist(), num_iters=7, optimize_target=True,
                                 ref_q=[0.0] * D, seed=5)
         args = [torch.from_numpy(a).to(DEV) for a in (q, target, comp)]
-        res = kin.optimize(*args, 1.0, banana_mesh(), verbose=False, trace_rows=True)
+        res = kin.optimize(*args, 1.0, banana_mesh(), verbose=False, trace_rows=True, split_step=one == "0")
         torch.cuda.synchronize()
         outs[one] = ([t.cpu().numpy() for t in res[:3]] + [bool(res[3])] + [kin.best_loss.cpu().numpy()] +
                      [r.cpu().numpy() for r in kin.loss_rows])
@@ -575,10 +575,10 @@ def test_kin_one_launch_iteration_equals_two_launches(monkeypatch, robot):
             assert _bitwise_equal_nan_aware(a, b)
 
 
-def _kin_fk_walk_cache(monkeypatch, mode, E):
+def _kin_fk_walk_cache(mode, E):
     """The one-launch Kin iteration's FK-walk cache (cdx_kin_opt_buffers::fk_state: the step's next-fingertip walk kept
     for the next iteration's FK backward, used only when the candidate's joint row still has the bits it was walked on)
-    against walking every iteration: "nocache" runs the one-launch loop without the cache (CDX_KIN_FK_CACHE=0), "alt"
+    against walking every iteration: "nocache" runs the one-launch loop without the cache (``fk_cache=False``), "alt"
     alternates two-launch and one-launch iterations, so that every one-launch iteration finds the cache one step stale
     (written two iterations back) and must detect it and walk.  Both give the bits of the cached loop and of the
     all-two-launch loop — deep iiwa7_allegro chain, E candidates (a partial last workgroup)."""
@@ -586,16 +586,14 @@ def _kin_fk_walk_cache(monkeypatch, mode, E):
     from compliancedex_amd.workloads import banana_mesh, config4_kin_inputs
     links, offs, palm, q, target, comp = config4_kin_inputs(E, device=DEV, q_scale=0.3)
     outs = {}
-    for name, env in (("cached", {"CDX_KIN_FUSED_STEP": "1", "CDX_KIN_FK_CACHE": "1"}),
-                      (mode, {"CDX_KIN_FUSED_STEP": "alt", "CDX_KIN_FK_CACHE": "1"} if mode == "alt" else
-                       {"CDX_KIN_FUSED_STEP": "1", "CDX_KIN_FK_CACHE": "0"}),
-                      ("two", {"CDX_KIN_FUSED_STEP": "0"})):
-        for k, v in env.items():
-            monkeypatch.setenv(k, v)
+    for name, path in (("cached", dict(split_step=False, fk_cache=True)),
+                       (mode, dict(split_step="alt", fk_cache=True) if mode == "alt" else
+                        dict(split_step=False, fk_cache=False)),
+                       ("two", dict(split_step=True))):
         kin = KinGraspOptimizer("iiwa7_allegro", links, offs, palm_offset=palm.tolist(), num_iters=8,
                                 optimize_target=True, ref_q=[0.0] * q.shape[1], seed=5)
         args = [torch.from_numpy(a).to(DEV) for a in (q, target, comp)]
-        res = kin.optimize(*args, 1.0, banana_mesh(), verbose=False, trace_rows=True)
+        res = kin.optimize(*args, 1.0, banana_mesh(), verbose=False, trace_rows=True, **path)
         torch.cuda.synchronize()
         outs[name] = ([t.cpu().numpy() for t in res[:3]] + [kin.best_loss.cpu().numpy()] +
                       [r.cpu().numpy() for r in kin.loss_rows] + [kin.last_tips.cpu().numpy()])
@@ -608,23 +606,62 @@ def _kin_fk_walk_cache(monkeypatch, mode, E):
 
 
 @pytest.mark.parametrize("mode", ["alt", "nocache"])
-def test_kin_fk_walk_cache_equals_walking(monkeypatch, mode):
+def test_kin_fk_walk_cache_equals_walking(mode):
     """_kin_fk_walk_cache at E = 3000."""
-    _kin_fk_walk_cache(monkeypatch, mode, 3000)
+    _kin_fk_walk_cache(mode, 3000)
 
 
 @pytest.mark.parametrize("mode", ["alt", "nocache"])
-def test_kin_fk_walk_cache_equals_walking_unaligned_tail(monkeypatch, mode):
+def test_kin_fk_walk_cache_equals_walking_unaligned_tail(mode):
     """_kin_fk_walk_cache at E = 3001: with D = 23 the last workgroup's joint rows end 3 floats into a 16-byte unit,
     where the kernel's row check re-reads the block's first unit (cdx_kin.hip, the cache's row compare) — the last
     candidate's tail joints are then compared with candidate e0's first joints, one row reading another.  The results
     must still be those of walking, to the bit."""
-    _kin_fk_walk_cache(monkeypatch, mode, 3001)
+    _kin_fk_walk_cache(mode, 3001)
 
 
-def test_sdf_one_launch_iteration_equals_two_launches(monkeypatch):
+def test_kin_loop_ignores_retired_env_switches(monkeypatch):
+    """The package reads no A/B environment variable (as the library, tests/test_screen.py): with the four retired
+    switches set to their non-default values, a KinGraspOptimizer loop (iiwa7_allegro, E = 67 — a partial last
+    workgroup —, 3 iterations) still takes the default path: one cdx_kin_iteration launch per iteration, cdx_kin_step
+    only to finalise, the FK-walk cache allocated, the three queries in one launch, re-sorted every 16 iterations."""
+    from compliancedex_amd import KinGraspOptimizer
+    from compliancedex_amd import _native as N
+    from compliancedex_amd.workloads import banana_mesh, config4_kin_inputs
+    for k, v in (("CDX_KIN_FUSED_STEP", "0"), ("CDX_KIN_FK_CACHE", "0"), ("CDX_SDF_CONCURRENT", "0"),
+                 ("CDX_SDF_RESORT", "1")):
+        monkeypatch.setenv(k, v)
+    E, iters = 67, 3
+    lib = N.load()
+    calls = {"iteration": 0, "step": []}
+    real_iteration, real_step = lib.cdx_kin_iteration, lib.cdx_kin_step
+
+    def iteration(*a):
+        calls["iteration"] += 1
+        return real_iteration(*a)
+
+    def step(chain, cfg, buf, n, T, s, finalize, stream):
+        calls["step"].append((s, finalize))
+        return real_step(chain, cfg, buf, n, T, s, finalize, stream)
+
+    monkeypatch.setattr(lib, "cdx_kin_iteration", iteration, raising=False)
+    monkeypatch.setattr(lib, "cdx_kin_step", step, raising=False)
+    links, offs, palm, q, target, comp = config4_kin_inputs(E, device=DEV, q_scale=0.3)
+    kin = KinGraspOptimizer("iiwa7_allegro", links, offs, palm_offset=palm.tolist(), num_iters=iters,
+                            optimize_target=True, ref_q=[0.0] * q.shape[1], seed=5)
+    kin.optimize(*[torch.from_numpy(a).to(DEV) for a in (q, target, comp)], 1.0, banana_mesh(), verbose=False,
+                 trace_rows=True)
+    torch.cuda.synchronize()
+    assert calls["iteration"] == iters
+    assert calls["step"] == [(iters, 1)]
+    loop = kin.last_loop
+    assert getattr(loop, "fk_state", None) is not None
+    assert loop.concurrent == 3 and loop.resort == 16
+
+
+def test_sdf_one_launch_iteration_equals_two_launches():
     """The SDF optimiser's one-launch iteration (kin_cost4_kernel<8, false, STEP>: cost, backward, best iterate, RMSprop
-    and the box clamps) against cdx_kin_cost + cdx_kin_step (CDX_KIN_FUSED_STEP=0): the same bits, with fingertips
+    and the box clamps) against cdx_kin_cost + cdx_kin_step (``split_step=True``): the same bits, with fingertips
     both inside and outside the clamp box."""
     from compliancedex_amd import SDFGraspOptimizer
     from compliancedex_amd.optimizer import FINGERTIP_LB, FINGERTIP_UB
@@ -640,10 +677,9 @@ def test_sdf_one_launch_iteration_equals_two_launches(monkeypatch):
     comp = np.tile(np.array([10.0, 10.0, 10.0, 20.0], np.float32), (E, 1))
     outs = {}
     for one in ("1", "0"):
-        monkeypatch.setenv("CDX_KIN_FUSED_STEP", one)
         opt = SDFGraspOptimizer([FINGERTIP_LB, FINGERTIP_UB], num_iters=7, optimize_target=True, seed=5)
         res = opt.optimize(*(torch.from_numpy(a).to(DEV) for a in (tips, target, comp)), 1, banana_mesh(),
-                           verbose=False, trace_rows=True)
+                           verbose=False, trace_rows=True, split_step=one == "0")
         torch.cuda.synchronize()
         outs[one] = ([t.cpu().numpy() for t in res[:3]] + [bool(res[3])] + [opt.best_loss.cpu().numpy()] +
                      [r.cpu().numpy() for r in opt.loss_rows])
@@ -682,11 +718,11 @@ def test_sdf_stale_order_gives_the_same_results():
             assert _bitwise_equal_nan_aware(x, y)
 
 
-def test_sdf_workspace_order_only_from_a_sort(monkeypatch):
+def test_sdf_workspace_order_only_from_a_sort():
     """a query on a mesh with NaN-capable faces (SDF_MESH_EXACT: brute-force tile rule) neither sorts nor
     walks, so it must not leave a workspace looking as if it held an order.  A reuse_order query or a query_batch on
     a culled mesh through that workspace raises instead of walking an unwritten order; the fused loop's sequential
-    variant (CDX_SDF_CONCURRENT=0) with an EXACT deflated mesh and a CULLED full mesh sorts explicitly and gives the
+    variant (``concurrent=0``) with an EXACT deflated mesh and a CULLED full mesh sorts explicitly and gives the
     same bits as fresh one-shot queries."""
     from compliancedex_amd import PreparedMesh, compute_sdf_with_faces
     from compliancedex_amd import _native as N
@@ -718,11 +754,10 @@ def test_sdf_workspace_order_only_from_a_sort(monkeypatch):
     b = [t.cpu().numpy() for t in compute_sdf_with_faces(pts, faces)[:4]]
     for x, y in zip(a, b):
         assert _bitwise_equal_nan_aware(x, y)
-    monkeypatch.setenv("CDX_SDF_CONCURRENT", "0")
     E, T = P // 4, 4
     tgt = (lo + (hi - lo) * torch.from_numpy(rng.random((E, T, 3))).to(DEV).float()).contiguous()
     loop = _FusedLoop(E, T, torch.zeros(E, 3, device=DEV), tgt.clone(), torch.zeros(E, T, device=DEV), faces,
-                      faces_exact, DEV)
+                      faces_exact, DEV, concurrent=0)
     assert loop.mesh_def.kind == N.SDF_MESH_EXACT and loop.concurrent == 0
     for it in range(3):
         moved = (pts + 1e-3 * it).contiguous()

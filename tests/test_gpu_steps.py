@@ -305,12 +305,11 @@ def test_kin_one_launch_step_skips_the_commit_like_two_launches(monkeypatch):
     monkeypatch.setattr(lib, "cdx_kin_step", step, raising=False)
     outs = {}
     for one in ("1", "0"):
-        monkeypatch.setenv("CDX_KIN_FUSED_STEP", one)
         kin = KinGraspOptimizer(st.FUSED["robot"], x["links"], x["offsets"], palm_offset=x["palm"].tolist(),
                                 num_iters=iters, optimize_target=True, ref_q=[0.0] * x["q"].shape[1], device=DEV)
         res = kin.optimize(*[torch.from_numpy(x[k]).to(DEV) for k in ("q", "target", "comp")], 1.0, banana_mesh(),
                            verbose=False, kabsch_noise=[torch.from_numpy(n).to(DEV) for n in x["noise"]],
-                           trace_rows=True)
+                           trace_rows=True, split_step=one == "0")
         torch.cuda.synchronize()
         loop = kin.last_loop
         outs[one] = dict(opt_pose=res[0], opt_comp=res[1], opt_target=res[2], opt_value=kin.best_loss,

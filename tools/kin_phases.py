@@ -31,11 +31,10 @@ def main():
     links, offs, palm, q, target, comp = config4_kin_inputs(E, device="cuda", q_scale=0.05)
     out = {}
     for cache in ("1", "0"):
-        os.environ["CDX_KIN_FK_CACHE"] = cache
         kin = KinGraspOptimizer("iiwa7_allegro", links, offs, palm_offset=palm.tolist(), num_iters=12,
                                 optimize_target=True, ref_q=[0.0] * 23)
         args = [torch.from_numpy(a).to("cuda") for a in (q, target, comp)]
-        kin.optimize(*args, 1, banana_mesh(), verbose=False)
+        kin.optimize(*args, 1, banana_mesh(), verbose=False, fk_cache=cache == "1")
         torch.cuda.synchronize()
         lib = N.load()
         buf = (ctypes.c_uint64 * (4096 * 16))()
