@@ -305,6 +305,16 @@ _SIGS = {
     "cdx_gpis_mode_abi_sizes": (None, [C.POINTER(C.c_size_t)]),
 }
 
+# (getter, the structs it reports in its order, label of the group): load() holds every layout to the library's sizeof
+_ABI_SIZES = [
+    ("cdx_abi_sizes", [CdxGpis, CdxBody, CdxChain, CdxProblem, CdxCollision, CdxAdam, CdxOptBuffers, CdxForceEq,
+                       CdxScreenReport, CdxKinParams, CdxKinOpt, CdxKinOptBuffers, CdxSdfBatchQuery], "core"),
+    ("cdx_gpis_mode_abi_sizes", [CdxGpisModeParams, CdxGpisModeOpt, CdxGpisModeBuffers], "GPIS mode"),
+    ("cdx_ik_abi_size", [CdxIkParams], "IK"),
+    ("cdx_wrench_abi_size", [CdxWrenchParams], "wrench"),
+    ("cdx_hand_abi_sizes", [CdxHand, CdxHandParams], "hand"),
+]
+
 _lib = None
 _lock = threading.Lock()
 
@@ -328,30 +338,17 @@ def load():
             fn = getattr(lib, name)
             fn.restype = res
             fn.argtypes = args
-        sizes = (C.c_size_t * 13)()
-        lib.cdx_abi_sizes(sizes)
-        mine = [C.sizeof(CdxGpis), C.sizeof(CdxBody), C.sizeof(CdxChain), C.sizeof(CdxProblem),
-                C.sizeof(CdxCollision), C.sizeof(CdxAdam), C.sizeof(CdxOptBuffers), C.sizeof(CdxForceEq),
-                C.sizeof(CdxScreenReport), C.sizeof(CdxKinParams), C.sizeof(CdxKinOpt), C.sizeof(CdxKinOptBuffers),
-                C.sizeof(CdxSdfBatchQuery)]
-        if list(sizes) != mine:
-            raise ImportError(f"ABI struct size mismatch: library {list(sizes)} vs binding {mine}")
-        sizes = (C.c_size_t * 3)()
-        lib.cdx_gpis_mode_abi_sizes(sizes)
-        mine = [C.sizeof(CdxGpisModeParams), C.sizeof(CdxGpisModeOpt), C.sizeof(CdxGpisModeBuffers)]
-        if list(sizes) != mine:
-            raise ImportError(f"ABI struct size mismatch (GPIS mode): library {list(sizes)} vs binding {mine}")
-        if lib.cdx_ik_abi_size() != C.sizeof(CdxIkParams):
-            raise ImportError(f"ABI struct size mismatch (IK): library {lib.cdx_ik_abi_size()} vs binding "
-                              f"{C.sizeof(CdxIkParams)}")
-        if lib.cdx_wrench_abi_size() != C.sizeof(CdxWrenchParams):
-            raise ImportError(f"ABI struct size mismatch (wrench): library {lib.cdx_wrench_abi_size()} vs binding "
-                              f"{C.sizeof(CdxWrenchParams)}")
-        sizes = (C.c_size_t * 2)()
-        lib.cdx_hand_abi_sizes(sizes)
-        mine = [C.sizeof(CdxHand), C.sizeof(CdxHandParams)]
-        if list(sizes) != mine:
-            raise ImportError(f"ABI struct size mismatch (hand): library {list(sizes)} vs binding {mine}")
+        for getter, structs, label in _ABI_SIZES:
+            fn = getattr(lib, getter)
+            if fn.argtypes:  # fills an array, one size per struct
+                sizes = (C.c_size_t * len(structs))()
+                fn(sizes)
+                theirs = list(sizes)
+            else:  # returns the size of its one struct
+                theirs = [fn()]
+            mine = [C.sizeof(s) for s in structs]
+            if theirs != mine:
+                raise ImportError(f"ABI struct size mismatch ({label}): library {theirs} vs binding {mine}")
         info = build_info()
         if not info["matches"] and "CDX_LIB" not in os.environ:
             import warnings

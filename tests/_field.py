@@ -1,6 +1,4 @@
 """Helpers shared by test_field_cpu.py and test_gpu_field.py: the host surface extract and the rule in numpy."""
-import ctypes as C
-
 import numpy as np
 
 from tests._host import host, p
@@ -16,9 +14,6 @@ def point_axes(lb, ub, steps):
 def host_extract(mean, normal, steps, flip, axes, capacity=None, dtype=None):
     """cdxh_surface_extract on host arrays: (count, cells, points, normals) with `capacity` rows (default: all)."""
     lib = host()
-    lib.cdxh_surface_extract.restype = C.c_int64
-    lib.cdxh_surface_extract.argtypes = [C.c_void_p, C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_void_p,
-                                         C.c_void_p, C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p]
     mean = np.ascontiguousarray(mean)
     normal = np.ascontiguousarray(normal, dtype=mean.dtype)
     if dtype is None:

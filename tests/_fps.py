@@ -1,6 +1,5 @@
 """Helpers shared by test_fps_cpu.py and test_gpu_fps.py: the farthest-point sampling rule of csrc/cdx_fps.h stated in
 numpy, the host build (cdxh_fps) and the clouds both files sample."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -34,9 +33,6 @@ def numpy_fps(X, K, start=0):
 def host_fps(X, K, start=0, dtype=None):
     """cdxh_fps on a [P, 3] or [B, P, 3] host array in its own dtype: (rc, sel, radius, points)."""
     lib = host()
-    lib.cdxh_fps.restype = C.c_int
-    lib.cdxh_fps.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                             C.c_void_p]
     X = np.ascontiguousarray(X)
     B, P = (X.shape[0], X.shape[1]) if X.ndim == 3 else (1, X.shape[0])
     if dtype is None:

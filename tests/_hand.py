@@ -250,24 +250,8 @@ def family(case, S, pairs):
 
 
 # ------------------------------------------------------------------ the host build
-def host_lib():
-    lib = _host.host()
-    if not getattr(lib, "_hand_sigs", False):
-        P, I64 = C.c_void_p, C.c_int64
-        lib.cdxh_hand_bytes.restype = C.c_size_t
-        lib.cdxh_hand_bytes.argtypes = [C.c_int32, C.c_int32]
-        lib.cdxh_hand_prepare.argtypes = [C.c_int32, C.c_int32, P, P, P, C.c_int32, P, P, C.POINTER(N.CdxHand)]
-        lib.cdxh_hand_spheres.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxHand), I64, P, P, P, P, P]
-        lib.cdxh_hand_cost.argtypes = [C.POINTER(N.CdxHand), C.POINTER(N.CdxHandParams), I64] + [P] * 7
-        lib.cdxh_hand_pullback.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxHand), I64] + [P] * 6
-        lib.cdxh_hand_sincos.argtypes = [P, I64, P, P]
-        lib.cdxh_hand_sincos.restype = None
-        lib._hand_sigs = True
-    return lib
-
-
-def ptr(a):
-    return None if a is None else a.ctypes.data_as(C.c_void_p)
+host_lib = _host.host
+ptr = _host.p
 
 
 def host_prepare_raw(n_bodies, local, radius, body, pairs):

@@ -53,11 +53,6 @@ def presets(hs, E, seed=None):
 def host_term(chain, hand, par, E, poses, centers, dist, gdist, po, weight, accumulate, outs):
     """cdxh_hand_term on numpy arrays; ``outs``: dict of arrays written in place (a missing key: NULL) → rc."""
     lib = H.host_lib()
-    if not getattr(lib, "_hand_term_sig", False):
-        P = C.c_void_p
-        lib.cdxh_hand_term.argtypes = ([C.POINTER(N.CdxChain), C.POINTER(N.CdxHand), C.POINTER(N.CdxHandParams), C.c_int64] +
-                                       [P] * 5 + [C.c_double, C.c_int32] + [P] * 6)
-        lib._hand_term_sig = True
     return lib.cdxh_hand_term(chain, hand, par, E, H.ptr(poses), H.ptr(centers), H.ptr(dist), H.ptr(gdist), H.ptr(po),
                               weight, accumulate, *[H.ptr(outs.get(k)) for k in OUTS])
 

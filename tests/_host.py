@@ -1,30 +1,10 @@
-"""Test-only loader of libcdx_host.so (host build of the per-candidate device code)."""
+"""numpy wrappers of libcdx_host.so (host build of the per-candidate device code; bound in compliancedex_amd._host)."""
 import ctypes as C
-import os
 
 import numpy as np
 
-from compliancedex_amd._native import LIB_DIR, CdxChain, CdxProblem
-
-_lib = None
-
-
-def host():
-    global _lib
-    if _lib is None:
-        path = os.path.join(LIB_DIR, "libcdx_host.so")
-        if not os.path.exists(path):
-            from compliancedex_amd.build import build_host
-            build_host()
-        _lib = C.CDLL(path)
-        P = C.c_void_p
-        _lib.cdxh_n_queries.restype = C.c_int64
-        _lib.cdxh_n_queries.argtypes = [C.POINTER(CdxProblem), C.c_int64]
-    return _lib
-
-
-def p(a):
-    return a.ctypes.data_as(C.c_void_p)
+from compliancedex_amd._host import load as host, ptr as p
+from compliancedex_amd._native import CdxChain, CdxProblem
 
 
 def fk_forward(chain: CdxChain, q):
@@ -32,7 +12,7 @@ def fk_forward(chain: CdxChain, q):
     B = q.shape[0]
     pos = np.zeros((B, chain.n_tips * 3), np.float32)
     quat = np.zeros((B, chain.n_tips * 4), np.float32)
-    rc = host().cdxh_fk_forward(C.byref(chain), p(q), C.c_int64(B), p(pos), p(quat))
+    rc = host().cdxh_fk_forward(C.byref(chain), p(q), B, p(pos), p(quat))
     assert rc == 0, rc
     return pos, quat
 
@@ -41,7 +21,7 @@ def fk_backward(chain: CdxChain, q, gpos):
     q = np.ascontiguousarray(q, dtype=np.float32)
     gpos = np.ascontiguousarray(gpos, dtype=np.float32)
     gq = np.zeros_like(q)
-    rc = host().cdxh_fk_backward(C.byref(chain), p(q), C.c_int64(q.shape[0]), p(gpos), p(gq))
+    rc = host().cdxh_fk_backward(C.byref(chain), p(q), q.shape[0], p(gpos), p(gq))
     assert rc == 0, rc
     return gq
 
@@ -52,7 +32,7 @@ def closure_queries(prob: CdxProblem, q, target, palm):
     X = np.zeros((Mq, 3))
     q, target = np.ascontiguousarray(q, np.float64), np.ascontiguousarray(target, np.float64)
     pp, po = np.ascontiguousarray(palm[:, :3]), np.ascontiguousarray(palm[:, 3:])
-    rc = host().cdxh_closure_queries(C.byref(prob), C.c_int64(E), p(q), p(target), p(pp), p(po), p(X))
+    rc = host().cdxh_closure_queries(C.byref(prob), E, p(q), p(target), p(pp), p(po), p(X))
     assert rc == 0, rc
     return X
 
@@ -68,7 +48,7 @@ def closure_cost(prob: CdxProblem, q, comp, target, palm, noise, gp):
                grad_comp=np.zeros((E, T)), grad_target=np.zeros((E, T, 3)), grad_palm_pos=np.zeros((E, 3)),
                grad_palm_ori=np.zeros((E, 3)), flip=np.zeros(K * E, np.int32))
     arrs = [np.ascontiguousarray(gp[k], np.float64) for k in ("mean", "gmean", "normal", "std", "gstd")]
-    rc = host().cdxh_closure_cost(C.byref(prob), C.c_int64(E), p(q), p(comp), p(target), p(pp), p(po), p(noise),
+    rc = host().cdxh_closure_cost(C.byref(prob), E, p(q), p(comp), p(target), p(pp), p(po), p(noise),
                              *[p(a) for a in arrs],
                              *[p(out[k]) for k in ("total_loss", "total_margin", "grad_q", "grad_comp", "grad_target",
                                                    "grad_palm_pos", "grad_palm_ori", "flip")])
@@ -89,7 +69,7 @@ def sdf_forward(points, faces):
     P, F = len(points), len(faces)
     d = np.zeros(P, np.float32); s = np.zeros(P, np.int32); n = np.zeros((P, 3), np.float32)
     c = np.zeros((P, 3), np.float32); f = np.zeros(P, np.int32)
-    host().cdxh_sdf_forward(p(points), C.c_int64(P), p(faces), C.c_int64(F), p(d), p(s), p(n), p(c), p(f))
+    host().cdxh_sdf_forward(p(points), P, p(faces), F, p(d), p(s), p(n), p(c), p(f))
     return d, s, n, c, f
 
 
@@ -99,7 +79,7 @@ def collision(desc, q, palm):
     E, D = q.shape
     cost, g_q = np.zeros(E), np.zeros((E, D))
     g_pp, g_po = np.zeros((E, 3)), np.zeros((E, 3))
-    rc = host().cdxh_collision(C.byref(desc), C.c_int64(E), p(q), p(pp), p(po), p(cost), p(g_q), p(g_pp), p(g_po))
+    rc = host().cdxh_collision(C.byref(desc), E, p(q), p(pp), p(po), p(cost), p(g_q), p(g_pp), p(g_po))
     assert rc == 0, rc
     return cost, g_q, np.concatenate([g_pp, g_po], 1)
 
@@ -110,7 +90,7 @@ def force_eq(desc, tip, target, comp, normal, noise, g_reward, g_fn):
     reward, margin, fn = np.zeros(B), np.zeros((B, T)), np.zeros((B, T))
     flip = np.zeros(B, np.int32)
     g_tip, g_target, g_comp = np.zeros((B, T, 3)), np.zeros((B, T, 3)), np.zeros((B, T))
-    host().cdxh_force_eq(C.byref(desc), C.c_int64(B), *(p(x) for x in a), p(reward), p(margin), p(fn), p(flip),
+    host().cdxh_force_eq(C.byref(desc), B, *(p(x) for x in a), p(reward), p(margin), p(fn), p(flip),
                          p(g_tip), p(g_target), p(g_comp))
     return dict(reward=reward, margin=margin, force_norm=fn, flip=flip, grad_tip=g_tip, grad_target=g_target,
                 grad_comp=g_comp)

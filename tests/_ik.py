@@ -20,9 +20,7 @@ def fk_jacobian_host(desc: CdxChain, q, ang=True):
     B, T, D = q.shape[0], desc.n_tips, desc.n_dofs
     lin = np.full((B, T, 3, D), 7.0, np.float32)
     a = np.full((B, T, 3, D), 7.0, np.float32) if ang else None
-    fn = host().cdxh_fk_jacobian
-    fn.restype = C.c_int
-    rc = fn(C.byref(desc), p(q), C.c_int64(B), p(lin), p(a) if ang else None)
+    rc = host().cdxh_fk_jacobian(C.byref(desc), p(q), B, p(lin), p(a))
     assert rc == 0, rc
     return lin, a
 
@@ -40,11 +38,8 @@ def ik_solve_host(desc: CdxChain, params: CdxIkParams, q0, target, palm=None, pa
     err = np.full((E, T), 7.0)
     iters = np.full(E, -7, np.int32)
     status = np.full(E, -7, np.int32)
-    fn = host().cdxh_ik_solve
-    fn.restype = C.c_int
-    rc = fn(C.byref(desc), C.byref(params), C.c_int64(E), p(q0), C.c_int32(F64 if q0.dtype == np.float64 else F32),
-            p(target), None if palm is None else p(palm), po, None if w is None else p(w), p(q), p(err), p(iters),
-            p(status))
+    rc = host().cdxh_ik_solve(C.byref(desc), C.byref(params), E, p(q0), F64 if q0.dtype == np.float64 else F32,
+                              p(target), p(palm), po, p(w), p(q), p(err), p(iters), p(status))
     assert rc == 0, rc
     return dict(q=q, err=err, iters=iters, status=status)
 

@@ -1,6 +1,5 @@
 """Helpers shared by test_knn_cpu.py and test_gpu_knn.py: the rule of csrc/cdx_knn.h stated in numpy (neighbours,
 covariance, Jacobi, normals, the outlier mask), the host build's bindings and the cases both files run."""
-import ctypes as C
 
 import numpy as np
 
@@ -169,9 +168,6 @@ def _dtype(X):
 def host_knn(X, K, Q=None, max_d2=INF, mode=SCAN, dtype=None):
     """cdxh_knn on host arrays in their own dtype: (rc, idx, d2, count)."""
     lib = host()
-    lib.cdxh_knn.restype = C.c_int
-    lib.cdxh_knn.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                             C.c_void_p, C.c_void_p, C.c_void_p]
     X = np.ascontiguousarray(X)
     Qc = None if Q is None else np.ascontiguousarray(Q, dtype=X.dtype)
     M = len(X) if Q is None else len(Qc)
@@ -187,9 +183,6 @@ def host_knn(X, K, Q=None, max_d2=INF, mode=SCAN, dtype=None):
 def host_normals(X, idx, count, eye=None):
     """cdxh_cloud_normals: (normals, eigenvalues, cov)."""
     lib = host()
-    lib.cdxh_cloud_normals.restype = C.c_int
-    lib.cdxh_cloud_normals.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64,
-                                       C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     X = np.ascontiguousarray(X)
     idx, count = np.ascontiguousarray(idx, np.int64), np.ascontiguousarray(count, np.int32)
     P, K = idx.shape
@@ -203,8 +196,6 @@ def host_normals(X, idx, count, eye=None):
 
 def host_sym3_eig(cov):
     lib = host()
-    lib.cdxh_sym3_eig.restype = None
-    lib.cdxh_sym3_eig.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     cov = np.ascontiguousarray(cov, np.float64)
     w, V = np.zeros((len(cov), 3)), np.zeros((len(cov), 3, 3))
     lib.cdxh_sym3_eig(p(cov), len(cov), p(w), p(V))
@@ -214,8 +205,6 @@ def host_sym3_eig(cov):
 def host_grid(X):
     """cdxh_knn_grid of a float64 cloud: dict(info [4] = lo, inv; dims [3]; cell [P, 3]; below, above [3, MAX_DIM])."""
     lib = host()
-    lib.cdxh_knn_grid.restype = C.c_int
-    lib.cdxh_knn_grid.argtypes = [C.c_void_p, C.c_int64] + [C.c_void_p] * 5
     X = np.ascontiguousarray(X, np.float64)
     g = dict(info=np.zeros(4), dims=np.zeros(3, np.int32), cell=np.zeros((len(X), 3), np.int32),
              below=np.zeros((3, MAX_DIM)), above=np.zeros((3, MAX_DIM)))
@@ -226,8 +215,6 @@ def host_grid(X):
 def host_ring_bound(g, Q, r):
     """(cq int32 [M, 3], bound f64 [M], none bool [M]) of cdx::knn_ring_bound at ring r, in the kernel's arithmetic."""
     lib = host()
-    lib.cdxh_knn_ring_bound.restype = C.c_int
-    lib.cdxh_knn_ring_bound.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_int32] + [C.c_void_p] * 3
     Q = np.ascontiguousarray(Q, np.float64)
     cq, bound, none = np.zeros((len(Q), 3), np.int32), np.zeros(len(Q)), np.zeros(len(Q), np.int32)
     assert lib.cdxh_knn_ring_bound(p(g["info"]), p(g["dims"]), p(g["below"]), p(g["above"]), p(Q), len(Q), r, p(cq),

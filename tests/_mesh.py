@@ -1,6 +1,5 @@
 """Helpers shared by test_mesh_cpu.py and test_gpu_mesh.py: the marching-tetrahedra rule of csrc/cdx_mesh.h stated in
 numpy (written from the rule's prose, not from the header), the host build's binding, and topology checks."""
-import ctypes as C
 import itertools
 
 import numpy as np
@@ -108,9 +107,6 @@ def host_mesh(mean, axes, vcap=None, fcap=None, dtype=None):
     """cdxh_mesh_extract on host arrays: ((V, F), vertices, keys, faces) with vcap / fcap rows (default: all), rows
     past the capacity left at guard values."""
     lib = host()
-    lib.cdxh_mesh_extract.restype = C.c_int
-    lib.cdxh_mesh_extract.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int64,
-                                      C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     mean = np.ascontiguousarray(mean)
     s = mean.shape[0]
     if dtype is None:
@@ -134,9 +130,6 @@ def host_mesh(mean, axes, vcap=None, fcap=None, dtype=None):
 def host_refine(mean, fv, axes, keys, state=None):
     """cdxh_mesh_refine: fv None starts the state from the lattice, else one step: (state [5, V], vertices [V, 3])."""
     lib = host()
-    lib.cdxh_mesh_refine.restype = C.c_int
-    lib.cdxh_mesh_refine.argtypes = [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p,
-                                     C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p]
     mean = np.ascontiguousarray(mean)
     dtype = {np.dtype(np.float32): F32, np.dtype(np.float64): F64}[mean.dtype]
     ax = [np.ascontiguousarray(a, np.float64) for a in axes]

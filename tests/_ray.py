@@ -1,7 +1,6 @@
 """Helpers shared by test_ray_cpu.py and test_gpu_ray.py: the ray casting and depth unprojection rules of csrc/cdx_ray.h
 stated in numpy, the host build (cdxh_ray_cast, cdxh_pixel_rays, cdxh_depth_unproject, cdxh_ray_ball_miss) and the
 meshes and rays both files cast."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -108,9 +107,6 @@ def numpy_unproject(depth, intr, scale, trunc, z_max=None, M=None, stride=1):
 
 def host_cast(faces, origins, dirs, tmin=0.0, tmax=np.inf):
     lib = host()
-    lib.cdxh_ray_cast.restype = C.c_int
-    lib.cdxh_ray_cast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
-                                  C.c_void_p, C.c_void_p, C.c_void_p]
     faces = np.ascontiguousarray(faces, np.float32)
     o, d = np.ascontiguousarray(origins, np.float64), np.ascontiguousarray(dirs, np.float64)
     R = len(o)
@@ -122,8 +118,6 @@ def host_cast(faces, origins, dirs, tmin=0.0, tmax=np.inf):
 
 def host_pixel_rays(W, H, intr, M):
     lib = host()
-    lib.cdxh_pixel_rays.restype = C.c_int
-    lib.cdxh_pixel_rays.argtypes = [C.c_int32, C.c_int32, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     intr, M = np.ascontiguousarray(intr, np.float64), np.ascontiguousarray(M, np.float64)
     o, d = np.zeros((H * W, 3)), np.zeros((H * W, 3))
     assert lib.cdxh_pixel_rays(W, H, p(intr), p(M), p(o), p(d)) == 0
@@ -132,9 +126,6 @@ def host_pixel_rays(W, H, intr, M):
 
 def host_unproject(depth, intr, scale, trunc, z_max=None, M=None, stride=1):
     lib = host()
-    lib.cdxh_depth_unproject.restype = C.c_int64
-    lib.cdxh_depth_unproject.argtypes = [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_void_p, C.c_double,
-                                         C.c_double, C.c_double, C.c_void_p, C.c_int64, C.c_void_p]
     depth = np.ascontiguousarray(depth)
     dt = {np.dtype(np.float32): F32, np.dtype(np.float64): F64, np.dtype(np.uint16): U16}[depth.dtype]
     H, W = depth.shape
@@ -150,8 +141,6 @@ def host_unproject(depth, intr, scale, trunc, z_max=None, M=None, stride=1):
 
 def host_ball_miss(origins, dirs, s0, s1, balls):
     lib = host()
-    lib.cdxh_ray_ball_miss.restype = None
-    lib.cdxh_ray_ball_miss.argtypes = [C.c_void_p] * 5 + [C.c_int64, C.c_void_p, C.c_void_p]
     o, d = np.ascontiguousarray(origins, np.float64), np.ascontiguousarray(dirs, np.float64)
     s0, s1 = np.ascontiguousarray(s0, np.float64), np.ascontiguousarray(s1, np.float64)
     balls = np.ascontiguousarray(balls, np.float32)

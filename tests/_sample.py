@@ -1,7 +1,6 @@
 """Helpers shared by test_sample_cpu.py and test_gpu_sample.py: the surface-sampling rule of csrc/cdx_sample.h stated in
 numpy (Philox4x32-10, prepare, draw), the host build (cdxh_sample_prepare / cdxh_sample_draw / cdxh_philox4x32_10) and
 the meshes both files sample."""
-import ctypes as C
 import os
 
 import numpy as np
@@ -93,8 +92,6 @@ def _dtype(faces):
 
 def host_philox(counter, key):
     lib = host()
-    lib.cdxh_philox4x32_10.restype = None
-    lib.cdxh_philox4x32_10.argtypes = [C.c_void_p] * 3
     c, k, out = np.array(counter, np.uint32), np.array(key, np.uint32), np.zeros(4, np.uint32)
     lib.cdxh_philox4x32_10(p(c), p(k), p(out))
     return tuple(int(x) for x in out)
@@ -103,8 +100,6 @@ def host_philox(counter, key):
 def host_prepare(faces, dtype=None, F=None):
     """cdxh_sample_prepare on a host array in its own dtype: (rc, C uint64 [F], info)."""
     lib = host()
-    lib.cdxh_sample_prepare.restype = C.c_int
-    lib.cdxh_sample_prepare.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
     faces = np.ascontiguousarray(faces)
     cdf = np.zeros(len(faces), np.uint64)
     info = np.full(1, -1, np.int32)
@@ -116,9 +111,6 @@ def host_prepare(faces, dtype=None, F=None):
 def host_draw(faces, cdf, seed, first, K):
     """cdxh_sample_draw: (rc, points, face, bary, normal)."""
     lib = host()
-    lib.cdxh_sample_draw.restype = C.c_int
-    lib.cdxh_sample_draw.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
     faces = np.ascontiguousarray(faces)
     rows = max(K, 0)
     points, face = np.full((rows, 3), -7.0), np.full(rows, -9, np.int64)

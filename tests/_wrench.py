@@ -32,10 +32,8 @@ def solve_host(tips, normals, **kw):
     tips, normals = np.ascontiguousarray(tips, np.float64), np.ascontiguousarray(normals, np.float64)
     E, T = tips.shape[:2]
     out = outputs(E, T)
-    fn = host().cdxh_min_wrench
-    fn.restype = C.c_int
     par = params(T, **kw)
-    rc = fn(C.byref(par), C.c_int64(E), p(tips), p(normals), *[p(out[k]) for k in FIELDS])
+    rc = host().cdxh_min_wrench(C.byref(par), E, p(tips), p(normals), *[p(out[k]) for k in FIELDS])
     assert rc == 0, rc
     return out
 

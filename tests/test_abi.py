@@ -1,15 +1,85 @@
-"""The C-ABI library loads (no GPU needed) and exports every symbol include/cdx.h declares;
-binding struct layouts match the library's sizeof.  CPU only."""
+"""The C-ABI library loads (no GPU needed) and exports every symbol include/cdx.h declares; binding struct layouts
+match the library's sizeof; both ctypes tables (_native._SIGS, _host._SIGS) agree with the C text in names, arity and
+argument classes.  CPU only."""
+import ctypes as C
 import os
 import re
 
 from tests.conftest import REPO
 
+# C scalar type → the ctypes that may bind it (int and int32_t are the same size on this ABI; the tables mix them)
+SCALARS = {"int": (C.c_int, C.c_int32), "int32_t": (C.c_int, C.c_int32), "int64_t": (C.c_int64,),
+           "uint64_t": (C.c_uint64,), "size_t": (C.c_size_t,), "double": (C.c_double,)}
+
+
+def prototypes(src, prefix, end):
+    """{name: (return type, [parameter types])} of the C functions named ``prefix*`` in ``src``: declarations
+    (end ";") or definitions (end "{").  Comments go first; types lose ``const`` and the parameter's name."""
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"//[^\n]*", "", src)
+
+    def ctype(text, named):
+        text = " ".join(text.replace("*", " * ").split())
+        if named and text != "void":
+            text = text.rsplit(" ", 1)[0]
+        return re.sub(r"\bconst ", "", text).replace(" *", "*")
+    out = {}
+    pattern = r"^\s*((?:const\s+)?\w+[\s*]+)(%s\w+)\s*\(([^()]*)\)\s*%s" % (prefix, re.escape(end))
+    for ret, name, params in re.findall(pattern, src, flags=re.M):
+        types = [ctype(p, True) for p in params.split(",") if p.strip()]
+        out[name] = (ctype(ret, False), [] if types == ["void"] else types)
+    return out
+
+
+def header_prototypes():
+    return prototypes(open(os.path.join(REPO, "include", "cdx.h")).read(), "cdx_", ";")
+
+
+def host_prototypes():
+    """The definitions inside host_ref.cpp's extern "C" block."""
+    src = open(os.path.join(REPO, "compliancedex_amd", "csrc", "host_ref.cpp")).read()
+    return prototypes(src.split('extern "C" {', 1)[1].rsplit('}  // extern "C"', 1)[0], "cdxh_", "{")
+
+
+def _binds(ctype, bound):
+    """A C type against the ctypes class bound to it (None: void)."""
+    if ctype == "void":
+        return bound is None
+    if bound is None:
+        return False
+    if ctype == "cdx_stream_t":
+        return bound is C.c_void_p
+    if ctype.endswith("*"):
+        if bound is C.c_void_p or (bound is C.c_char_p and ctype == "char*"):
+            return True
+        if not issubclass(bound, C._Pointer):
+            return False
+        to, base = bound._type_, ctype[:-1]
+        if issubclass(to, C.Structure):  # POINTER(CdxFooBar) ↔ cdx_foo_bar*
+            return re.sub(r"(?<!^)(?=[A-Z])", "_", to.__name__).lower() == base
+        return to in SCALARS.get(base, ())
+    return bound in SCALARS.get(ctype, ())
+
+
+def abi_mismatches(protos, sigs):
+    """[(function, where)] for every disagreement of a ctypes table {name: (restype, argtypes)} with parsed C
+    prototypes: "unbound" (declared, not in the table), "undeclared" (in the table, not in the C text), "arity",
+    "return" or "arg <index>"."""
+    bad = [(n, "unbound") for n in sorted(set(protos) - set(sigs))]
+    bad += [(n, "undeclared") for n in sorted(set(sigs) - set(protos))]
+    for name in sorted(set(protos) & set(sigs)):
+        (ret, params), (res, args) = protos[name], sigs[name]
+        if not _binds(ret, res):
+            bad.append((name, "return"))
+        if len(params) != len(args):
+            bad.append((name, "arity"))
+            continue
+        bad += [(name, f"arg {i}") for i, (c, a) in enumerate(zip(params, args)) if not _binds(c, a)]
+    return bad
+
 
 def declared_functions():
-    src = open(os.path.join(REPO, "include", "cdx.h")).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"^\s*(?:const\s+)?\w+\**\s+\**(cdx_\w+)\s*\(", src, flags=re.M)))
+    return sorted(header_prototypes())
 
 
 def test_header_declares_the_path():
@@ -17,6 +87,69 @@ def test_header_declares_the_path():
     for n in ("cdx_gpis_mean", "cdx_gpis_std", "cdx_fk_forward", "cdx_fk_backward", "cdx_closure",
               "cdx_sdf_forward", "cdx_sdf_backward"):
         assert n in names
+
+
+def test_native_table_matches_the_header():
+    from compliancedex_amd import _native
+    protos = header_prototypes()
+    assert len(protos) == len(_native._SIGS) >= 101
+    assert abi_mismatches(protos, _native._SIGS) == []
+
+
+def test_host_table_matches_host_ref():
+    """A cdxh_* function without its line in _host._SIGS, or whose line has another arity or argument class than its
+    definition, fails here."""
+    from compliancedex_amd import _host
+    protos = host_prototypes()
+    assert len(protos) == len(_host._SIGS) >= 38
+    assert abi_mismatches(protos, _host._SIGS) == []
+
+
+def test_abi_checker_can_fail():
+    """A dropped last argument, a c_int64 bound as c_int32 and a removed entry are reported, and nothing else."""
+    from compliancedex_amd import _host
+    sigs = {k: (r, list(a)) for k, (r, a) in _host._SIGS.items()}
+    sigs["cdxh_hand_cost"][1].pop()
+    at = sigs["cdxh_knn"][1].index(C.c_int64)
+    sigs["cdxh_knn"][1][at] = C.c_int32
+    del sigs["cdxh_svd3"]
+    assert abi_mismatches(host_prototypes(), sigs) == [("cdxh_svd3", "unbound"), ("cdxh_hand_cost", "arity"),
+                                                        ("cdxh_knn", f"arg {at}")]
+    # the parser on text of its own: a pointer bound as an integer, a wrong struct, a wrong return, an extra entry
+    protos = prototypes("int f_a(const cdx_chain* c, double* x);  /* int f_no(void); */\nvoid f_b(void);\n"
+                        "const char* f_c(cdx_stream_t s);  // int f_not(int)\nsize_t f_d(const cdx_hand *h, int n);",
+                        "f_", ";")
+    assert protos == {"f_a": ("int", ["cdx_chain*", "double*"]), "f_b": ("void", []),
+                      "f_c": ("char*", ["cdx_stream_t"]), "f_d": ("size_t", ["cdx_hand*", "int"])}
+    from compliancedex_amd._native import CdxChain
+    good = {"f_a": (C.c_int, [C.POINTER(CdxChain), C.c_void_p]), "f_b": (None, []),
+            "f_c": (C.c_char_p, [C.c_void_p]), "f_d": (C.c_size_t, [C.c_void_p, C.c_int32])}
+    assert abi_mismatches(protos, good) == []
+    bad = {"f_a": (C.c_int, [C.POINTER(CdxChain), C.c_int64]), "f_b": (C.c_int, []),
+           "f_c": (C.c_char_p, [C.c_void_p]), "f_d": (C.c_size_t, [C.POINTER(CdxChain), C.c_int32]),
+           "f_e": (None, [])}
+    assert abi_mismatches(protos, bad) == [("f_e", "undeclared"), ("f_a", "arg 1"), ("f_b", "return"),
+                                           ("f_d", "arg 0")]
+
+
+def test_bindings_live_in_their_two_modules():
+    """Outside _native.py, _host.py and tests/_sdf_oracle.py (another library) no Python file of tests/, tools/ or the
+    package opens a library itself or assigns a signature: a cdxh_* function is bound by its line in _host._SIGS.
+    (The cdx_diag_* symbols of the timing-only diagnostic builds are bound where their tool loads such a build.)"""
+    skip = {os.path.join("compliancedex_amd", "_native.py"), os.path.join("compliancedex_amd", "_host.py"),
+            os.path.join("tests", "_sdf_oracle.py")}
+    found = []
+    for top in ("tests", "tools", "compliancedex_amd"):
+        for root, _, files in os.walk(os.path.join(REPO, top)):
+            for name in files:
+                path = os.path.relpath(os.path.join(root, name), REPO)
+                if not name.endswith(".py") or path in skip:
+                    continue
+                for i, line in enumerate(open(os.path.join(REPO, path), encoding="utf-8"), 1):
+                    sig = re.search(r"(\w+)\.(argtypes|restype)\s*=[^=]", line)
+                    if re.search(r"CDLL\(", line) or (sig and not sig.group(1).startswith("cdx_diag_")):
+                        found.append(f"{path}:{i}: {line.strip()}")
+    assert found == []
 
 
 def test_library_exports_every_declared_symbol():

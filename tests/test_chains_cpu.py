@@ -96,7 +96,7 @@ def host_fk(desc, q, B, quat=True):
     T = desc.n_tips
     pos = np.full((B + GUARD, 3 * T), 7.0, np.float32)
     qt = np.full((B + GUARD, 4 * T), 7.0, np.float32)
-    rc = _host.host().cdxh_fk_forward(C.byref(desc), p(np.ascontiguousarray(q[:B])), C.c_int64(B), p(pos),
+    rc = _host.host().cdxh_fk_forward(C.byref(desc), p(np.ascontiguousarray(q[:B])), B, p(pos),
                                       p(qt) if quat else None)
     assert (pos[B:] == 7.0).all() and (qt[B:] == 7.0).all()
     return rc, pos[:B], qt[:B]
@@ -104,7 +104,7 @@ def host_fk(desc, q, B, quat=True):
 
 def host_bwd(desc, q, gpos, B):
     gq = np.full((B + GUARD, desc.n_dofs), 7.0, np.float32)
-    rc = _host.host().cdxh_fk_backward(C.byref(desc), p(np.ascontiguousarray(q[:B])), C.c_int64(B),
+    rc = _host.host().cdxh_fk_backward(C.byref(desc), p(np.ascontiguousarray(q[:B])), B,
                                        p(np.ascontiguousarray(gpos[:B])), p(gq))
     assert (gq[B:] == 7.0).all()
     return rc, gq[:B]
@@ -114,7 +114,7 @@ def host_jac(desc, q, B, ang=True):
     T, D = desc.n_tips, desc.n_dofs
     lin = np.full((B + GUARD, T, 3, D), 7.0, np.float32)
     a = np.full((B + GUARD, T, 3, D), 7.0, np.float32)
-    rc = _host.host().cdxh_fk_jacobian(C.byref(desc), p(np.ascontiguousarray(q[:B])), C.c_int64(B), p(lin),
+    rc = _host.host().cdxh_fk_jacobian(C.byref(desc), p(np.ascontiguousarray(q[:B])), B, p(lin),
                                        p(a) if ang else None)
     assert (lin[B:] == 7.0).all() and (a[B:] == 7.0).all()
     return rc, lin[:B], a[:B] if ang else None
@@ -195,8 +195,7 @@ def test_host_entries_refuse_an_over_deep_chain(depth):
     par = ik_params(lower, upper, [0.0] * depth, 0.0, 5, 1e-5)
     outs = [np.full((2, depth), 7.0), np.full((2, 1), 7.0), np.full(2, -7, np.int32), np.full(2, -7, np.int32)]
     q0, target = np.zeros((2, depth)), np.zeros((2, 1, 3))
-    h.cdxh_ik_solve.restype = C.c_int
-    rc = h.cdxh_ik_solve(C.byref(desc), C.byref(par), C.c_int64(2), p(q0), C.c_int32(1), p(target), None, None, None,
+    rc = h.cdxh_ik_solve(C.byref(desc), C.byref(par), 2, p(q0), 1, p(target), None, None, None,
                          *[p(a) for a in outs])
     assert rc == ECHAIN and all((a == (7.0 if a.dtype == np.float64 else -7)).all() for a in outs)
     # closure: queries and cost
@@ -204,18 +203,18 @@ def test_host_entries_refuse_an_over_deep_chain(depth):
     prob = build_problem(d4, None, ref_q=[0.0] * depth)
     X = np.full((400, 3), 7.0)
     z = lambda *s: np.zeros(s)  # noqa: E731
-    assert h.cdxh_closure_queries(C.byref(prob), C.c_int64(1), p(z(1, depth)), p(z(1, 4, 3)), p(z(1, 3)), p(z(1, 3)),
+    assert h.cdxh_closure_queries(C.byref(prob), 1, p(z(1, depth)), p(z(1, 4, 3)), p(z(1, 3)), p(z(1, 3)),
                                   p(X)) == ECHAIN and (X == 7.0).all()
     outs = [np.full(s, 7.0) for s in ((1,), (1, 4), (1, depth), (1, 4), (1, 4, 3), (1, 3), (1, 3))]
     flip = np.full(4, -7, np.int32)
     gp = [z(400), z(400, 3), z(400, 3), z(400), z(400, 3)]
-    assert h.cdxh_closure_cost(C.byref(prob), C.c_int64(1), p(z(1, depth)), p(z(1, 4) + 10), p(z(1, 4, 3)), p(z(1, 3)),
+    assert h.cdxh_closure_cost(C.byref(prob), 1, p(z(1, depth)), p(z(1, 4) + 10), p(z(1, 4, 3)), p(z(1, 3)),
                                p(z(1, 3)), p(z(3, 9)), *[p(a) for a in gp], *[p(a) for a in outs], p(flip)) == ECHAIN
     assert all((a == 7.0).all() for a in outs) and (flip == -7).all()
     # collision
     col = build_collision(d4, [[0, 1]])
     outs = [np.full(s, 7.0) for s in ((1,), (1, depth), (1, 3), (1, 3))]
-    assert h.cdxh_collision(C.byref(col), C.c_int64(1), p(z(1, depth)), p(z(1, 3)), p(z(1, 3)),
+    assert h.cdxh_collision(C.byref(col), 1, p(z(1, depth)), p(z(1, 3)), p(z(1, 3)),
                             *[p(a) for a in outs]) == ECHAIN and all((a == 7.0).all() for a in outs)
     # KinGPIS: the loop state of a valid chain, then the over-deep descriptor in its place
     from tests.test_gpis_mode_cpu import HostLoop, _inputs, _lib, _opt, _params
@@ -226,7 +225,7 @@ def test_host_entries_refuse_an_over_deep_chain(depth):
         loop.a[k][:] = 7.0
     prm, cfg = _params(1, hand), _opt((2e-3, 1e-3, 0.2))
     nz = np.ascontiguousarray(noise[0].reshape(2, 9))
-    assert _lib().cdxh_gpis_mode_cost(d4, prm, loop.b, 2, 4, nz.ctypes.data, 0, 0) == ECHAIN
+    assert _lib().cdxh_gpis_mode_cost(d4, prm, loop.b, 2, 4, p(nz), 0, 0) == ECHAIN
     assert _lib().cdxh_gpis_mode_step(d4, prm, cfg, loop.b, 2, 4, 0, 0) == ECHAIN
     for k in ("loss", "g_pose", "g_target", "g_comp", "pose", "v_pose"):
         assert (loop.a[k] == 7.0).all(), k

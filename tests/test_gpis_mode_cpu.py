@@ -24,17 +24,7 @@ BOX_LB = np.asarray(FINGERTIP_LB, np.float32).astype(np.float64)
 BOX_UB = np.asarray(FINGERTIP_UB, np.float32).astype(np.float64)
 
 
-def _lib():
-    h = _host.host()
-    P = C.c_void_p
-    h.cdxh_gpis_mode_cost.restype = C.c_int
-    h.cdxh_gpis_mode_cost.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxGpisModeParams),
-                                      C.POINTER(N.CdxGpisModeBuffers), C.c_int64, C.c_int32, P, C.c_uint64, C.c_int32]
-    h.cdxh_gpis_mode_step.restype = C.c_int
-    h.cdxh_gpis_mode_step.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxGpisModeParams),
-                                      C.POINTER(N.CdxGpisModeOpt), C.POINTER(N.CdxGpisModeBuffers), C.c_int64,
-                                      C.c_int32, C.c_int32, C.c_int32]
-    return h
+_lib = _host.host
 
 
 @pytest.fixture(scope="module")
@@ -142,7 +132,7 @@ class HostLoop:
 
     def cost(self, prm, noise, s, seed=0):
         nz = None if noise is None else np.ascontiguousarray(noise.reshape(self.n, 9))
-        rc = _lib().cdxh_gpis_mode_cost(self.chain, prm, self.b, self.n, T, None if nz is None else nz.ctypes.data,
+        rc = _lib().cdxh_gpis_mode_cost(self.chain, prm, self.b, self.n, T, _host.p(nz),
                                         seed, s)
         assert rc == 0
         return self.a["loss"].copy()

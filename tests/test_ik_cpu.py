@@ -123,7 +123,6 @@ def test_bad_rows_stay_in_their_row():
 def test_argument_errors():
     _, desc, *_ = _ik.hand()
     fn = _host.host().cdxh_ik_solve
-    fn.restype = C.c_int
     c = _ik.case_results()
     E = len(c["q0"])
     q, err = np.zeros((E, 16)), np.zeros((E, 4))
@@ -131,7 +130,7 @@ def test_argument_errors():
     p = _host.p
 
     def call(par, E=E, q0=p(c["q0"]), desc=desc):
-        return fn(C.byref(desc), C.byref(par), C.c_int64(E), q0, C.c_int32(_ik.F64), p(c["target"]), None, None, None,
+        return fn(C.byref(desc), C.byref(par), E, q0, _ik.F64, p(c["target"]), None, None, None,
                   p(q), p(err), p(it), p(st))
 
     assert call(_ik.params()) == 0

@@ -59,10 +59,9 @@ def test_grad_is_optional():
     tips, normals = W.family("A")
     out = W.outputs(len(tips), 4)
     fn = _host.host().cdxh_min_wrench
-    fn.restype = C.c_int
     par = W.params()
     args = [_host.p(out[k]) for k in W.FIELDS[:-1]]
-    assert fn(C.byref(par), C.c_int64(len(tips)), _host.p(tips), _host.p(normals), *args, None) == 0
+    assert fn(C.byref(par), len(tips), _host.p(tips), _host.p(normals), *args, None) == 0
     ref = solve(tips, normals)
     for k in W.FIELDS[:-1]:
         assert same_bits(out[k], ref[k]), k
@@ -85,13 +84,12 @@ def test_argument_errors():
     tips, normals = W.family("A")
     E = len(tips)
     fn = _host.host().cdxh_min_wrench
-    fn.restype = C.c_int
     out = W.outputs(E, 4)
     p = _host.p
 
     def call(par, E=E, tips_p=p(tips), drop=None):
         args = [None if k == drop else p(out[k]) for k in W.FIELDS]
-        return fn(C.byref(par) if par is not None else None, C.c_int64(E), tips_p, p(normals), *args)
+        return fn(C.byref(par) if par is not None else None, E, tips_p, p(normals), *args)
 
     assert call(None) == -1
     assert call(W.params(), E=-1) == -1

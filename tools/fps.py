@@ -21,7 +21,6 @@ fallback.
   python tools/fps.py [--reps 7] [--out PATH] [--shapes 2048:200,8192:2048,100000:2048,1000000:2048] [--no-host]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -75,18 +74,11 @@ def torch_loop(x, k, start=0):
 def host_fps(X, k):
     """(seconds on one core, sel) of cdxh_fps."""
     import numpy as np
-    from compliancedex_amd import _native as N
-    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
-    if not os.path.exists(path):
-        from compliancedex_amd.build import build_host
-        build_host()
-    lib = C.CDLL(path)
-    lib.cdxh_fps.restype = C.c_int
-    lib.cdxh_fps.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_int64, C.c_int64, C.c_int64, C.c_void_p, C.c_void_p,
-                             C.c_void_p]
+    from compliancedex_amd import _host, _native as N
+    lib = _host.load()
     sel = np.empty(k, np.int64)
     t = time.perf_counter()
-    rc = lib.cdxh_fps(X.ctypes.data, N.DTYPE_F64, len(X), 1, k, 0, sel.ctypes.data, None, None)
+    rc = lib.cdxh_fps(_host.ptr(X), N.DTYPE_F64, len(X), 1, k, 0, _host.ptr(sel), None, None)
     dt = time.perf_counter() - t
     assert rc == 0
     return dt, sel

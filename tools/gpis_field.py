@@ -79,27 +79,19 @@ def step_visualization(g, state, steps, reps):
 
 def step_surface(g, state, steps, reps):
     """(c), (d), (e) on one field."""
-    import ctypes as C
-
     import numpy as np
     import torch
-    from compliancedex_amd import _native as N
+    from compliancedex_amd import _host, _native as N
     lb, ub = BOXES[state]
     mean, _, normal, _, _ = g.get_visualization_data(lb, ub, steps=steps, fused=True)
-    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
-    if not os.path.exists(path):
-        from compliancedex_amd.build import build_host
-        build_host()
-    host = C.CDLL(path)
-    host.cdxh_surface_extract.restype = C.c_int64
+    host, p = _host.load(), _host.ptr
     axes = [np.linspace(lb[d], ub[d], steps) for d in range(3)]
     cap = (steps - 2) ** 3
     hp, hn = np.zeros((cap, 3)), np.zeros((cap, 3), np.float32)
 
     def host_extract():
-        p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
-        return host.cdxh_surface_extract(p(mean), p(normal), C.c_int32(N.DTYPE_F32), C.c_int32(steps), C.c_int32(0),
-                                         p(axes[0]), p(axes[1]), p(axes[2]), C.c_int64(cap), None, p(hp), p(hn))
+        return host.cdxh_surface_extract(p(mean), p(normal), N.DTYPE_F32, steps, 0, p(axes[0]), p(axes[1]), p(axes[2]),
+                                         cap, None, p(hp), p(hn))
 
     paths = {"c_topcd_device": lambda: g.topcd(mean, normal, lb, ub, steps=steps), "d_extract_host": host_extract,
              "e_surface": lambda: g.surface(lb, ub, steps=steps)}

@@ -124,23 +124,11 @@ def torch_mesh(mean, axes):
     return vertices, keys, torch.searchsorted(keys, rows).to(torch.int32)
 
 
-def host_lib():
-    import ctypes as C
-    from compliancedex_amd import _native as N
-    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
-    if not os.path.exists(path):
-        from compliancedex_amd.build import build_host
-        build_host()
-    return C.CDLL(path)
-
-
 def step_tomesh(g, state, steps, reps):
     """(a) – (d) on one lattice: the state's mean on the float64 point axes."""
-    import ctypes as C
-
     import numpy as np
     import torch
-    from compliancedex_amd import _native as N
+    from compliancedex_amd import _host, _native as N
     lb, ub = BOXES[state]
     dev = g.X1.device
     pax = g._point_axes(lb, ub, steps)
@@ -148,16 +136,15 @@ def step_tomesh(g, state, steps, reps):
     mean_d = g.pred_mean(grid).contiguous()
     mean = mean_d.cpu().numpy()
     axes = [np.ascontiguousarray(a) for a in pax.cpu().numpy()]
-    host = host_lib()
-    p = lambda a: a.ctypes.data_as(C.c_void_p)  # noqa: E731
+    host, p = _host.load(), _host.ptr
     counts = np.zeros(2, np.int64)
-    args = [p(mean), C.c_int32(N.DTYPE_F64), C.c_int32(steps), p(axes[0]), p(axes[1]), p(axes[2])]
-    assert host.cdxh_mesh_extract(*args, C.c_int64(0), C.c_int64(0), None, None, None, p(counts)) == 0
+    args = [p(mean), N.DTYPE_F64, steps, p(axes[0]), p(axes[1]), p(axes[2])]
+    assert host.cdxh_mesh_extract(*args, 0, 0, None, None, None, p(counts)) == 0
     V, F = int(counts[0]), int(counts[1])
     hv, hk, hf = np.zeros((V, 3)), np.zeros(V, np.int64), np.zeros((F, 3), np.int32)
 
     def host_extract():
-        return host.cdxh_mesh_extract(*args, C.c_int64(V), C.c_int64(F), p(hv), p(hk), p(hf), p(counts))
+        return host.cdxh_mesh_extract(*args, V, F, p(hv), p(hk), p(hf), p(counts))
 
     paths = {"a_tomesh_device": lambda: g.tomesh(mean, lb, ub, steps=steps), "c_extract_host": host_extract,
              "d_torch_statement": lambda: torch_mesh(mean_d, pax)}

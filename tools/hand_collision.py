@@ -19,7 +19,6 @@ appended to the record (default profiles/hand_collision.jsonl).  Needs a GPU: th
   python tools/hand_collision.py [--reps 7] [--rows 4096,16384,65536] [--kinds gpis,mesh] [--urdf PATH] [--out PATH]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import subprocess
@@ -114,24 +113,13 @@ def torch_cost(tables, centers, dist, gdist, floor_z):
 def host_seconds(hs, q, palm, dist, gdist, floor_z):
     """Seconds of the host build's spheres + cost + pull-back on one core."""
     import numpy as np
-    from compliancedex_amd import _native as N
-    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
-    if not os.path.exists(path):
-        from compliancedex_amd.build import build_host
-        build_host()
-    lib = C.CDLL(path)
-    P, I64 = C.c_void_p, C.c_int64
-    lib.cdxh_hand_bytes.restype = C.c_size_t
-    lib.cdxh_hand_bytes.argtypes = [C.c_int32, C.c_int32]
-    lib.cdxh_hand_prepare.argtypes = [C.c_int32, C.c_int32, P, P, P, C.c_int32, P, P, C.POINTER(N.CdxHand)]
-    lib.cdxh_hand_spheres.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxHand), I64, P, P, P, P, P]
-    lib.cdxh_hand_cost.argtypes = [C.POINTER(N.CdxHand), C.POINTER(N.CdxHandParams), I64] + [P] * 7
-    lib.cdxh_hand_pullback.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxHand), I64] + [P] * 6
+    from compliancedex_amd import _host, _native as N
+    lib, p = _host.load(), _host.ptr
     S, Pn, E = hs.n_spheres, len(hs.pairs), q.shape[0]
     buf = np.zeros(lib.cdxh_hand_bytes(S, Pn), np.uint8)
     h = N.CdxHand()
-    assert lib.cdxh_hand_prepare(hs.desc.n_bodies, S, hs.local.ctypes.data, hs.radius.ctypes.data, hs.body.ctypes.data,
-                                 Pn, hs.pairs.ctypes.data, buf.ctypes.data, C.byref(h)) == 0
+    assert lib.cdxh_hand_prepare(hs.desc.n_bodies, S, p(hs.local), p(hs.radius), p(hs.body), Pn, p(hs.pairs), p(buf),
+                                 h) == 0
     par = N.CdxHandParams()
     for k, v in KW.items():
         setattr(par, k, v)
@@ -141,12 +129,9 @@ def host_seconds(hs, q, palm, dist, gdist, floor_z):
     cost, depth, worst, g = np.empty(E), np.empty((E, 3)), np.empty((E, 3), np.int32), np.empty((E, S, 3))
     g_q, g_pp, g_po = np.empty((E, hs.desc.n_dofs)), np.empty((E, 3)), np.empty((E, 3))
     t = time.perf_counter()
-    rc = lib.cdxh_hand_spheres(C.byref(hs.desc), C.byref(h), E, q.ctypes.data, pp.ctypes.data, po.ctypes.data,
-                               poses.ctypes.data, cen.ctypes.data)
-    rc |= lib.cdxh_hand_cost(C.byref(h), C.byref(par), E, cen.ctypes.data, dist.ctypes.data, gdist.ctypes.data,
-                             cost.ctypes.data, depth.ctypes.data, worst.ctypes.data, g.ctypes.data)
-    rc |= lib.cdxh_hand_pullback(C.byref(hs.desc), C.byref(h), E, poses.ctypes.data, g.ctypes.data, po.ctypes.data,
-                                 g_q.ctypes.data, g_pp.ctypes.data, g_po.ctypes.data)
+    rc = lib.cdxh_hand_spheres(hs.desc, h, E, p(q), p(pp), p(po), p(poses), p(cen))
+    rc |= lib.cdxh_hand_cost(h, par, E, p(cen), p(dist), p(gdist), p(cost), p(depth), p(worst), p(g))
+    rc |= lib.cdxh_hand_pullback(hs.desc, h, E, p(poses), p(g), p(po), p(g_q), p(g_pp), p(g_po))
     dt = time.perf_counter() - t
     assert rc == 0
     return dt

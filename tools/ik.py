@@ -19,7 +19,6 @@ appended to the record (default profiles/ik.jsonl).  Needs a GPU: there is no fa
   python tools/ik.py [--reps 7] [--rows 4096,16384,65536] [--robots allegro,iiwa7_allegro] [--out PATH]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import subprocess
@@ -97,16 +96,9 @@ def torch_ik(rm, links, offsets, q0, target, lo, hi, max_iters=50, tol=1e-5, mu0
 def host_seconds(rm, links, offsets, q0, target):
     """Seconds of cdxh_ik_solve on one core, and its status / iteration arrays."""
     import numpy as np
-    from compliancedex_amd import _native as N
+    from compliancedex_amd import _host, _native as N
     from compliancedex_amd.ik import ik_params, joint_box
-    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
-    if not os.path.exists(path):
-        from compliancedex_amd.build import build_host
-        build_host()
-    lib = C.CDLL(path)
-    lib.cdxh_ik_solve.restype = C.c_int
-    lib.cdxh_ik_solve.argtypes = [C.POINTER(N.CdxChain), C.POINTER(N.CdxIkParams), C.c_int64, C.c_void_p, C.c_int32] + \
-        [C.c_void_p] * 8
+    lib, p = _host.load(), _host.ptr
     params = ik_params(*joint_box(rm.get_joint_limits()))
     desc = rm._descriptor(links, offsets)
     q0, target = np.ascontiguousarray(q0.cpu().numpy()), np.ascontiguousarray(target.cpu().numpy())
@@ -114,8 +106,8 @@ def host_seconds(rm, links, offsets, q0, target):
     q, err = np.empty_like(q0), np.empty((E, T))
     iters, status = np.empty(E, np.int32), np.empty(E, np.int32)
     t = time.perf_counter()
-    rc = lib.cdxh_ik_solve(desc, C.byref(params), E, q0.ctypes.data, N.DTYPE_F64, target.ctypes.data, None, None, None,
-                           q.ctypes.data, err.ctypes.data, iters.ctypes.data, status.ctypes.data)
+    rc = lib.cdxh_ik_solve(desc, params, E, p(q0), N.DTYPE_F64, p(target), None, None, None, p(q), p(err), p(iters),
+                           p(status))
     dt = time.perf_counter() - t
     assert rc == 0
     return dt, status, iters

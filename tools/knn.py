@@ -21,7 +21,6 @@ fallback.
   python tools/knn.py [--reps 7] [--big-reps 3] [--sizes 256,…,1000000] [--ks 1,20,30,64] [--out PATH]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -36,18 +35,11 @@ from tools.fps import cloud, event_ms, stats  # noqa: E402
 def host_knn_seconds(X, k):
     """Seconds of cdxh_knn (brute force) on one core."""
     import numpy as np
-    from compliancedex_amd import _native as N
-    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
-    if not os.path.exists(path):
-        from compliancedex_amd.build import build_host
-        build_host()
-    lib = C.CDLL(path)
-    lib.cdxh_knn.restype = C.c_int
-    lib.cdxh_knn.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_int64, C.c_int64, C.c_double, C.c_int32,
-                             C.c_void_p, C.c_void_p, C.c_void_p]
+    from compliancedex_amd import _host, _native as N
+    lib = _host.load()
     idx = np.empty((len(X), k), np.int64)
     t = time.perf_counter()
-    rc = lib.cdxh_knn(X.ctypes.data, N.DTYPE_F64, len(X), None, len(X), k, float("inf"), 1, idx.ctypes.data, None, None)
+    rc = lib.cdxh_knn(_host.ptr(X), N.DTYPE_F64, len(X), None, len(X), k, float("inf"), 1, _host.ptr(idx), None, None)
     dt = time.perf_counter() - t
     assert rc == 0
     return dt, idx

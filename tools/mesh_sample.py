@@ -22,7 +22,6 @@ GPU: there is no fallback.
   python tools/mesh_sample.py [--reps 7] [--out PATH] [--samples 10000,1000000,10000000] [--no-host] [--no-torch]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -94,33 +93,18 @@ def torch_draw(faces64, cdf, total, seed, first, K):
     return (f[:, 0] + u[:, None] * (f[:, 1] - f[:, 0])) + v[:, None] * (f[:, 2] - f[:, 0]), face
 
 
-def host_lib():
-    from compliancedex_amd import _native as N
-    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
-    if not os.path.exists(path):
-        from compliancedex_amd.build import build_host
-        build_host()
-    lib = C.CDLL(path)
-    lib.cdxh_sample_prepare.restype = C.c_int
-    lib.cdxh_sample_prepare.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_void_p]
-    lib.cdxh_sample_draw.restype = C.c_int
-    lib.cdxh_sample_draw.argtypes = [C.c_void_p, C.c_int32, C.c_int64, C.c_void_p, C.c_uint64, C.c_uint64, C.c_int64,
-                                     C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]
-    return lib
-
-
 def host_run(faces, K, seed):
     """(prepare seconds, draw seconds, points, face) of the host build on one core."""
     import numpy as np
-    from compliancedex_amd import _native as N
-    lib = host_lib()
+    from compliancedex_amd import _host, _native as N
+    lib, p = _host.load(), _host.ptr
     cdf, info = np.zeros(len(faces), np.uint64), np.zeros(1, np.int32)
     t0 = time.perf_counter()
-    assert lib.cdxh_sample_prepare(faces.ctypes.data, N.DTYPE_F32, len(faces), cdf.ctypes.data, info.ctypes.data) == 0
+    assert lib.cdxh_sample_prepare(p(faces), N.DTYPE_F32, len(faces), p(cdf), p(info)) == 0
     t1 = time.perf_counter()
     points, face = np.empty((K, 3)), np.empty(K, np.int64)
-    assert lib.cdxh_sample_draw(faces.ctypes.data, N.DTYPE_F32, len(faces), cdf.ctypes.data, seed, 0, K,
-                                points.ctypes.data, face.ctypes.data, None, None) == 0
+    assert lib.cdxh_sample_draw(p(faces), N.DTYPE_F32, len(faces), p(cdf), seed, 0, K, p(points), p(face), None,
+                                None) == 0
     return t1 - t0, time.perf_counter() - t1, points, face
 
 

@@ -106,20 +106,12 @@ def torch_cast(faces, o, d, tmin=0.0, tmax=float("inf"), block=2048):
 def host_cast(faces, o, d):
     """(seconds on one core, t, face) of cdxh_ray_cast."""
     import numpy as np
-    from compliancedex_amd import _native as N
-    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
-    if not os.path.exists(path):
-        from compliancedex_amd.build import build_host
-        build_host()
-    lib = C.CDLL(path)
-    lib.cdxh_ray_cast.restype = C.c_int
-    lib.cdxh_ray_cast.argtypes = [C.c_void_p, C.c_int64, C.c_void_p, C.c_void_p, C.c_int64, C.c_double, C.c_double,
-                                  C.c_void_p, C.c_void_p, C.c_void_p]
+    from compliancedex_amd import _host
+    lib, p = _host.load(), _host.ptr
     R = len(o)
     t, face = np.empty(R), np.empty(R, np.int32)
     t0 = time.perf_counter()
-    rc = lib.cdxh_ray_cast(faces.ctypes.data, len(faces), o.ctypes.data, d.ctypes.data, R, 0.0, float("inf"),
-                           t.ctypes.data, face.ctypes.data, None)
+    rc = lib.cdxh_ray_cast(p(faces), len(faces), p(o), p(d), R, 0.0, float("inf"), p(t), p(face), None)
     dt = time.perf_counter() - t0
     assert rc == 0
     return dt, t, face

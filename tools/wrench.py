@@ -19,7 +19,6 @@ appended to the record (default profiles/wrench.jsonl).  Needs a GPU: there is n
   python tools/wrench.py [--reps 7] [--rows 4096,16384,65536] [--families A,D] [--out PATH]
 """
 import argparse
-import ctypes as C
 import json
 import os
 import subprocess
@@ -145,21 +144,15 @@ def torch_min_wrench(tips, normals, mu=MU, fmin=FMIN, reg=REG, rho=RHO, tol=TOL,
 def host_seconds(tips, normals):
     """Seconds of cdxh_min_wrench on one core, and its status / iteration arrays."""
     import numpy as np
-    from compliancedex_amd import _native as N
+    from compliancedex_amd import _host
     from compliancedex_amd.wrench import wrench_params
-    path = os.path.join(N.LIB_DIR, "libcdx_host.so")
-    if not os.path.exists(path):
-        from compliancedex_amd.build import build_host
-        build_host()
-    lib = C.CDLL(path)
-    lib.cdxh_min_wrench.restype = C.c_int
-    lib.cdxh_min_wrench.argtypes = [C.POINTER(N.CdxWrenchParams), C.c_int64] + [C.c_void_p] * 10
+    lib, p = _host.load(), _host.ptr
     E, T = tips.shape[:2]
     par = wrench_params(T, MU, FMIN, REG, MAX_ITERS, TOL, RHO, CHECK_EVERY)
     out = [np.empty((E, T, 3)), np.empty(E), np.empty((E, T)), np.empty((E, 6)), np.empty(E), np.empty(E, np.int32),
            np.empty(E, np.int32), np.empty((E, T, 3))]
     t = time.perf_counter()
-    rc = lib.cdxh_min_wrench(C.byref(par), E, tips.ctypes.data, normals.ctypes.data, *[a.ctypes.data for a in out])
+    rc = lib.cdxh_min_wrench(par, E, p(tips), p(normals), *[p(a) for a in out])
     dt = time.perf_counter() - t
     assert rc == 0
     return dt, out[6], out[5]
