@@ -6,6 +6,9 @@ Drop-in operators (same names / arguments as the reference):
   solve_ik / IKResult / DifferentiableRobotModel.inverse_kinematics / results.joint_angles_from_contacts
                                PyBullet's calculateInverseKinematics (verify_pregrasp.py:50-53): fingertips → joint
                                angles for E candidates in one launch, parity with PyBullet's solver unpinned
+  solve_ik_pose / IKPoseResult / inverse_kinematics(solve_palm=True) / results.hand_pose_from_contacts
+                               the same with the wrist an unknown: fingertips → joint angles and palm pose, for the
+                               fingertip-space optimisers' results (the reference's writer cannot finish those)
   compute_sdf                  torchsdf/sdf.py
   ProbabilisticGraspOptimizer  optimize_pregrasp.py:614-839
   KinGraspOptimizer / SDFGraspOptimizer / GPISGraspOptimizer / KinGPISGraspOptimizer / WCKinGPISGraspOptimizer
@@ -53,7 +56,7 @@ from .raycast import (Camera, cast_rays, depth_to_pointcloud, observable_pointcl
 from .sampling import (SurfaceSampler, sample_points_poisson_disk, sample_points_uniformly,  # noqa: F401
                        surface_sampler)
 from .robot_model import DifferentiableRobotModel  # noqa: F401
-from .ik import IKResult, solve_ik  # noqa: F401
+from .ik import IKPoseResult, IKResult, solve_ik, solve_ik_pose  # noqa: F401
 from .wrench import (MinWrenchResult, compute_margin, min_wrench, minimum_wrench_reward,  # noqa: F401
                      solve_minimum_wrench)
 from .hand import HandSpheres, HandTerm, hand_collision, penetration_report, spheres_from_urdf  # noqa: F401

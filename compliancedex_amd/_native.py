@@ -229,6 +229,9 @@ _SIGS = {
     "cdx_ik_abi_size": (C.c_size_t, []),
     "cdx_ik_solve": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxIkParams), _I64, _P, C.c_int32, _P, _P,
                                C.POINTER(C.c_double), _P, _P, _P, _P, _P, _P, _P]),
+    "cdx_ik_solve_pose": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxIkParams), _I64, _P, C.c_int32, _P, _P, _P,
+                                    C.POINTER(C.c_double)] + [_P] * 9),
+    "cdx_ik_pose_rows_per_block": (C.c_int32, [C.c_int32, C.c_int32]),
     "cdx_min_wrench": (C.c_int, [C.POINTER(CdxWrenchParams), _I64] + [_P] * 11),
     "cdx_wrench_rows_per_block": (C.c_int32, [C.c_int32]),
     "cdx_wrench_abi_size": (C.c_size_t, []),

@@ -1,7 +1,8 @@
 // Fingertip Jacobians and batched inverse kinematics: the rule shared by the kernels (cdx_ik.hip) and the host build
-// (host_ref.cpp: cdxh_fk_jacobian, cdxh_ik_solve, the CPU yardsticks of those kernels).  The reference turns fingertips
-// back into a hand pose with PyBullet's calculateInverseKinematics (verify_pregrasp.py:50-53, bullet_robot.py:262-280)
-// and has compute_endeffector_jacobian (robot_model.py:643-683); parity with PyBullet's solver is unpinned.
+// (host_ref.cpp: cdxh_fk_jacobian, cdxh_ik_solve, cdxh_ik_solve_pose, the CPU yardsticks of those kernels).  The
+// reference turns fingertips back into a hand pose with PyBullet's calculateInverseKinematics (verify_pregrasp.py:50-53,
+// bullet_robot.py:262-280) and has compute_endeffector_jacobian (robot_model.py:643-683); parity with PyBullet's solver
+// is unpinned.
 //
 // Jacobian.  For tip k of the chain at joint row q (float32), with p the tip position of cdx_fk_forward (offset
 //   included), and for every moving joint j on the tip's path its world axis ω_j = R_parent·F_j·e_axis and world
@@ -38,6 +39,38 @@
 //     Accepted if every pivot was > 0 and cost(q′) < cost(q): q ← q′, μ ← max(μ/ν, μ_min).  Else μ ← min(μ·ν, μ_max).
 //     The accepted cost never rises.
 //   Outputs: q (float32 values), err_k = e_k at the returned q (unweighted), iters, status.
+//
+// Free-wrist inverse kinematics (ik_pose_row).  The same solve with the palm's rigid pose an unknown next to the joints:
+//   per row, independent of every other row.  State: q float32 [D] clamped as above, pp double [3], Rp double [9]
+//   (row-major).  Inputs as above without `palm`, plus palm0_pos [3] / palm0_rot [9] (both or neither).  A row with a
+//   non-finite q0, target, w, palm0_pos or palm0_rot has status 2: q = q0, NaN in palm_pos / palm_rot / err, iters 0.
+//   Fingertips, residuals, cost, emax: exactly ik_eval's with the current (Rp, pp):
+//     tip_k = (Rp·double(FK_f32(q)_k) + pp) + palm_offset.  The pose carries no cost term of its own.
+//   Start.  With palm0_pos / palm0_rot: (pp, Rp) are those values as they are — an orthogonal palm0_rot is the caller's
+//     contract, nothing re-orthonormalises it.  Without: the weighted Kabsch fit of the start's own fingertips onto the
+//     targets.  v_k = double(FK_f32(q)_k) at the clamped q0, t_k = target_k − palm_offset, W = Σ_k w_k (k ascending),
+//     c_v = (Σ w_k·v_k)/W, c_t = (Σ w_k·t_k)/W, H = Σ_k (w_k·(v_k − c_v))·(t_k − c_t)ᵀ,
+//     Rp = kabsch_rotation<double>(H, zero noise) = V·diag(1, 1, d)·Uᵀ of H = U·S·Vᵀ (cdx_cost.h), which takes v onto t,
+//     pp = c_t − Rp·c_v.  Fallback — fewer than three tips with w_k > 0, W not > 0, or a non-finite entry in Rp —:
+//     Rp = I, pp = c_t − c_v, and pp = 0 where W is not > 0.
+//   No trigonometric function is called anywhere in the row: the pose is a matrix from start to end.
+//   Loop: the fixed-palm loop with D′ = D + 6 columns.  The step's unknowns are (δq [D], t_b [3], ω_b [3]), the pose
+//     increment written in the PALM frame, so the step stays the palm-frame step above: rows 3k..3k+2 of Jl gain six
+//     float32 columns after the joint columns, t_b: I₃, ω_b: −[v_k]× = [[0, vz, −vy], [−vz, 0, vx], [vy, −vx, 0]] with v_k
+//     the float32 FK tip — exact entries.  u as above.
+//     g_d for d < D as above (ρ term, bounds);  g_d = Σ_rows Jl[row][d]·u[row] for the six pose columns: no ρ term, and
+//       a pose column is never fixed on a bound.
+//     κ = μ + ρ damps all D′ columns.  On the pose columns ρ is a step damping only (it shortens the step as it does the
+//       joints'), never a pull towards a rest pose.  A, b, the Cholesky, the substitutions and δ [D′] as above.
+//     Trial point: q′ as above;  pp′ = pp + Rp·t_b;  with a = ½·ω_b, s = (ax² + ay²) + az², the Cayley rotation
+//       C = ((1 − s)·I + 2·a·aᵀ + 2·[a]×)/(1 + s), entry by entry C_ii = ((1 − s) + 2·a_i²)/(1 + s),
+//       C_ij = (2·a_i·a_j ∓ 2·a_k)/(1 + s) (− for ij = 01, 12, 20) — plain arithmetic, orthogonal before rounding;
+//       Rp′ = Rp·C (mat3_mul).  No re-orthonormalisation: the drift is a few roundings per ACCEPTED step.
+//     Accepted as above (every pivot > 0 and cost(q′, Rp′, pp′) < cost): (q, Rp, pp) ← (q′, Rp′, pp′).  The μ schedule,
+//       the stop tests and the statuses are the fixed-palm ones.
+//   Outputs: q, palm_pos = pp, palm_rot = Rp, err (unweighted, at the returned q and pose), iters, status.
+//   Storage: IkMem of (T, D + 6): J has row stride D + 6, g has D + 6 entries (q / qn use their first D).  The pose and
+//   its trial copy (2 × 12 doubles) are indexed by constants only and live in registers.
 //
 // Storage.  Every per-row array (IkMem) is addressed as base[i·s]: s = 1 on the host, and on the device the arrays of
 // the lanes of a workgroup are interleaved in LDS (s = lanes, base shifted by the lane), so no array indexed at run time
@@ -202,6 +235,58 @@ CDX_HD double ik_eval(const cdx_chain& c, const cdx_ik_params& p, const Q& q, co
   return 0.5 * ss + (0.5 * p.rho) * sq;
 }
 
+// The damped system of one step over the first D columns of every row of m.J (row stride D): A = W·J·Jᵀ·W + κI and
+// b = W·J·g, A = L·Lᵀ in place, y = A⁻¹·b by two substitutions, then y ← w·y in m.y (the header's order of operations).
+// False if a pivot was not > 0.
+CDX_HD bool ik_gram_solve(const IkMem& m, const double* w, int n, int D, double kappa) {
+  const int s = m.s;
+  // A and b
+  for (int a = 0; a < n; ++a) {
+    const double wa = w ? w[a / 3] : 1.0;
+    for (int b = 0; b <= a; ++b) {
+      const double wb = w ? w[b / 3] : 1.0;
+      double acc = 0.0;
+      CDX_IK_UNROLL
+      for (int d = 0; d < D; ++d) acc += (double)m.J[(size_t)(a * D + d) * s] * (double)m.J[(size_t)(b * D + d) * s];
+      acc = (wa * wb) * acc;
+      if (a == b) acc += kappa;
+      m.A[(size_t)(a * (a + 1) / 2 + b) * s] = acc;
+    }
+    double acc = 0.0;
+    CDX_IK_UNROLL
+    for (int d = 0; d < D; ++d) acc += (double)m.J[(size_t)(a * D + d) * s] * m.g[(size_t)d * s];
+    m.y[(size_t)a * s] = wa * acc;
+  }
+  // A = L·Lᵀ in place
+  bool pd = true;
+  for (int i = 0; i < n; ++i)
+    for (int j = 0; j <= i; ++j) {
+      double sum = m.A[(size_t)(i * (i + 1) / 2 + j) * s];
+      CDX_IK_UNROLL
+      for (int k = 0; k < j; ++k) sum -= m.A[(size_t)(i * (i + 1) / 2 + k) * s] * m.A[(size_t)(j * (j + 1) / 2 + k) * s];
+      if (i == j) {
+        pd = pd && sum > 0.0;
+        m.A[(size_t)(i * (i + 1) / 2 + j) * s] = sqrt(sum);
+      } else {
+        m.A[(size_t)(i * (i + 1) / 2 + j) * s] = sum / m.A[(size_t)(j * (j + 1) / 2 + j) * s];
+      }
+    }
+  for (int i = 0; i < n; ++i) {
+    double sum = m.y[(size_t)i * s];
+    CDX_IK_UNROLL
+    for (int k = 0; k < i; ++k) sum -= m.A[(size_t)(i * (i + 1) / 2 + k) * s] * m.y[(size_t)k * s];
+    m.y[(size_t)i * s] = sum / m.A[(size_t)(i * (i + 1) / 2 + i) * s];
+  }
+  for (int i = n - 1; i >= 0; --i) {
+    double sum = m.y[(size_t)i * s];
+    CDX_IK_UNROLL
+    for (int k = i + 1; k < n; ++k) sum -= m.A[(size_t)(k * (k + 1) / 2 + i) * s] * m.y[(size_t)k * s];
+    m.y[(size_t)i * s] = sum / m.A[(size_t)(i * (i + 1) / 2 + i) * s];
+  }
+  for (int a = 0; a < n; ++a) m.y[(size_t)a * s] = (w ? w[a / 3] : 1.0) * m.y[(size_t)a * s];
+  return pd;
+}
+
 // One row of the solve (p: after ik_prepare; po: 3 doubles).  Leaves the result in m.q, writes err [T] and *iters,
 // returns the status.  Status 2 leaves m untouched.
 CDX_HD int ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0, const double* target,
@@ -274,50 +359,7 @@ CDX_HD int ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, 
       m.g[(size_t)d * s] = g;
     }
     const double kappa = mu + p.rho;
-    // A and b
-    for (int a = 0; a < n; ++a) {
-      const double wa = w ? w[a / 3] : 1.0;
-      for (int b = 0; b <= a; ++b) {
-        const double wb = w ? w[b / 3] : 1.0;
-        double acc = 0.0;
-        CDX_IK_UNROLL
-        for (int d = 0; d < D; ++d) acc += (double)m.J[(size_t)(a * D + d) * s] * (double)m.J[(size_t)(b * D + d) * s];
-        acc = (wa * wb) * acc;
-        if (a == b) acc += kappa;
-        m.A[(size_t)(a * (a + 1) / 2 + b) * s] = acc;
-      }
-      double acc = 0.0;
-      CDX_IK_UNROLL
-      for (int d = 0; d < D; ++d) acc += (double)m.J[(size_t)(a * D + d) * s] * m.g[(size_t)d * s];
-      m.y[(size_t)a * s] = wa * acc;
-    }
-    // A = L·Lᵀ in place
-    bool pd = true;
-    for (int i = 0; i < n; ++i)
-      for (int j = 0; j <= i; ++j) {
-        double sum = m.A[(size_t)(i * (i + 1) / 2 + j) * s];
-        CDX_IK_UNROLL
-        for (int k = 0; k < j; ++k) sum -= m.A[(size_t)(i * (i + 1) / 2 + k) * s] * m.A[(size_t)(j * (j + 1) / 2 + k) * s];
-        if (i == j) {
-          pd = pd && sum > 0.0;
-          m.A[(size_t)(i * (i + 1) / 2 + j) * s] = sqrt(sum);
-        } else {
-          m.A[(size_t)(i * (i + 1) / 2 + j) * s] = sum / m.A[(size_t)(j * (j + 1) / 2 + j) * s];
-        }
-      }
-    for (int i = 0; i < n; ++i) {
-      double sum = m.y[(size_t)i * s];
-      CDX_IK_UNROLL
-      for (int k = 0; k < i; ++k) sum -= m.A[(size_t)(i * (i + 1) / 2 + k) * s] * m.y[(size_t)k * s];
-      m.y[(size_t)i * s] = sum / m.A[(size_t)(i * (i + 1) / 2 + i) * s];
-    }
-    for (int i = n - 1; i >= 0; --i) {
-      double sum = m.y[(size_t)i * s];
-      CDX_IK_UNROLL
-      for (int k = i + 1; k < n; ++k) sum -= m.A[(size_t)(k * (k + 1) / 2 + i) * s] * m.y[(size_t)k * s];
-      m.y[(size_t)i * s] = sum / m.A[(size_t)(i * (i + 1) / 2 + i) * s];
-    }
-    for (int a = 0; a < n; ++a) m.y[(size_t)a * s] = (w ? w[a / 3] : 1.0) * m.y[(size_t)a * s];
+    const bool pd = ik_gram_solve(m, w, n, D, kappa);
     // the trial point
     for (int d = 0; d < D; ++d) {
       double acc = 0.0;
@@ -345,6 +387,206 @@ CDX_HD int ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, 
     const double d[3] = {dc[(size_t)(3 * k) * s], dc[(size_t)(3 * k + 1) * s], dc[(size_t)(3 * k + 2) * s]};
     err[k] = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
   }
+  *iters = it;
+  return status;
+}
+
+// The Kabsch start of ik_pose_row (see above): v [3T] (stride s) holds double(FK_f32(q)_k).
+CDX_HD void ik_pose_start(int T, const double* v, int s, const double* target, const double* po, const double* w,
+                          double* Rp, double* pp) {
+  double cv[3] = {0.0, 0.0, 0.0}, ct[3] = {0.0, 0.0, 0.0}, W = 0.0;
+  int npos = 0;
+  for (int k = 0; k < T; ++k) {
+    const double wk = w ? w[k] : 1.0;
+    W += wk;
+    npos += wk > 0.0 ? 1 : 0;
+    for (int i = 0; i < 3; ++i) {
+      cv[i] += wk * v[(size_t)(3 * k + i) * s];
+      ct[i] += wk * (target[3 * k + i] - po[i]);
+    }
+  }
+  for (int i = 0; i < 9; ++i) Rp[i] = (i % 4 == 0) ? 1.0 : 0.0;
+  if (!(W > 0.0)) {
+    for (int i = 0; i < 3; ++i) pp[i] = 0.0;
+    return;
+  }
+  for (int i = 0; i < 3; ++i) {
+    cv[i] /= W;
+    ct[i] /= W;
+  }
+  if (npos >= 3) {
+    double H[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    for (int k = 0; k < T; ++k) {
+      const double wk = w ? w[k] : 1.0;
+      for (int r = 0; r < 3; ++r) {
+        const double a = wk * (v[(size_t)(3 * k + r) * s] - cv[r]);
+        for (int i = 0; i < 3; ++i) H[3 * r + i] += a * ((target[3 * k + i] - po[i]) - ct[i]);
+      }
+    }
+    const double noise[9] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0};
+    KabschTape tp;
+    double R[9];
+    kabsch_rotation<double>(H, noise, tp, R);
+    bool fin = true;
+    for (int i = 0; i < 9; ++i) fin = fin && __builtin_isfinite(R[i]);
+    if (fin)
+      for (int i = 0; i < 9; ++i) Rp[i] = R[i];
+  }
+  double x[3];
+  mat3_vec(Rp, cv, x);
+  for (int i = 0; i < 3; ++i) pp[i] = ct[i] - x[i];
+}
+
+// One row of the free-wrist solve (p: after ik_prepare; po: 3 doubles; m: IkMem of (T, D + 6)).  Leaves q in m.q,
+// writes palm_pos [3], palm_rot [9], err [T] and *iters, returns the status.  Status 2 leaves m untouched.
+CDX_HD int ik_pose_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0,
+                       const double* target, const double* palm0_pos, const double* palm0_rot, const double* w,
+                       const IkMem& m, double* palm_pos, double* palm_rot, double* err, int32_t* iters) {
+  const int T = c.n_tips, D = c.n_dofs, Dp = D + 6, n = 3 * T, s = m.s;
+  bool fin = true;
+  for (int d = 0; d < D; ++d) {
+    const double v = q0[d];
+    fin = fin && __builtin_isfinite(v) && __builtin_isfinite((float)v);
+  }
+  for (int i = 0; i < n; ++i) fin = fin && __builtin_isfinite(target[i]);
+  if (palm0_pos) {
+    for (int i = 0; i < 3; ++i) fin = fin && __builtin_isfinite(palm0_pos[i]);
+    for (int i = 0; i < 9; ++i) fin = fin && __builtin_isfinite(palm0_rot[i]);
+  }
+  if (w)
+    for (int k = 0; k < T; ++k) fin = fin && __builtin_isfinite(w[k]);
+  *iters = 0;
+  if (!fin) {
+    for (int k = 0; k < T; ++k) err[k] = NAN;
+    for (int i = 0; i < 3; ++i) palm_pos[i] = NAN;
+    for (int i = 0; i < 9; ++i) palm_rot[i] = NAN;
+    return 2;
+  }
+  for (int d = 0; d < D; ++d) {
+    const float f = (float)q0[d], lo = (float)p.lower[d], hi = (float)p.upper[d];
+    m.q[(size_t)d * s] = f < lo ? lo : (f > hi ? hi : f);
+  }
+  const QStride q{m.q, s}, qn{m.qn, s};
+  double Rp[9], pp[3], Rn[9], pn[3];
+  if (palm0_pos) {
+    for (int i = 0; i < 9; ++i) Rp[i] = palm0_rot[i];
+    for (int i = 0; i < 3; ++i) pp[i] = palm0_pos[i];
+  } else {
+    double* v = m.dv + (size_t)n * s;  // (the second residual buffer: free until the first trial point)
+    for (int k = 0; k < T; ++k) {
+      float pf[3];
+      fk_tip(c, k, q, pf, nullptr);
+      for (int i = 0; i < 3; ++i) v[(size_t)(3 * k + i) * s] = (double)pf[i];
+    }
+    ik_pose_start(T, v, s, target, po, w, Rp, pp);
+  }
+  int cur = 0;
+  double emax;
+  double cost = ik_eval(c, p, q, target, w, Rp, pp, po, m.dv, s, &emax);
+  double mu = p.mu0;
+  int it = 0, status;
+  for (;;) {
+    if (emax <= p.tol) { status = 0; break; }
+    if (it >= p.max_iters) { status = 1; break; }
+    ++it;
+    // Jl at q: the joint columns, then t_b and ω_b
+    CDX_IK_UNROLL
+    for (int i = 0; i < n * Dp; ++i) m.J[(size_t)i * s] = 0.f;
+    for (int k = 0; k < T; ++k) {
+      float pf[3];
+      fk_tip(c, k, q, pf, nullptr);
+      fk_tip_columns(c, k, q, pf, [&](int d, const float* l, const float*) {
+        for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * k + i) * Dp + d) * s] = l[i];
+      });
+      float* r0 = m.J + (size_t)((3 * k) * Dp + D) * s;
+      float* r1 = m.J + (size_t)((3 * k + 1) * Dp + D) * s;
+      float* r2 = m.J + (size_t)((3 * k + 2) * Dp + D) * s;
+      r0[0] = 1.f; r1[(size_t)1 * s] = 1.f; r2[(size_t)2 * s] = 1.f;
+      r0[(size_t)4 * s] = pf[2];  r0[(size_t)5 * s] = -pf[1];
+      r1[(size_t)3 * s] = -pf[2]; r1[(size_t)5 * s] = pf[0];
+      r2[(size_t)3 * s] = pf[1];  r2[(size_t)4 * s] = -pf[0];
+    }
+    // u = w·Rpᵀ·(w·d) into y
+    const double* dc = m.dv + (size_t)(cur * n) * s;
+    for (int k = 0; k < T; ++k) {
+      const double wk = w ? w[k] : 1.0;
+      const double r[3] = {wk * dc[(size_t)(3 * k) * s], wk * dc[(size_t)(3 * k + 1) * s], wk * dc[(size_t)(3 * k + 2) * s]};
+      double u[3];
+      mat3t_vec(Rp, r, u);
+      for (int i = 0; i < 3; ++i) m.y[(size_t)(3 * k + i) * s] = wk * u[i];
+    }
+    // g: the joints with their ρ term and bounds, the pose columns bare
+    for (int d = 0; d < Dp; ++d) {
+      double acc = 0.0;
+      CDX_IK_UNROLL
+      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * Dp + d) * s] * m.y[(size_t)a * s];
+      double g = acc;
+      if (d < D) {
+        const double qd = (double)q[d];
+        g = acc + p.rho * (p.ref_q[d] - qd);
+        if ((qd <= p.lower[d] && g < 0.0) || (qd >= p.upper[d] && g > 0.0)) {
+          g = 0.0;
+          for (int a = 0; a < n; ++a) m.J[(size_t)(a * Dp + d) * s] = 0.f;
+        }
+      }
+      m.g[(size_t)d * s] = g;
+    }
+    const double kappa = mu + p.rho;
+    const bool pd = ik_gram_solve(m, w, n, Dp, kappa);
+    // the trial point
+    for (int d = 0; d < D; ++d) {
+      double acc = 0.0;
+      CDX_IK_UNROLL
+      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * Dp + d) * s] * m.y[(size_t)a * s];
+      const double v = (double)q[d] + (m.g[(size_t)d * s] - acc) / kappa;
+      m.qn[(size_t)d * s] = (float)(v < p.lower[d] ? p.lower[d] : (v > p.upper[d] ? p.upper[d] : v));
+    }
+    double st[6];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+    for (int j = 0; j < 6; ++j) {
+      double acc = 0.0;
+      CDX_IK_UNROLL
+      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * Dp + D + j) * s] * m.y[(size_t)a * s];
+      st[j] = (m.g[(size_t)(D + j) * s] - acc) / kappa;
+    }
+    {
+      double x[3];
+      mat3_vec(Rp, st, x);
+      for (int i = 0; i < 3; ++i) pn[i] = pp[i] + x[i];
+      const double a[3] = {0.5 * st[3], 0.5 * st[4], 0.5 * st[5]};
+      const double ss = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], den = 1.0 + ss, one = 1.0 - ss;
+      const double C[9] = {(one + 2.0 * (a[0] * a[0])) / den,        (2.0 * (a[0] * a[1]) - 2.0 * a[2]) / den,
+                           (2.0 * (a[0] * a[2]) + 2.0 * a[1]) / den, (2.0 * (a[1] * a[0]) + 2.0 * a[2]) / den,
+                           (one + 2.0 * (a[1] * a[1])) / den,        (2.0 * (a[1] * a[2]) - 2.0 * a[0]) / den,
+                           (2.0 * (a[2] * a[0]) - 2.0 * a[1]) / den, (2.0 * (a[2] * a[1]) + 2.0 * a[0]) / den,
+                           (one + 2.0 * (a[2] * a[2])) / den};
+      mat3_mul(Rp, C, Rn);
+    }
+    double emn;
+    const double cn = ik_eval(c, p, qn, target, w, Rn, pn, po, m.dv + (size_t)((1 - cur) * n) * s, s, &emn);
+    if (pd && cn < cost) {
+      for (int d = 0; d < D; ++d) m.q[(size_t)d * s] = m.qn[(size_t)d * s];
+      for (int i = 0; i < 9; ++i) Rp[i] = Rn[i];
+      for (int i = 0; i < 3; ++i) pp[i] = pn[i];
+      cur = 1 - cur;
+      cost = cn;
+      emax = emn;
+      mu = mu / p.nu;
+      mu = mu > p.mu_min ? mu : p.mu_min;
+    } else {
+      mu = mu * p.nu;
+      mu = mu < p.mu_max ? mu : p.mu_max;
+    }
+  }
+  const double* dc = m.dv + (size_t)(cur * n) * s;
+  for (int k = 0; k < T; ++k) {
+    const double d[3] = {dc[(size_t)(3 * k) * s], dc[(size_t)(3 * k + 1) * s], dc[(size_t)(3 * k + 2) * s]};
+    err[k] = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+  }
+  for (int i = 0; i < 3; ++i) palm_pos[i] = pp[i];
+  for (int i = 0; i < 9; ++i) palm_rot[i] = Rp[i];
   *iters = it;
   return status;
 }

@@ -10,6 +10,9 @@
 //                       wave ends when its last row stops (rows that stopped sit masked off).  The workgroup is sized
 //                       by the LDS a row needs (ik_lanes): the largest power of two ≤ 64 lanes that leaves room for four
 //                       workgroups on a compute unit — a hand's row needs 1.9 KB, so 16 rows share a workgroup.
+//   ik_pose_kernel      the same layout for the free-wrist solve (ik_pose_row): six more columns per row of Jl (a hand's
+//                       row needs 2.3 KB, still 16 rows a workgroup; iiwa7_allegro 2.8 KB, 8 rows), the palm pose and
+//                       its trial copy in registers.
 #include <hip/hip_runtime.h>
 
 #include "cdx_ik.h"
@@ -58,6 +61,39 @@ __global__ __launch_bounds__(64) void ik_solve_kernel(IkArgs a, int64_t E, const
     else
       ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : m.q[(size_t)d * lanes];
   }
+  iters[e] = it;
+  status[e] = st;
+}
+
+// The free-wrist solve (ik_pose_row): the layout of ik_solve_kernel with D + 6 columns per row of Jl; the pose and its
+// trial copy are indexed by constants and stay in registers.
+__global__ __launch_bounds__(64) void ik_pose_kernel(IkArgs a, int64_t E, const void* __restrict__ q0, int q_f64,
+                                                     const double* __restrict__ target,
+                                                     const double* __restrict__ palm0_pos,
+                                                     const double* __restrict__ palm0_rot, const double* __restrict__ w,
+                                                     void* __restrict__ q, double* __restrict__ palm_pos,
+                                                     double* __restrict__ palm_rot, double* __restrict__ err,
+                                                     int32_t* __restrict__ iters, int32_t* __restrict__ status) {
+  const IkArgs& ka = *(const IkArgs*)(__builtin_amdgcn_kernarg_segment_ptr());
+  const int lanes = (int)blockDim.x, lane = (int)threadIdx.x;
+  const int64_t e = (int64_t)blockIdx.x * lanes + lane;
+  if (e >= E) return;
+  const int T = ka.c.n_tips, D = ka.c.n_dofs;
+  const cdx::IkMem m = cdx::ik_mem_at(ik_lds, T, D + 6, lane, lanes);
+  const cdx::Q0Row q0r{q_f64 ? (const void*)((const double*)q0 + e * D) : (const void*)((const float*)q0 + e * D), q_f64};
+  int32_t it;
+  double pp[3], Rp[9];
+  const int st = cdx::ik_pose_row(ka.c, ka.p, ka.po, q0r, target + e * T * 3, palm0_pos ? palm0_pos + e * 3 : nullptr,
+                                  palm0_rot ? palm0_rot + e * 9 : nullptr, w ? w + e * T : nullptr, m, pp, Rp,
+                                  err + e * T, &it);
+  for (int d = 0; d < D; ++d) {
+    if (q_f64)
+      ((double*)q)[e * D + d] = st == 2 ? ((const double*)q0)[e * D + d] : (double)m.q[(size_t)d * lanes];
+    else
+      ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : m.q[(size_t)d * lanes];
+  }
+  for (int i = 0; i < 3; ++i) palm_pos[e * 3 + i] = pp[i];
+  for (int i = 0; i < 9; ++i) palm_rot[e * 9 + i] = Rp[i];
   iters[e] = it;
   status[e] = st;
 }
@@ -120,6 +156,39 @@ int cdx_ik_solve(const cdx_chain* chain, const cdx_ik_params* params, int64_t E,
   hipLaunchKernelGGL(ik_solve_kernel, dim3((unsigned)blocks), dim3((unsigned)lanes), lds,
                      reinterpret_cast<hipStream_t>(stream), a, E, q0, (int)(q_dtype == CDX_DTYPE_F64), target, palm, w, q,
                      err, iters, status);
+  return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;
+}
+
+int32_t cdx_ik_pose_rows_per_block(int32_t n_tips, int32_t n_dofs) {
+  if (n_tips <= 0 || n_tips > CDX_MAX_TIPS || n_dofs < 0 || n_dofs > CDX_MAX_DOFS) return 0;
+  return ik_lanes(n_tips, n_dofs + 6);
+}
+
+int cdx_ik_solve_pose(const cdx_chain* chain, const cdx_ik_params* params, int64_t E, const void* q0, int32_t q_dtype,
+                      const double* target, const double* palm0_pos, const double* palm0_rot, const double* palm_offset,
+                      const double* w, void*, void* q, double* palm_pos, double* palm_rot, double* err, int32_t* iters,
+                      int32_t* status, cdx_stream_t stream) {
+  int rc = cdx::ik_chain_code(chain);
+  if (rc) return rc;
+  IkArgs a;
+  rc = cdx::ik_prepare(params, chain->n_dofs, &a.p);
+  if (rc) return rc;
+  if (E < 0 || (q_dtype != CDX_DTYPE_F32 && q_dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (!q0 || !target || !q || !palm_pos || !palm_rot || !err || !iters || !status) return CDX_ECHAIN;
+  if (!palm0_pos != !palm0_rot) return CDX_ECHAIN;
+  a.c = *chain;
+  for (int i = 0; i < 3; ++i) {
+    a.po[i] = palm_offset ? palm_offset[i] : 0.0;
+    if (!__builtin_isfinite(a.po[i])) return CDX_EINVAL;
+  }
+  const int T = chain->n_tips, D = chain->n_dofs + 6, lanes = ik_lanes(T, D);
+  const size_t lds = cdx::ik_mem_bytes(T, D) * lanes;
+  const int64_t blocks = (E + lanes - 1) / lanes;
+  if (blocks > 0x7fffffff || lds > 65536) return CDX_EINVAL;
+  hipLaunchKernelGGL(ik_pose_kernel, dim3((unsigned)blocks), dim3((unsigned)lanes), lds,
+                     reinterpret_cast<hipStream_t>(stream), a, E, q0, (int)(q_dtype == CDX_DTYPE_F64), target, palm0_pos,
+                     palm0_rot, w, q, palm_pos, palm_rot, err, iters, status);
   return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;
 }
 

@@ -400,6 +400,44 @@ int cdxh_ik_solve(const cdx_chain* c, const cdx_ik_params* params, int64_t E, co
   return CDX_OK;
 }
 
+// The free-wrist solve (ik_pose_row), with cdx_ik_solve_pose's argument checks.
+int cdxh_ik_solve_pose(const cdx_chain* c, const cdx_ik_params* params, int64_t E, const void* q0, int32_t q_dtype,
+                       const double* target, const double* palm0_pos, const double* palm0_rot, const double* palm_offset,
+                       const double* w, void* q, double* palm_pos, double* palm_rot, double* err, int32_t* iters,
+                       int32_t* status) {
+  int rc = cdx::ik_chain_code(c);
+  if (rc) return rc;
+  cdx_ik_params p;
+  rc = cdx::ik_prepare(params, c->n_dofs, &p);
+  if (rc) return rc;
+  if (E < 0 || (q_dtype != CDX_DTYPE_F32 && q_dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (!q0 || !target || !q || !palm_pos || !palm_rot || !err || !iters || !status) return CDX_ECHAIN;
+  if (!palm0_pos != !palm0_rot) return CDX_ECHAIN;
+  double po[3];
+  for (int i = 0; i < 3; ++i) {
+    po[i] = palm_offset ? palm_offset[i] : 0.0;
+    if (!__builtin_isfinite(po[i])) return CDX_EINVAL;
+  }
+  const int T = c->n_tips, D = c->n_dofs, f64 = q_dtype == CDX_DTYPE_F64;
+  std::vector<double> mem((cdx::ik_mem_bytes(T, D + 6) + 7) / 8);
+  const cdx::IkMem m = cdx::ik_mem_at(mem.data(), T, D + 6, 0, 1);
+  for (int64_t e = 0; e < E; ++e) {
+    const cdx::Q0Row q0r{f64 ? (const void*)((const double*)q0 + e * D) : (const void*)((const float*)q0 + e * D), f64};
+    const int st = cdx::ik_pose_row(*c, p, po, q0r, target + e * T * 3, palm0_pos ? palm0_pos + e * 3 : nullptr,
+                                    palm0_rot ? palm0_rot + e * 9 : nullptr, w ? w + e * T : nullptr, m,
+                                    palm_pos + e * 3, palm_rot + e * 9, err + e * T, iters + e);
+    for (int d = 0; d < D; ++d) {
+      if (f64)
+        ((double*)q)[e * D + d] = st == 2 ? ((const double*)q0)[e * D + d] : (double)m.q[d];
+      else
+        ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : m.q[d];
+    }
+    status[e] = st;
+  }
+  return CDX_OK;
+}
+
 // The minimum-wrench solve (cdx_wrench.h) row by row, with the device entry's argument checks.
 int cdxh_min_wrench(const cdx_wrench_params* params, int64_t E, const double* tips, const double* normals,
                     double* forces, double* wrench, double* margin, double* dual, double* gap, int32_t* iters,

@@ -19,6 +19,12 @@ IKResult.__doc__ = """q [E, D] (the dtype of q0, float32 values), err [E, T] flo
 iters [E] int32, status [E] int32: 0 converged (largest weighted fingertip error ≤ tol), 1 max_iters used,
 2 a non-finite input in the row (q = q0, err = NaN).  Device tensors."""
 
+IKPoseResult = namedtuple("IKPoseResult", ["q", "palm_pose", "palm_pos", "palm_rot", "err", "iters", "status"])
+IKPoseResult.__doc__ = """The free-wrist solve's result: q, err, iters, status as IKResult; palm_pos [E, 3] and palm_rot
+[E, 3, 3] float64, the palm pose the solve returns (fingertips = palm_rot·FK(q) + palm_pos + palm_offset), and
+palm_pose [E, 6] = palm_pos + the XYZ Euler angles of palm_rot, the form the optimisers and ``forward_kinematics`` take.
+A status-2 row has NaN in the three pose fields.  Device tensors."""
+
 LM_DEFAULTS = dict(mu0=1e-3, mu_min=1e-9, mu_max=1e6, nu=4.0)
 
 
@@ -130,3 +136,100 @@ def solve_ik(robot_model, target, link_names, offsets=None, q0=None, palm_pose=N
                              None, N.ptr(q), N.ptr(err), N.ptr(iters), N.ptr(status), N.stream_ptr(dev)),
             "cdx_ik_solve")
     return IKResult(q, err, iters, status)
+
+
+def euler_xyz_matrix(angles):
+    """R = (Rx(a)·Ry(b))·Rz(c) [..., 3, 3] float64 of XYZ Euler angles [..., 3], as csrc/cdx_cost.h's euler_xyz builds
+    the palm rotation.  Any device, batched."""
+    ang = torch.as_tensor(angles, dtype=torch.float64)
+    s, c = torch.sin(ang), torch.cos(ang)
+    one, zero = torch.ones_like(s[..., 0]), torch.zeros_like(s[..., 0])
+
+    def mat(*rows):
+        return torch.stack([torch.stack(r, -1) for r in rows], -2)
+    X = mat((one, zero, zero), (zero, c[..., 0], -s[..., 0]), (zero, s[..., 0], c[..., 0]))
+    Y = mat((c[..., 1], zero, s[..., 1]), (zero, one, zero), (-s[..., 1], zero, c[..., 1]))
+    Z = mat((c[..., 2], -s[..., 2], zero), (s[..., 2], c[..., 2], zero), (zero, zero, one))
+    return torch.matmul(torch.matmul(X, Y), Z)
+
+
+def matrix_to_euler_xyz(R):
+    """The inverse of ``euler_xyz_matrix`` for rotations [..., 3, 3] → angles [..., 3] float64 with |b| ≤ π/2.  From
+    R = [[cb·cc, −cb·sc, sb], [·, ·, −sa·cb], [·, ·, ca·cb]]: b = atan2(R02, hypot(R00, R01)), a = atan2(−R12, R22),
+    c = atan2(−R01, R00).  Where hypot(R00, R01) = 0 (b = ±π/2: a and c act about one axis) c = 0 and
+    a = atan2(R21, R11), which is what the matrix reads at c = 0."""
+    R = torch.as_tensor(R, dtype=torch.float64)
+    h = torch.hypot(R[..., 0, 0], R[..., 0, 1])
+    lock = h == 0
+    b = torch.atan2(R[..., 0, 2], h)
+    a = torch.where(lock, torch.atan2(R[..., 2, 1], R[..., 1, 1]), torch.atan2(-R[..., 1, 2], R[..., 2, 2]))
+    c = torch.where(lock, torch.zeros_like(h), torch.atan2(-R[..., 0, 1], R[..., 0, 0]))
+    return torch.stack([a, b, c], -1)
+
+
+def _start_pose(palm_pose0, E, dev):
+    """(pos [E, 3], rot [E, 3, 3]) contiguous float64 device tensors of a start pose given as [E, 6] / [6] (position +
+    XYZ Euler angles) or as a (pos, rot) pair; (None, None) for None."""
+    if palm_pose0 is None:
+        return None, None
+    if isinstance(palm_pose0, (tuple, list)) and len(palm_pose0) == 2 and hasattr(palm_pose0[1], "shape") \
+            and tuple(palm_pose0[1].shape[-2:]) == (3, 3):
+        return _rows(palm_pose0[0], E, (3,), "palm_pose0 position", dev), _rows(palm_pose0[1], E, (3, 3),
+                                                                               "palm_pose0 rotation", dev)
+    pose = _rows(palm_pose0, E, (6,), "palm_pose0", dev)
+    return pose[:, :3].contiguous(), euler_xyz_matrix(pose[:, 3:]).contiguous()
+
+
+def solve_ik_pose(robot_model, target, link_names, offsets=None, q0=None, palm_pose0=None, palm_offset=None,
+                  weights=None, ref_q=None, rho=0.0, max_iters=100, tol=1e-5, **lm):
+    """Joint angles AND the palm's rigid pose with which the fingertips reach ``target`` [E, T, 3] → IKPoseResult
+    (cdx_ik_solve_pose; the rule is ik_pose_row in csrc/cdx_ik.h).  Arguments as ``solve_ik``, but the palm is an
+    unknown: ``palm_pose0`` [E, 6] or [6] (position + XYZ Euler angles) or a (pos [E, 3], rot [E, 3, 3]) pair is only the
+    start; None starts every row at the weighted Kabsch fit of its start's fingertips onto its targets.  ``rho`` pulls
+    the joints towards ``ref_q`` and damps the pose's step; it never pulls the pose.  The pose is not unique where the
+    joints can make up for it: different starts give different, equally valid hands
+    (results.hand_pose_from_contacts ranks them).  Runs on the current stream without waiting for it."""
+    lib = N.load()
+    dev = robot_model._device
+    T, D = len(link_names), robot_model._n_dofs
+    target = torch.as_tensor(target, dtype=torch.float64, device=dev)
+    if target.ndim == 2 and target.shape == (T, 3):
+        target = target.unsqueeze(0)
+    if target.ndim != 3 or target.shape[1:] != (T, 3):
+        raise ValueError(f"target must have shape [E, {T}, 3], got {tuple(target.shape)}")
+    if not target.is_cuda:
+        raise RuntimeError("compliancedex_amd IK runs on the GPU only")
+    E = target.shape[0]
+    target = target.contiguous()
+    lower, upper = joint_box(robot_model.get_joint_limits())
+    params = ik_params(lower, upper, _host_list(ref_q), rho, max_iters, tol, **lm)
+    if q0 is None:
+        q0 = torch.tensor([params.ref_q[d] for d in range(D)], dtype=torch.float64, device=dev)
+    else:
+        q0 = torch.as_tensor(q0, device=dev)
+        if q0.dtype not in (torch.float32, torch.float64):
+            q0 = q0.to(torch.float64)
+    if q0.shape == (D,):
+        q0 = q0.expand(E, D)
+    if q0.shape != (E, D):
+        raise ValueError(f"q0 must have shape {(E, D)} or {(D,)}, got {tuple(q0.shape)}")
+    q0 = q0.detach().contiguous()
+    pos0, rot0 = _start_pose(palm_pose0, E, dev)
+    w = _rows(weights, E, (T,), "weights", dev)
+    po = _host_list(palm_offset)
+    if po is not None and len(po) != 3:
+        raise ValueError("palm_offset must have 3 entries")
+    po_c = (C.c_double * 3)(*po) if po is not None else None
+    q = torch.empty_like(q0)
+    palm_pos = torch.empty(E, 3, dtype=torch.float64, device=dev)
+    palm_rot = torch.empty(E, 3, 3, dtype=torch.float64, device=dev)
+    err = torch.empty(E, T, dtype=torch.float64, device=dev)
+    iters = torch.empty(E, dtype=torch.int32, device=dev)
+    status = torch.empty(E, dtype=torch.int32, device=dev)
+    chain = robot_model._descriptor(link_names, offsets)
+    dtype = N.DTYPE_F64 if q0.dtype == torch.float64 else N.DTYPE_F32
+    N.check(lib.cdx_ik_solve_pose(chain, C.byref(params), E, N.ptr(q0), dtype, N.ptr(target), N.ptr(pos0), N.ptr(rot0),
+                                  po_c, N.ptr(w), None, N.ptr(q), N.ptr(palm_pos), N.ptr(palm_rot), N.ptr(err),
+                                  N.ptr(iters), N.ptr(status), N.stream_ptr(dev)), "cdx_ik_solve_pose")
+    palm_pose = torch.cat([palm_pos, matrix_to_euler_xyz(palm_rot)], 1)
+    return IKPoseResult(q, palm_pose, palm_pos, palm_rot, err, iters, status)

@@ -114,9 +114,13 @@ class DifferentiableRobotModel(torch.nn.Module):
         return lin[:, 0], ang[:, 0]
 
     def inverse_kinematics(self, target, link_names, offsets=None, q0=None, palm_pose=None, palm_offset=None,
-                           weights=None, ref_q=None, rho=0.0, max_iters=50, tol=1e-5, **lm):
+                           weights=None, ref_q=None, rho=0.0, max_iters=None, tol=1e-5, solve_palm=False, **lm):
         """Joint angles whose fingertips reach ``target`` [E, T, 3] → IKResult(q, err, iters, status); see
-        ik.solve_ik."""
-        from .ik import solve_ik
-        return solve_ik(self, target, link_names, offsets, q0, palm_pose, palm_offset, weights, ref_q, rho, max_iters,
-                        tol, **lm)
+        ik.solve_ik.  ``solve_palm=True`` solves the palm's pose with the joints → IKPoseResult (ik.solve_ik_pose);
+        ``palm_pose`` is then only the start (None: the Kabsch start).  ``max_iters`` None: 50, or 100 with the palm."""
+        from .ik import solve_ik, solve_ik_pose
+        if solve_palm:
+            return solve_ik_pose(self, target, link_names, offsets, q0, palm_pose, palm_offset, weights, ref_q, rho,
+                                 100 if max_iters is None else max_iters, tol, **lm)
+        return solve_ik(self, target, link_names, offsets, q0, palm_pose, palm_offset, weights, ref_q, rho,
+                        50 if max_iters is None else max_iters, tol, **lm)

@@ -365,6 +365,21 @@ int cdx_ik_solve(const cdx_chain* chain, const cdx_ik_params* params, int64_t E,
 int32_t cdx_ik_rows_per_block(int32_t n_tips, int32_t n_dofs);
 size_t cdx_ik_abi_size(void);
 
+/* Free-wrist inverse kinematics: cdx_ik_solve with the palm's rigid pose an unknown next to the joint angles (the rule is
+ * ik_pose_row in csrc/cdx_ik.h; one launch, no workspace, `workspace` may be NULL).  Arguments as cdx_ik_solve, but:
+ *   palm0_pos [E*3] / palm0_rot [E*9] f64 (row-major rotation, orthogonal by the caller's contract): the start pose,
+ *   both or neither — both NULL starts every row at the weighted Kabsch fit of its start's fingertips onto its targets.
+ * Outputs besides q / err / iters / status: palm_pos [E*3], palm_rot [E*9] f64, the pose at the returned q (the
+ *   fingertips are palm_rot·FK(q) + palm_pos + palm_offset).  A status-2 row (a non-finite q0, target, w, palm0_pos or
+ *   palm0_rot) has q = q0 and NaN in palm_pos / palm_rot / err.
+ * Return codes as cdx_ik_solve; exactly one of palm0_pos / palm0_rot NULL → CDX_ECHAIN. */
+int cdx_ik_solve_pose(const cdx_chain* chain, const cdx_ik_params* params, int64_t E, const void* q0, int32_t q_dtype,
+                      const double* target, const double* palm0_pos, const double* palm0_rot,
+                      const double* palm_offset, const double* w, void* workspace, void* q, double* palm_pos,
+                      double* palm_rot, double* err, int32_t* iters, int32_t* status, cdx_stream_t stream);
+/* Rows per workgroup of cdx_ik_solve_pose for a chain of these sizes (for tests of its seams). */
+int32_t cdx_ik_pose_rows_per_block(int32_t n_tips, int32_t n_dofs);
+
 /* Batched minimum-wrench contact forces (what the reference asks of cvxpy in math_utils.py:6-57; the rule is
  * csrc/cdx_wrench.h): per candidate row, the forces F [T][3] inside their friction cones (n̂·F ≤ −‖F‖/sqrt(1 + mu²))
  * that press at least min_force along the normal (n̂·F ≤ −min_force) and minimise

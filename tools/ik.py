@@ -9,6 +9,13 @@ same rule on the device — fingertips from ``compute_forward_kinematics``, the 
 to --host-rows.  Besides the times the record keeps the share of rows each path converged, the iteration counts, and how
 far the torch statement's joint angles are from the kernel's.
 
+The free-wrist solve (cdx_ik_solve_pose, ``solve_ik_pose``) is timed beside it on the same q* and q0: targets the
+fingertips of (q*, palm*) with palm* within ±0.2 m and XYZ angles (±π, ±1.2, ±π), the start pose palm* moved by ≤ 0.05 m
+per axis and turned by ≤ 0.3 rad about a random axis — the family of tests/_ik_pose.py —, once with that start pose and
+once with the Kabsch start; its own torch statement (``torch_ik_pose``) and its host build on one core
+(cdxh_ik_solve_pose) are the yardsticks, and ``pose_over_fixed`` is its time over the fixed-palm solve's at the same E.
+Iteration medians and the share of rows that use all ``max_iters`` iterations (status 1) are kept for every path.
+
 Device times are HIP events around one call after a warm-up call of every path, the paths alternating within each
 repeat; the median of --reps and the spread (max − min)/median are kept.
 
@@ -35,7 +42,8 @@ IIWA7_OFFSETS = [[0.0, -0.04, 0.015], [0.0, -0.04, 0.015], [0.0, -0.04, 0.015], 
 
 
 def inputs(rm, links, offsets, E, spread, seed=0):
-    """(q0, target) on the device: q* in the inner 80 % of the joint box, q0 = q* ± spread clamped."""
+    """(q0, target, lo, hi, q*) — all but q* on the device: q* in the inner 80 % of the joint box, q0 = q* ± spread
+    clamped."""
     import torch
     from compliancedex_amd.ik import joint_box
     lower, upper = joint_box(rm.get_joint_limits())
@@ -46,7 +54,7 @@ def inputs(rm, links, offsets, E, spread, seed=0):
     q0 = torch.minimum(torch.maximum(qs + spread * (2.0 * torch.rand(qs.shape, generator=g, dtype=torch.float64) - 1.0),
                                      lo), hi)
     target = rm.compute_forward_kinematics(qs.cuda().float(), links, offsets=offsets)[0].double().view(E, len(links), 3)
-    return q0.cuda(), target, lo.cuda(), hi.cuda()
+    return q0.cuda(), target, lo.cuda(), hi.cuda(), qs
 
 
 def torch_ik(rm, links, offsets, q0, target, lo, hi, max_iters=50, tol=1e-5, mu0=1e-3, mu_min=1e-9, mu_max=1e6, nu=4.0):
@@ -93,6 +101,112 @@ def torch_ik(rm, links, offsets, q0, target, lo, hi, max_iters=50, tol=1e-5, mu0
     return q, r.view(E, T, 3).norm(dim=2), iters
 
 
+def pose_inputs(rm, links, offsets, qs, E, seed=1):
+    """(target, pos0, rot0) on the device for q* ``qs``: the fingertips of (q*, palm*) and the displaced start pose."""
+    import math
+    import torch
+    from compliancedex_amd.ik import euler_xyz_matrix
+    g = torch.Generator().manual_seed(seed)
+
+    def rand(*shape):
+        return 2.0 * torch.rand(*shape, generator=g, dtype=torch.float64) - 1.0
+    pos = 0.2 * rand(E, 3)
+    rot = euler_xyz_matrix(rand(E, 3) * torch.tensor([math.pi, 1.2, math.pi], dtype=torch.float64))
+    axis = torch.nn.functional.normalize(torch.randn(E, 3, generator=g, dtype=torch.float64), dim=1)
+    ang = 0.3 * rand(E, 1)
+    K = torch.zeros(E, 3, 3, dtype=torch.float64)
+    K[:, 0, 1], K[:, 0, 2], K[:, 1, 0] = -axis[:, 2], axis[:, 1], axis[:, 2]
+    K[:, 1, 2], K[:, 2, 0], K[:, 2, 1] = -axis[:, 0], -axis[:, 1], axis[:, 0]
+    turn = torch.eye(3, dtype=torch.float64) + torch.sin(ang)[:, :, None] * K + (1 - torch.cos(ang))[:, :, None] * (K @ K)
+    pos0, rot0 = pos + 0.05 * rand(E, 3), rot @ turn
+    local = rm.compute_forward_kinematics(qs.cuda().float(), links, offsets=offsets)[0].double().view(E, len(links), 3)
+    target = torch.einsum("eij,etj->eti", rot.cuda(), local) + pos.cuda()[:, None]
+    return target.contiguous(), pos0.cuda().contiguous(), rot0.cuda().contiguous()
+
+
+def torch_ik_pose(rm, links, offsets, q0, target, pos0, rot0, lo, hi, max_iters=100, tol=1e-5, mu0=1e-3, mu_min=1e-9,
+                  mu_max=1e6, nu=4.0):
+    """ik_pose_row of csrc/cdx_ik.h (ρ = 0, unit weights, a given start pose) with torch operators on the device."""
+    import torch
+    E, D = q0.shape
+    T = len(links)
+    lo32, hi32 = lo.float(), hi.float()
+    dev = q0.device
+
+    def residual(q32, R, p):
+        v = rm.compute_forward_kinematics(q32, links, offsets=offsets)[0].double().view(E, T, 3)
+        return target - (torch.einsum("eij,etj->eti", R, v) + p[:, None]), v
+
+    q, R, p = torch.minimum(torch.maximum(q0.float(), lo32), hi32), rot0.clone(), pos0.clone()
+    r, v = residual(q, R, p)
+    cost = 0.5 * (r * r).sum((1, 2))
+    mu = torch.full((E,), mu0, dtype=torch.float64, device=dev)
+    iters = torch.zeros(E, dtype=torch.int32, device=dev)
+    eye = torch.eye(3 * T, dtype=torch.float64, device=dev)
+    eye3 = torch.eye(3, dtype=torch.float64, device=dev)
+    for _ in range(max_iters):
+        act = r.norm(dim=2).amax(1) > tol
+        if not bool(act.any()):
+            break
+        iters += act
+        J = torch.zeros(E, T, 3, D + 6, dtype=torch.float64, device=dev)
+        J[..., :D] = rm.compute_fingertip_jacobians(q, links, offsets)[0].double()
+        J[..., D:D + 3] = eye3
+        J[:, :, 0, D + 4], J[:, :, 0, D + 5] = v[:, :, 2], -v[:, :, 1]
+        J[:, :, 1, D + 3], J[:, :, 1, D + 5] = -v[:, :, 2], v[:, :, 0]
+        J[:, :, 2, D + 3], J[:, :, 2, D + 4] = v[:, :, 1], -v[:, :, 0]
+        J = J.view(E, 3 * T, D + 6)
+        u = torch.einsum("eji,etj->eti", R, r).reshape(E, 3 * T)
+        g = torch.bmm(J.transpose(1, 2), u.unsqueeze(2)).squeeze(2)
+        qd = q.double()
+        free = torch.ones(E, D + 6, dtype=torch.bool, device=dev)
+        free[:, :D] = ~(((qd <= lo) & (g[:, :D] < 0)) | ((qd >= hi) & (g[:, :D] > 0)))
+        J = J * free.unsqueeze(1)
+        g = g * free
+        A = torch.bmm(J, J.transpose(1, 2)) + mu.view(E, 1, 1) * eye
+        y, info = torch.linalg.solve_ex(A, torch.bmm(J, g.unsqueeze(2)))
+        delta = (g - torch.bmm(J.transpose(1, 2), y).squeeze(2)) / mu.view(E, 1)
+        qn = torch.minimum(torch.maximum(qd + delta[:, :D], lo), hi).float()
+        pn = p + torch.einsum("eij,ej->ei", R, delta[:, D:D + 3])
+        a = 0.5 * delta[:, D + 3:]
+        s = (a * a).sum(1).view(E, 1, 1)
+        ax = torch.zeros(E, 3, 3, dtype=torch.float64, device=dev)
+        ax[:, 0, 1], ax[:, 0, 2], ax[:, 1, 0] = -a[:, 2], a[:, 1], a[:, 2]
+        ax[:, 1, 2], ax[:, 2, 0], ax[:, 2, 1] = -a[:, 0], -a[:, 1], a[:, 0]
+        Rn = R @ (((1 - s) * eye3 + 2 * a[:, :, None] * a[:, None, :] + 2 * ax) / (1 + s))
+        rn, vn = residual(qn, Rn, pn)
+        cn = 0.5 * (rn * rn).sum((1, 2))
+        ok = act & (info == 0) & (cn < cost)
+        q = torch.where(ok.unsqueeze(1), qn, q)
+        p = torch.where(ok.unsqueeze(1), pn, p)
+        R = torch.where(ok.view(E, 1, 1), Rn, R)
+        r = torch.where(ok.view(E, 1, 1), rn, r)
+        v = torch.where(ok.view(E, 1, 1), vn, v)
+        cost = torch.where(ok, cn, cost)
+        mu = torch.where(act, torch.where(ok, (mu / nu).clamp(min=mu_min), (mu * nu).clamp(max=mu_max)), mu)
+    return q, r.norm(dim=2), iters
+
+
+def host_pose_seconds(rm, links, offsets, q0, target, pos0, rot0):
+    """Seconds of cdxh_ik_solve_pose on one core, and its status / iteration arrays."""
+    import numpy as np
+    from compliancedex_amd import _host, _native as N
+    from compliancedex_amd.ik import ik_params, joint_box
+    lib, p = _host.load(), _host.ptr
+    params = ik_params(*joint_box(rm.get_joint_limits()), max_iters=100)
+    desc = rm._descriptor(links, offsets)
+    q0, target, pos0, rot0 = (np.ascontiguousarray(t.cpu().numpy()) for t in (q0, target, pos0, rot0))
+    E, T = q0.shape[0], len(links)
+    q, pp, pr, err = np.empty_like(q0), np.empty((E, 3)), np.empty((E, 9)), np.empty((E, T))
+    iters, status = np.empty(E, np.int32), np.empty(E, np.int32)
+    t = time.perf_counter()
+    rc = lib.cdxh_ik_solve_pose(desc, params, E, p(q0), N.DTYPE_F64, p(target), p(pos0), p(rot0), None, None, p(q), p(pp),
+                                p(pr), p(err), p(iters), p(status))
+    dt = time.perf_counter() - t
+    assert rc == 0
+    return dt, status, iters
+
+
 def host_seconds(rm, links, offsets, q0, target):
     """Seconds of cdxh_ik_solve on one core, and its status / iteration arrays."""
     import numpy as np
@@ -114,16 +228,21 @@ def host_seconds(rm, links, offsets, q0, target):
 
 
 def run_shape(robot, E, args):
+    import numpy as np
     import torch
-    from compliancedex_amd import DifferentiableRobotModel, solve_ik
+    from compliancedex_amd import DifferentiableRobotModel, solve_ik, solve_ik_pose
     rm = DifferentiableRobotModel(robot, device="cuda")
     if robot == "iiwa7_allegro":
         links, offsets, spread = IIWA7_LINKS, IIWA7_OFFSETS, 0.2
     else:
         links, offsets, spread = rm.chain.config["ee_link_name"], rm.chain.config["ee_link_offset"], 0.3
-    q0, target, lo, hi = inputs(rm, links, offsets, E, spread)
+    q0, target, lo, hi, qs = inputs(rm, links, offsets, E, spread)
+    ptarget, pos0, rot0 = pose_inputs(rm, links, offsets, qs, E)
     paths = {"kernel": lambda: solve_ik(rm, target, links, offsets, q0=q0),
-             "torch": lambda: torch_ik(rm, links, offsets, q0, target, lo, hi)}
+             "torch": lambda: torch_ik(rm, links, offsets, q0, target, lo, hi),
+             "pose_kernel": lambda: solve_ik_pose(rm, ptarget, links, offsets, q0=q0, palm_pose0=(pos0, rot0)),
+             "pose_kernel_kabsch": lambda: solve_ik_pose(rm, ptarget, links, offsets, q0=q0),
+             "pose_torch": lambda: torch_ik_pose(rm, links, offsets, q0, ptarget, pos0, rot0, lo, hi)}
     for f in paths.values():  # warm-up: code objects, allocator blocks
         f()
     torch.cuda.synchronize()
@@ -145,6 +264,25 @@ def run_shape(robot, E, args):
         rec["host_one_core_ms"] = round(sec * 1e3, 2)
         rec["host_converged"] = round(float((hstatus == 0).mean()), 5)
         rec["host_over_kernel"] = round(sec * 1e3 / rec["kernel"]["median_ms"], 1)
+    for name in ("pose_kernel", "pose_kernel_kabsch"):
+        pres = paths[name]()
+        rec[name + "_converged"] = round(float((pres.status == 0).double().mean()), 5)
+        rec[name + "_all_iters_share"] = round(float((pres.status == 1).double().mean()), 5)
+        rec[name + "_iters_median_max"] = [int(pres.iters.median()), int(pres.iters.max())]
+    pres = paths["pose_kernel"]()
+    pq, perr, piters = paths["pose_torch"]()
+    rec["pose_torch_converged"] = round(float((perr.amax(1) <= 1e-5).double().mean()), 5)
+    rec["pose_torch_iters_median_max"] = [int(piters.median()), int(piters.max())]
+    rec["pose_torch_q_max_abs_diff"] = float((pq.double() - pres.q).abs().max())
+    rec["pose_torch_over_kernel"] = round(rec["pose_torch"]["median_ms"] / rec["pose_kernel"]["median_ms"], 1)
+    rec["pose_over_fixed"] = round(rec["pose_kernel"]["median_ms"] / rec["kernel"]["median_ms"], 2)
+    rec["kernel_all_iters_share"] = round(float((res.status == 1).double().mean()), 5)
+    if E <= args.host_rows:
+        sec, hstatus, hiters = host_pose_seconds(rm, links, offsets, q0, ptarget, pos0, rot0)
+        rec["pose_host_one_core_ms"] = round(sec * 1e3, 2)
+        rec["pose_host_converged"] = round(float((hstatus == 0).mean()), 5)
+        rec["pose_host_iters_median_max"] = [int(np.median(hiters)), int(hiters.max())]
+        rec["pose_host_over_kernel"] = round(sec * 1e3 / rec["pose_kernel"]["median_ms"], 1)
     rec["device"] = torch.cuda.get_device_name(0)
     return rec
 
