@@ -14,8 +14,6 @@
 //                               and the five parameter gradients        — :713-769, :49-118
 #include <hip/hip_runtime.h>
 
-#include "cdx_ab.h"
-
 #include <atomic>
 #include <cstdlib>
 
@@ -530,39 +528,16 @@ struct ClosureWs {
   size_t bytes;
 };
 
-// Where the screened closure forks the GPIS mean onto its side stream (CDX_FORK_MEAN overrides):
-//   2 (default): after the screen — the mean fills the CUs the selection / compaction kernels leave
-//     idle and shares the machine with the exact pass: 1.156–1.163 vs 1.188–1.200 ms per closure at
-//     config 2 unforked (profiles/r02o_fork_point_ab.txt);
-//   1: beside the screen — the screen stretched 0.334 → 0.425 ms (bf16 version), net loss
-//     (profiles/r02g_fork_mean_ab.txt);  3: after the exact pass, beside the ∇std pass: 1.175 ms;
-//   4: after the screen kernel, before its selection / compaction (≈ 30 µs of a nearly idle chip);
-//   0: no fork.  Values above 4 are taken as 0.
-int fork_point() {
-  static const int at = [] {
-    const char* e = cdx::ab_env("CDX_FORK_MEAN");
-    const int v = e ? std::max(0, atoi(e)) : 2;
-    return v > 4 ? 0 : v;
-  }();
-  return at;
-}
-bool fork_mean() {
-  static const bool on = fork_point() > 0;
-  return on;
-}
-
 // The closure screens the all-tip rows with the bf16 estimate when the GPIS state carries a
-// calibrated screen (cdx_gpis_screen_prepare + screen_delta), CDX_NO_SCREEN is unset and there are
+// calibrated screen (cdx_gpis_screen_prepare + screen_delta) and there are
 // enough rows to fill the chip: below SCREEN_MIN_ROWS the screen runs a handful of workgroups and
 // its fixed cost (five launches) exceeds the fp64 pass it saves (config 1: E = 64, N = 361 runs
 // 0.16 ms unscreened on split-K, 1.6 ms screened).
 constexpr int64_t SCREEN_MIN_ROWS = 4096;
 
 bool screen_on(const cdx_problem* p, int64_t E) {
-  static const bool off = cdx::ab_env("CDX_NO_SCREEN") != nullptr;
   const int64_t Ms = (int64_t)p->n_query_levels * E * p->chain.n_tips;
-  return !off && p->gpis.screen && p->gpis.screen_delta > 0 && p->chain.n_tips <= CDX_MAX_TIPS &&
-         Ms >= SCREEN_MIN_ROWS;
+  return p->gpis.screen && p->gpis.screen_delta > 0 && p->chain.n_tips <= CDX_MAX_TIPS && Ms >= SCREEN_MIN_ROWS;
 }
 
 // The variance cost takes max_f log(100·std_f) (:730), so ∇std is only ever needed at one
@@ -604,80 +579,15 @@ ClosureWs closure_ws_layout(const cdx_problem* p, int64_t E, char* base) {
   return w;
 }
 
-// Side stream of the screened closure (one per device, created on first use): the GPIS mean
-// (fp64 VALU-bound, 4-wave workgroups, 96 VGPRs, 8 KB LDS) runs concurrently with the selection and
-// exact-pass kernels (fork_point); the level kernel waits for it.  Fork and join are event waits
-// (hipGraph-capturable).  Not for concurrent cdx_closure calls from several host threads on one
-// device.
+// Side stream of the screened closure (one per device, created on first use): the Kabsch records, the GPIS
+// mean (fp64 VALU-bound, 4-wave workgroups, 96 VGPRs, 8 KB LDS) and the level kernel run on it beside the
+// selection, exact-pass and ∇std kernels of the caller's stream; the combine kernel waits for it.  Fork and
+// join are event waits (hipGraph-capturable).  Not for concurrent cdx_closure calls from several host
+// threads on one device.
 struct SideStream {
   hipStream_t s = nullptr;
-  hipEvent_t fork = nullptr, join = nullptr;  // main → side before mean A, side → main after it
-  hipEvent_t gate = nullptr, joinB = nullptr; // main → side after the ∇std pass, side → main after mean B
-  hipEvent_t late = nullptr;                   // main → side after the refine kernel (mean_sched() 4)
-  // the split mean schedule (mean_sched() 2): a second side stream for the mean chunks
-  hipStream_t s2 = nullptr;
-  hipEvent_t g1 = nullptr, g2 = nullptr, e2a = nullptr, jb = nullptr;
+  hipEvent_t fork = nullptr, join = nullptr;  // main → side at the fork, side → main after the side's last launch
 };
-
-// Mean schedule of the screened closure (CDX_MEAN_SCHED): 1 (default) the whole mean on the side stream
-// after the Kabsch records; 2 the mean in two chunks on a second side stream, each in a window where the
-// main stream runs latency- or bandwidth-bound kernels: rows [0, M1) (CDX_MEAN_CHUNK1 of them, default 0.3)
-// beside the selection / compaction — the refine pass waits for them —, the rest beside the merge and the
-// exact selection after the refine pass; the level kernel follows the all-tip and target rows; 4 the
-// whole mean after the refine kernel (the side stream waits an event recorded between it and the merge),
-// beside the bandwidth-bound merge and the latency-bound exact selection, instead of whichever of the
-// refine pass and the mean the command processor happens to dispatch first after the records.
-int mean_sched() {
-  static const int m = [] {
-    const char* e = cdx::ab_env("CDX_MEAN_SCHED");
-    return e ? atoi(e) : 1;
-  }();
-  return m;
-}
-// Order on the side stream (CDX_MEAN_FIRST): 0 (round 5 default) the Kabsch records, then mean A; 1 mean A
-// first (round 4's default, with the one-workgroup compaction: the mean then started in the window of the
-// latency-bound selection and compaction, 1.013 vs 1.036 ms, profiles/r04q_ab_mean_first_side_prio.jsonl).
-// With the compaction spread over the chip (screen_count / screen_place kernels, round 5) the mean's
-// workgroups arriving first stretch those two kernels instead: records first measured 0.984–0.989 vs
-// 0.996–0.998 ms per closure over 3 interleaved rounds (profiles/r05n_ab_side_order.jsonl).
-bool mean_first() {
-  static const bool on = [] {
-    const char* e = cdx::ab_env("CDX_MEAN_FIRST");
-    return e && atoi(e) != 0;
-  }();
-  return on;
-}
-// CDX_JOIN_EARLY=1: the caller's stream waits for the side stream (records, mean, level kernel) before the ∇std pass
-// instead of before the combine kernel — the level kernel ends ≈ 3 µs before the ∇std pass would start, and the
-// wait in front of the combine costs ≈ 7 µs of gap (A/B).
-bool join_early() {
-  static const bool on = [] {
-    const char* e = cdx::ab_env("CDX_JOIN_EARLY");
-    return e && atoi(e) != 0;
-  }();
-  return on;
-}
-double mean_chunk1() {
-  static const double f = [] {
-    const char* e = cdx::ab_env("CDX_MEAN_CHUNK1");
-    const double v = e ? atof(e) : 0.3;
-    return v < 0 ? 0.0 : (v > 1 ? 1.0 : v);
-  }();
-  return f;
-}
-
-// CDX_MEAN_SPLIT=1 splits the forked mean: part A — the all-tip and target rows, which the level
-// kernel reads — at the fork point; part B — the pregrasp and palm rows, read only by the combine
-// kernel — gated behind the ∇std pass, beside the latency-bound level kernel (3E lanes, ≈ 1/5 of the
-// SIMDs).  Off by default: 1.135–1.154 vs 1.095–1.110 ms per closure (profiles/r03e_mean_split_ab.jsonl)
-// — mean B's waves share SIMDs with the level kernel's long dependent chains and stretch them.
-bool mean_split() {
-  static const bool on = [] {
-    const char* e = cdx::ab_env("CDX_MEAN_SPLIT");
-    return e && atoi(e) != 0;
-  }();
-  return on;
-}
 
 // Kabsch records computed ahead of the level kernel (closure_kabsch_kernel), CDX_KABSCH_AHEAD: 1
 // (default) on the side stream ahead of the mean, one fork after the screen kernel; 0 the level kernel
@@ -691,27 +601,6 @@ int kabsch_mode() {
   return m;
 }
 
-// CDX_GRAD_FOLD=0 keeps the ∇std finalize kernel (A/B); default: the screened closure's level kernel
-// sums the ∇std pieces of its group itself (GpisView::fold) — one launch fewer.
-bool grad_fold() {
-  static const bool on = [] {
-    const char* e = cdx::ab_env("CDX_GRAD_FOLD");
-    return !e || atoi(e) != 0;
-  }();
-  return on;
-}
-
-// Fork/join events: no timing, and (CDX_SIDE_EVENT_FENCE=0 / unset) no system-scope fence — they order
-// two streams of one device, whose kernels see each other's writes at kernel boundaries anyway.
-unsigned side_event_flags() {
-  static const unsigned f = [] {
-    const char* e = cdx::ab_env("CDX_SIDE_EVENT_FENCE");
-    return (e && atoi(e) != 0) ? (unsigned)hipEventDisableTiming
-                               : (unsigned)(hipEventDisableTiming | hipEventDisableSystemFence);
-  }();
-  return f;
-}
-
 bool side_stream(SideStream& out) {
   static SideStream per_dev[64];
   int dev = 0;
@@ -719,27 +608,18 @@ bool side_stream(SideStream& out) {
   SideStream& ss = per_dev[dev];
   if (!ss.s) {
     hipStream_t st;
-    // CDX_SIDE_PRIO: < 0 creates the side stream at the device's lowest priority, > 0 at its highest (the
-    // CP prefers a higher-priority queue's dispatches; round 3's default, −3…−4 µs then with the records
-    // first, profiles/r03zi_side_prio_ab.jsonl, r03zj_side_prio_default_ab.jsonl), 0 normal (round 4
-    // default, with the mean first: the highest priority lets the mean's workgroups starve the main
-    // stream's compaction; 1.013 vs 1.016 (lowest) vs 1.036 ms (highest, records first),
-    // r04q_ab_mean_first_side_prio.jsonl).
-    const char* pe = cdx::ab_env("CDX_SIDE_PRIO");
-    const int want = pe ? atoi(pe) : 0;
-    int least = 0, greatest = 0;
-    hipError_t ce;
-    if (want != 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-      ce = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, want < 0 ? least : greatest);
-    else
-      ce = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    if (ce != hipSuccess) {
+    // normal priority: the highest lets the mean's workgroups starve the caller's stream, the lowest is within
+    // noise (1.013 vs 1.036 / 1.016 ms, profiles/r04q_ab_mean_first_side_prio.jsonl)
+    if (hipStreamCreateWithFlags(&st, hipStreamNonBlocking) != hipSuccess) {
       (void)hipGetLastError();
       return false;
     }
-    hipEvent_t ev[5];
-    for (int i = 0; i < 5; ++i) {
-      if (hipEventCreateWithFlags(&ev[i], side_event_flags()) != hipSuccess) {
+    // no timing and no system-scope fence: the events order two streams of one device, whose kernels see each
+    // other's writes at kernel boundaries anyway (with it 1.102–1.115 vs 1.095–1.108 ms,
+    // profiles/r03h_side_event_fence_ab.jsonl)
+    hipEvent_t ev[2];
+    for (int i = 0; i < 2; ++i) {
+      if (hipEventCreateWithFlags(&ev[i], hipEventDisableTiming | hipEventDisableSystemFence) != hipSuccess) {
         for (int j = 0; j < i; ++j) (void)hipEventDestroy(ev[j]);
         (void)hipStreamDestroy(st);
         (void)hipGetLastError();
@@ -749,38 +629,6 @@ bool side_stream(SideStream& out) {
     ss.s = st;
     ss.fork = ev[0];
     ss.join = ev[1];
-    ss.gate = ev[2];
-    ss.joinB = ev[3];
-    ss.late = ev[4];
-  }
-  if ((mean_sched() == 2 || mean_sched() == 3) && !ss.s2) {
-    // CDX_SIDEB_PRIO: the mean chunks' stream priority (0 normal, default: the merge's workgroups are
-    // dispatched first and the mean fills the CUs around them; > 0 highest, < 0 lowest)
-    const char* pe = cdx::ab_env("CDX_SIDEB_PRIO");
-    const int want = pe ? atoi(pe) : 0;
-    int least = 0, greatest = 0;
-    hipStream_t st;
-    hipError_t ce;
-    if (want != 0 && hipDeviceGetStreamPriorityRange(&least, &greatest) == hipSuccess)
-      ce = hipStreamCreateWithPriority(&st, hipStreamNonBlocking, want < 0 ? least : greatest);
-    else
-      ce = hipStreamCreateWithFlags(&st, hipStreamNonBlocking);
-    hipEvent_t ev[4];
-    int made = 0;
-    if (ce == hipSuccess)
-      for (; made < 4; ++made)
-        if (hipEventCreateWithFlags(&ev[made], side_event_flags()) != hipSuccess) break;
-    if (ce != hipSuccess || made < 4) {
-      for (int j = 0; j < made; ++j) (void)hipEventDestroy(ev[j]);
-      if (ce == hipSuccess) (void)hipStreamDestroy(st);
-      (void)hipGetLastError();
-      return false;
-    }
-    ss.s2 = st;
-    ss.g1 = ev[0];
-    ss.g2 = ev[1];
-    ss.e2a = ev[2];
-    ss.jb = ev[3];
   }
   out = ss;
   return true;
@@ -852,19 +700,6 @@ bool inject_fail(int stage) {
   int want = stage;
   return g_fail_stage.load(std::memory_order_relaxed) == stage &&
          g_fail_stage.compare_exchange_strong(want, 0, std::memory_order_relaxed);
-}
-
-// The screened closure's repair pass (CDX_SCREEN_REPAIR, default 1; 0 only for the cost A/B): when any
-// check of the closure failed — a kept or audited estimate off by more than its margin, an audited row
-// that is its group's exact maximum, a maximum on an unrun row — every all-tip row runs the exact pass
-// and the groups select as the unscreened closure does, inside the same closure (gated launches: no
-// host sync, hipGraph-capturable).
-bool screen_repair() {
-  static const bool on = [] {
-    const char* e = cdx::ab_env("CDX_SCREEN_REPAIR");
-    return !e || atoi(e) != 0;
-  }();
-  return on;
 }
 
 // The variance cost added by the combine kernel instead of the level kernel (CDX_VAR_LATE, default 1; 0 for
@@ -987,17 +822,19 @@ int cdx_closure(const cdx_problem* p, int64_t E, const double* q, const double* 
   if (hipGetLastError() != hipSuccess) return CDX_ELAUNCH;
   const bool scr = screen_on(p, E);
   SideStream ss;
-  const bool fork = scr && fork_mean() && side_stream(ss);
-  const SideStream* pending_b = nullptr;  // mean B still to be joined before the combine kernel
-  const double* krot = nullptr;           // Kabsch records computed ahead (else the level kernel's own SVD)
-  cdx::GradFold fold;                      // ∇std finalize folded into the level (or combine) kernel (screened)
+  const bool fork = scr && side_stream(ss);  // (no side stream: the mean on the caller's stream, no records)
+  const double* krot = nullptr;  // Kabsch records computed ahead (else the level kernel's own SVD)
+  cdx::GradFold fold;            // ∇std finalize folded into the level (or combine) kernel (screened)
   const bool vlate = var_late();
-  bool level_early = false;                // the level kernel already queued (side stream, after the mean)
+  bool level_early = false;      // the level kernel already queued (side stream, after the mean)
   int rc;
   if (!fork) {
     rc = cdx_gpis_mean(&p->gpis, w.X, Mq, w.mean, w.gmean, w.normal, stream);
     if (rc) return rc;
   }
+  GpisView gv;
+  gv.mean = w.mean; gv.gmean = w.gmean; gv.normal = w.normal; gv.std_ = w.std_; gv.gstd = w.gstd;
+  gv.E = E; gv.T = p->chain.n_tips; gv.Lq = p->n_query_levels; gv.e = 0;
   // whitened std at every all-tip query, keeping V = (L⁻¹K*ᵀ)ᵀ for the ∇std pass
   // … and the ∇std fingertip of each (distinct level, candidate): the all-tip rows q_alltip(u, e, f)
   // = (u·E + e)·T + f form groups of T, selected in the std finalize
@@ -1005,22 +842,9 @@ int cdx_closure(const cdx_problem* p, int64_t E, const double* q, const double* 
   if (scr) {
     // bf16 screen of every all-tip row → exact whitened fp64 pass for the fingertips that can still
     // be their group's maximum (≈ 1 per group) → ∇std at the group's maximum from its kept V row;
-    // the mean on the side stream beside the screen (SideStream)
+    // the Kabsch records, the mean and the level kernel on the side stream beside them (SideStream)
     const int T = p->chain.n_tips;
-    // Once the fork point has passed, every return joins the side stream back into `s` first:
-    // under capture an unjoined fork invalidates the graph, and eagerly the mean would keep writing
-    // the workspace after the error return.  (A join recorded before a failed launch_fork only waits
-    // on the event's previous record.)
-    bool forked = false, forkedB = false;
-    const int64_t MqA = mean_split() ? (int64_t)(p->n_query_levels + 1) * E * T : Mq;  // rows of mean A
-    const cdx_stream_t side = reinterpret_cast<cdx_stream_t>(ss.s);
-    // The Kabsch records (closure_kabsch_kernel, kabsch_mode() 1): first on the side stream, right
-    // after the screen kernel (the screen's waves leave too few registers for them to run beside it;
-    // after it they share the chip with the latency-bound selection and compaction), then mean A on
-    // the same stream — one fork, one join: every event record / wait on `s` costs ≈ 5 µs of stream
-    // time (profiles/r03s_*).  The mean is effectively serial after the refine pass anyway (it cannot
-    // share a CU with it), so queueing it behind the records costs nothing.
-    const int kmode = fork ? kabsch_mode() : 0;
+    const bool records = fork && kabsch_mode() == 1;
     auto launch_records = [&](hipStream_t st) {
       const int64_t KE = (int64_t)p->n_levels * E;
       const dim3 kg((unsigned)((KE + 63) / 64));
@@ -1035,176 +859,80 @@ int cdx_closure(const cdx_problem* p, int64_t E, const double* q, const double* 
                            kabsch_noise, seed, w.krot);
       return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;
     };
-    // mean_sched 4: the fork runs the records only; launch_late queues the mean and the level kernel behind
-    // the refine kernel's event
-    const bool late = kmode == 1 && vlate && !mean_split() && !mean_first() && mean_sched() == 4;
+    // One fork, one join: every event record / wait on `s` costs ≈ 5 µs of stream time (profiles/r03s_*).  Once
+    // the fork has passed, every return joins the side stream back into `s` first: under capture an unjoined
+    // fork invalidates the graph, and eagerly the side stream would keep writing the workspace after the error
+    // return.  (A join recorded before a failed launch_fork only waits on the event's previous record.)
+    bool forked = false;
     auto launch_fork = [&]() -> int {
       forked = true;
       if (hipEventRecord(ss.fork, s) != hipSuccess || hipStreamWaitEvent(ss.s, ss.fork, 0) != hipSuccess) return CDX_ELAUNCH;
-      if (kmode == 1 && !mean_first()) {
-        const int r = launch_records(ss.s);
-        if (r) return r;
-      }
-      if (late) return hipEventRecord(ss.join, ss.s) != hipSuccess ? CDX_ELAUNCH : CDX_OK;
-      int r = cdx_gpis_mean(&p->gpis, w.X, MqA, w.mean, w.gmean, w.normal, side);
+      // the records first (the mean first stretches the compaction: 0.996–0.998 vs 0.984–0.989 ms,
+      // profiles/r05n_ab_side_order.jsonl), then the whole mean (its pregrasp / palm rows beside the level kernel
+      // instead: 1.135–1.154 vs 1.095–1.110 ms, profiles/r03e_mean_split_ab.jsonl; in chunks on a second side
+      // stream: +30 µs, profiles/r04cde_ab_vstore_meansched_roots_merge.jsonl; behind the refine kernel:
+      // 1.005–1.007 vs 0.981–0.985 ms, profiles/r06l_ab_mean_after_refine.jsonl)
+      int r = records ? launch_records(ss.s) : CDX_OK;
       if (r) return r;
-      if (kmode == 1 && mean_first() && (r = launch_records(ss.s))) return r;
-      if (vlate) {  // the level kernel reads the mean A rows, the Kabsch records and no std
-        GpisView gv0;
-        gv0.mean = w.mean; gv0.gmean = w.gmean; gv0.normal = w.normal; gv0.std_ = w.std_; gv0.gstd = w.gstd;
-        gv0.E = E; gv0.T = T; gv0.Lq = p->n_query_levels; gv0.e = 0;
-        r = launch_level<true>(p, E, q, comp, target, kabsch_noise, seed, w, gv0, flip, kmode == 1 ? w.krot : nullptr,
-                               ss.s);
+      r = cdx_gpis_mean(&p->gpis, w.X, Mq, w.mean, w.gmean, w.normal, reinterpret_cast<cdx_stream_t>(ss.s));
+      if (r) return r;
+      if (vlate) {  // the level kernel reads the mean, the Kabsch records and no std
+        r = launch_level<true>(p, E, q, comp, target, kabsch_noise, seed, w, gv, flip, records ? w.krot : nullptr, ss.s);
         if (r) return r;
         level_early = true;
       }
       return hipEventRecord(ss.join, ss.s) != hipSuccess ? CDX_ELAUNCH : CDX_OK;
     };
-    auto launch_late = [&]() -> int {  // after the main stream recorded ss.late
-      if (hipStreamWaitEvent(ss.s, ss.late, 0) != hipSuccess) return CDX_ELAUNCH;
-      int r = cdx_gpis_mean(&p->gpis, w.X, Mq, w.mean, w.gmean, w.normal, side);
-      if (r) return r;
-      GpisView gv0;
-      gv0.mean = w.mean; gv0.gmean = w.gmean; gv0.normal = w.normal; gv0.std_ = w.std_; gv0.gstd = w.gstd;
-      gv0.E = E; gv0.T = T; gv0.Lq = p->n_query_levels; gv0.e = 0;
-      r = launch_level<true>(p, E, q, comp, target, kabsch_noise, seed, w, gv0, flip, w.krot, ss.s);
-      if (r) return r;
-      level_early = true;
-      return hipEventRecord(ss.join, ss.s) != hipSuccess ? CDX_ELAUNCH : CDX_OK;
-    };
-    auto launch_b = [&]() -> int {  // mean B, gated behind the work already on `s`
-      if (MqA >= Mq) return CDX_OK;
-      forkedB = true;
-      if (hipEventRecord(ss.gate, s) != hipSuccess || hipStreamWaitEvent(ss.s, ss.gate, 0) != hipSuccess) return CDX_ELAUNCH;
-      const int r = cdx_gpis_mean(&p->gpis, w.X + 3 * MqA, Mq - MqA, w.mean + MqA, w.gmean + 3 * MqA,
-                                  w.normal + 3 * MqA, side);
-      if (r) return r;
-      return hipEventRecord(ss.joinB, ss.s) != hipSuccess ? CDX_ELAUNCH : CDX_OK;
-    };
-    // The split mean schedule (mean_sched 2; needs the records ahead, the variance cost in the combine and
-    // no mean A/B split): side A = ss.s runs the Kabsch records and the level kernel, side B = ss.s2 the
-    // mean chunks.  Phase 1 at the fork point: A records; B rows [0, M1), then g1 (the refine pass waits
-    // for it).  Phase 2 right after the refine kernel (g2 recorded between it and the merge): B the
-    // remaining all-tip / target rows, e2a, the pregrasp / palm rows; A waits e2a, runs the level kernel and
-    // records join; B waits join and records jb, which the main stream waits for before the combine.
-    const bool sched2 = fork && kabsch_mode() == 1 && vlate && !mean_split() && (mean_sched() == 2 || mean_sched() == 3) && ss.s2;
-    // 3: the ∇std pass waits for both side streams (mean chunks, level kernel) instead of the combine, so
-    // that no mean / level workgroup holds a CU the pass needs
-    const bool wait_before_grad = sched2 && mean_sched() == 3;
-    bool joined_early = false;
-    const int64_t M01 = (int64_t)(p->n_query_levels + 1) * E * T;  // all-tip + target rows (the level kernel's)
-    const int64_t M1 = sched2 ? std::min<int64_t>(Mq, (int64_t)(mean_chunk1() * (double)Mq)) : 0;
-    bool forked2 = false;
-    const cdx_stream_t sideB = reinterpret_cast<cdx_stream_t>(ss.s2);
-    auto mean_rows = [&](int64_t a, int64_t b, cdx_stream_t st) -> int {
-      if (b <= a) return CDX_OK;
-      return cdx_gpis_mean(&p->gpis, w.X + 3 * a, b - a, w.mean + a, w.gmean + 3 * a, w.normal + 3 * a, st);
-    };
-    auto launch_fork2 = [&]() -> int {
-      forked = forked2 = true;
-      if (hipEventRecord(ss.fork, s) != hipSuccess || hipStreamWaitEvent(ss.s, ss.fork, 0) != hipSuccess ||
-          hipStreamWaitEvent(ss.s2, ss.fork, 0) != hipSuccess)
-        return CDX_ELAUNCH;
-      int r = launch_records(ss.s);
-      if (!r) r = mean_rows(0, M1, sideB);
-      if (!r && hipEventRecord(ss.g1, ss.s2) != hipSuccess) r = CDX_ELAUNCH;
-      return r;
-    };
-    auto launch_phase2 = [&]() -> int {  // after the main stream recorded g2
-      if (hipStreamWaitEvent(ss.s2, ss.g2, 0) != hipSuccess) return CDX_ELAUNCH;
-      int r = mean_rows(M1, std::max(M1, M01), sideB);
-      if (!r && hipEventRecord(ss.e2a, ss.s2) != hipSuccess) r = CDX_ELAUNCH;
-      if (!r) r = mean_rows(std::max(M1, M01), Mq, sideB);
-      if (r) return r;
-      if (hipStreamWaitEvent(ss.s, ss.e2a, 0) != hipSuccess) return CDX_ELAUNCH;
-      GpisView gv0;
-      gv0.mean = w.mean; gv0.gmean = w.gmean; gv0.normal = w.normal; gv0.std_ = w.std_; gv0.gstd = w.gstd;
-      gv0.E = E; gv0.T = T; gv0.Lq = p->n_query_levels; gv0.e = 0;
-      r = launch_level<true>(p, E, q, comp, target, kabsch_noise, seed, w, gv0, flip, w.krot, ss.s);
-      if (r) return r;
-      level_early = true;
-      if (hipEventRecord(ss.join, ss.s) != hipSuccess || hipStreamWaitEvent(ss.s2, ss.join, 0) != hipSuccess ||
-          hipEventRecord(ss.jb, ss.s2) != hipSuccess)
-        return CDX_ELAUNCH;
-      return CDX_OK;
-    };
     auto joined = [&](int r) -> int {
-      if (forked2) {  // both side streams' queued work, whichever phase failed
-        if ((hipEventRecord(ss.join, ss.s) != hipSuccess || hipEventRecord(ss.jb, ss.s2) != hipSuccess ||
-             hipStreamWaitEvent(s, ss.join, 0) != hipSuccess || hipStreamWaitEvent(s, ss.jb, 0) != hipSuccess) && !r)
-          r = CDX_ELAUNCH;
-        return r;
-      }
       if (forked && hipStreamWaitEvent(s, ss.join, 0) != hipSuccess && !r) r = CDX_ELAUNCH;
-      if (forkedB && hipStreamWaitEvent(s, ss.joinB, 0) != hipSuccess && !r) r = CDX_ELAUNCH;
       return r;
     };
-    // the mean's fork point (kabsch_mode 1 forks once, after the screen, whatever fork_point says)
-    const int fp = kmode == 1 ? 4 : (fork ? fork_point() : 0);
-    if (fp == 1 && (rc = launch_fork())) return joined(rc);
+    // The fork point: with the records, right after the screen kernel (the screen's waves leave too few
+    // registers for them to run beside it; after it they share the chip with the latency-bound selection and
+    // compaction); without them, after the screen's selection and compaction (beside the screen the mean
+    // stretched it 0.334 → 0.425 ms, profiles/r02g_fork_mean_ab.txt; after the exact pass 1.175 vs
+    // 1.156–1.163 ms, unforked 1.188–1.200 ms, profiles/r02o_fork_point_ab.txt).
     auto fork_cb = [](void* c) { return (*static_cast<decltype(launch_fork)*>(c))(); };
-    auto fork2_cb = [](void* c) { return (*static_cast<decltype(launch_fork2)*>(c))(); };
-    rc = sched2 ? cdx::screen_select_launch(p->gpis, w.X, Mg, T, w.screen_ws, w.sv2, w.std_, w.vpos, w.rows, w.keep,
-                                            w.zkey, w.stats, s, +fork2_cb, &launch_fork2)
-                : cdx::screen_select_launch(p->gpis, w.X, Mg, T, w.screen_ws, w.sv2, w.std_, w.vpos, w.rows, w.keep,
-                                            w.zkey, w.stats, s, fp == 4 ? +fork_cb : nullptr, &launch_fork);
+    rc = cdx::screen_select_launch(p->gpis, w.X, Mg, T, w.screen_ws, w.sv2, w.std_, w.vpos, w.rows, w.keep, w.zkey,
+                                   w.stats, s, records ? +fork_cb : nullptr, &launch_fork);
     if (!rc && inject_fail(1)) rc = CDX_ELAUNCH;
     if (rc) return joined(rc);
-    if (!sched2 && fp == 2 && (rc = launch_fork())) return joined(rc);
-    if (sched2 && hipStreamWaitEvent(s, ss.g1, 0) != hipSuccess) return joined(CDX_ELAUNCH);
+    if (fork && !records && (rc = launch_fork())) return joined(rc);
     double* rpart = nullptr;
     int64_t rpad = 0;
     rc = cdx::gpis_refine_launch(p->gpis, w.X, w.rows, w.stats + cdx::SS_EXTRA, (int)Mg, Ms, w.refine_ws, w.V, s, &rpart,
-                                 &rpad, nullptr, true, sched2 ? ss.g2 : (late && forked ? ss.late : nullptr));
-    if (!rc && sched2) rc = launch_phase2();
-    if (!rc && late && forked) rc = launch_late();
+                                 &rpad);
     if (!rc && inject_fail(2)) rc = CDX_ELAUNCH;
     if (rc) return joined(rc);
-    if (!sched2 && fp == 3 && (rc = launch_fork())) return joined(rc);
     rc = cdx::refine_select_launch(p->gpis, w.X, Mg, T, rpart, rpad, w.sv2, w.vpos, w.keep, w.std_, w.var, w.sel,
                                    w.Xg, w.vrow, w.stats, s);
     if (rc) return joined(rc);
-    if (screen_repair()) {
-      // the repair pass, gated on this closure's checks (a no-op launch pair otherwise): every all-tip row
-      // through the exact pass (identity list) and the unscreened selection — no screened result that
-      // failed a check leaves the closure, whichever entry point called it
-      cdx::RepairSel rs;
-      rs.X = w.X; rs.G = Mg; rs.T = T; rs.std_ = w.std_; rs.var = w.var; rs.Xg = w.Xg; rs.sel = w.sel; rs.vrow = w.vrow;
-      rs.stats = w.stats;
-      rc = cdx::gpis_refine_launch(p->gpis, w.X, nullptr, nullptr, (int)Ms, Ms, w.refine_ws, w.V, s, nullptr, nullptr,
-                                   w.stats, false, nullptr, &rs);
-      if (rc) return joined(rc);
-    }
-    if (wait_before_grad) {
-      if (hipStreamWaitEvent(s, ss.jb, 0) != hipSuccess) return joined(CDX_ELAUNCH);
-      joined_early = true;
-    } else if (forked && !sched2 && !forkedB && join_early()) {
-      if (hipStreamWaitEvent(s, ss.join, 0) != hipSuccess) return joined(CDX_ELAUNCH);
-      joined_early = true;
-    }
-    rc = cdx::gpis_grad_launch(p->gpis, w.Xg, Mg, w.sel, w.var, w.gstd, w.grad_ws, s, w.V, w.vrow,
-                               grad_fold() ? &fold : nullptr);
+    // The repair pass, gated on this closure's checks (a no-op launch otherwise; no host sync,
+    // hipGraph-capturable): when any check failed — a kept or audited estimate off by more than its margin, an
+    // audited row that is its group's exact maximum, a maximum on an unrun row — every all-tip row runs the
+    // exact pass (identity list) and the groups select as the unscreened closure does, so no screened result
+    // that failed a check leaves the closure, whichever entry point called it.
+    cdx::RepairSel rs;
+    rs.X = w.X; rs.G = Mg; rs.T = T; rs.std_ = w.std_; rs.var = w.var; rs.Xg = w.Xg; rs.sel = w.sel; rs.vrow = w.vrow;
+    rs.stats = w.stats;
+    rc = cdx::gpis_refine_launch(p->gpis, w.X, nullptr, nullptr, (int)Ms, Ms, w.refine_ws, w.V, s, nullptr, nullptr,
+                                 w.stats, false, &rs);
+    if (rc) return joined(rc);
+    // the ∇std pass leaves its pieces to the level / combine kernel (fold): one launch fewer than its finalize
+    rc = cdx::gpis_grad_launch(p->gpis, w.Xg, Mg, w.sel, w.var, w.gstd, w.grad_ws, s, w.V, w.vrow, &fold);
     if (!rc && inject_fail(3)) rc = CDX_ELAUNCH;
     if (rc) return joined(rc);
-    if (fork && !sched2 && (rc = launch_b())) return joined(rc);
-    // mean A (and the Kabsch records of mode 1) before the level kernel; mean B is joined before the
-    // combine kernel below (sched2: jb follows both side streams)
-    if (forked && !joined_early && hipStreamWaitEvent(s, sched2 ? ss.jb : ss.join, 0) != hipSuccess) {
-      forked = forked2 = false;
-      return joined(CDX_ELAUNCH);
-    }
-    if (kmode == 1 && forked) krot = w.krot;
-    if (forkedB) pending_b = &ss;
+    // the join, before the combine kernel (before the ∇std pass: 0.986–0.991 vs 0.982–0.987 ms,
+    // profiles/r05bk_join_early_ab.jsonl)
+    if (forked && hipStreamWaitEvent(s, ss.join, 0) != hipSuccess) return CDX_ELAUNCH;
+    if (records) krot = w.krot;
   } else {
     const cdx::VarSelect vs{p->chain.n_tips, w.sel, w.Xg};
     rc = cdx::gpis_var_launch(p->gpis, w.X, Ms, w.std_, w.var, w.var_ws, s, w.V, &vs);
     if (rc) return rc;
     rc = cdx::gpis_grad_launch(p->gpis, w.Xg, Mg, w.sel, w.var, w.gstd, w.grad_ws, s, w.V);
+    if (rc) return rc;
   }
-  if (rc) return rc;
-  GpisView gv;
-  gv.mean = w.mean; gv.gmean = w.gmean; gv.normal = w.normal; gv.std_ = w.std_; gv.gstd = w.gstd;
-  gv.E = E; gv.T = p->chain.n_tips; gv.Lq = p->n_query_levels; gv.e = 0;
   GpisView gvl = gv;  // ∇std from the pass's pieces when folded (the level kernel's view, or the combine's: vlate)
   gvl.fold = fold;
   gvl.var = w.var;
@@ -1213,12 +941,8 @@ int cdx_closure(const cdx_problem* p, int64_t E, const double* q, const double* 
   if (!level_early) {
     rc = vlate ? launch_level<true>(p, E, q, comp, target, kabsch_noise, seed, w, gv, flip, krot, s)
                : launch_level<false>(p, E, q, comp, target, kabsch_noise, seed, w, gvl, flip, krot, s);
-    if (rc) {
-      if (pending_b) (void)hipStreamWaitEvent(s, pending_b->joinB, 0);
-      return rc;
-    }
+    if (rc) return rc;
   }
-  if (pending_b && hipStreamWaitEvent(s, pending_b->joinB, 0) != hipSuccess) return CDX_ELAUNCH;
   rc = vlate ? launch_combine<true>(p, E, q, palm_pos, palm_ori, gvl, w, total_loss, total_margin, g_q, g_comp, g_target,
                                     g_palm_pos, g_palm_ori, s)
              : launch_combine<false>(p, E, q, palm_pos, palm_ori, gv, w, total_loss, total_margin, g_q, g_comp, g_target,
@@ -1226,14 +950,6 @@ int cdx_closure(const cdx_problem* p, int64_t E, const double* q, const double* 
   if (rc) return rc;
   cdx::prof_mark(cdx::PROF_COST, false, s);
   return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;
-}
-
-int cdx_ab_switches(void) {
-#if defined(CDX_AB_SWITCHES)
-  return 1;
-#else
-  return 0;
-#endif
 }
 
 int cdx_debug_fail_next_closure(int32_t stage) {
@@ -1339,10 +1055,8 @@ extern "C" int cdx_profile_enable(int stages) {
   using cdx::g_prof;
   const unsigned on = (unsigned)stages & ((1u << cdx::PROF_STAGES) - 1);
   if (on && !g_prof.created) {
-    // timing-only events: no system-scope fence (L2 writeback) at each record; CDX_PROF_EVENT_FLAGS
-    // (hex) overrides the flags for A/B runs
-    unsigned flags = hipEventDisableSystemFence;
-    if (const char* f = cdx::ab_env("CDX_PROF_EVENT_FLAGS")) flags = (unsigned)strtoul(f, nullptr, 16);
+    // timing-only events: no system-scope fence (L2 writeback) at each record
+    const unsigned flags = hipEventDisableSystemFence;
     const int total = cdx::PROF_STAGES * cdx::PROF_POOL * 2;
     hipEvent_t* evs = &g_prof.ev[0][0][0];
     for (int e = 0; e < total; ++e)

@@ -1372,19 +1372,18 @@ int gpis_refine_reset(const cdx_gpis& g, int64_t Mcap, void* ws, hipStream_t s) 
 
 template <int KT>
 static void refine_launch_kt(const cdx_gpis& g, const double* X, int64_t Mcap, const RefineList& rl, double* partial,
-                             int64_t M_pad, double* vout, hipStream_t s, bool prof, hipEvent_t after) {
+                             int64_t M_pad, double* vout, hipStream_t s, bool prof) {
   if (prof) prof_mark(PROF_GPIS_STD, true, s);
   hipLaunchKernelGGL((gpis_std_kernel<KT, MODE_VARL>), dim3(REFINE_PIECES), dim3(ST_THREADS), 0, s, g, X, Mcap, partial,
                      M_pad, 0, g.N_pad / ST_BN, vout, nullptr, nullptr, 0, rl);
   if (prof) prof_mark(PROF_GPIS_STD, false, s);
-  if (after) (void)hipEventRecord(after, s);
   if (!rl.rs.on)  // (the repair pass runs whole units: nothing to merge)
     hipLaunchKernelGGL(gpis_var_merge, dim3(REFINE_PIECES), dim3(MERGE_THREADS), 0, s, g, rl, M_pad, partial, vout);
 }
 
 int gpis_refine_launch(const cdx_gpis& g, const double* X, const int* rows, const int* extra, int G, int64_t Mcap,
                        void* ws, double* vout, hipStream_t s, double** partial_out, int64_t* M_pad_out, const int* gate,
-                       bool prof, hipEvent_t after_refine, const RepairSel* repair) {
+                       bool prof, const RepairSel* repair) {
   if (Mcap <= 0 || G <= 0 || G > Mcap) return CDX_EINVAL;
   if (repair && (!gate || rows || extra || repair->G * repair->T != G || repair->stats != gate)) return CDX_EINVAL;
   const int64_t M_pad = round_up(Mcap, ST_BM);
@@ -1403,9 +1402,9 @@ int gpis_refine_launch(const cdx_gpis& g, const double* X, const int* rows, cons
     for (int nt = 0; nt < Nt; ++nt) rl.uc[nt] = var_unit_cost(nt, g.N, g.N_pad);
   }
   switch (g.kernel) {
-    case CDX_KERNEL_TPS: refine_launch_kt<CDX_KERNEL_TPS>(g, X, Mcap, rl, partial, M_pad, vout, s, prof, after_refine); break;
-    case CDX_KERNEL_RBF: refine_launch_kt<CDX_KERNEL_RBF>(g, X, Mcap, rl, partial, M_pad, vout, s, prof, after_refine); break;
-    default: refine_launch_kt<CDX_KERNEL_JOINT>(g, X, Mcap, rl, partial, M_pad, vout, s, prof, after_refine); break;
+    case CDX_KERNEL_TPS: refine_launch_kt<CDX_KERNEL_TPS>(g, X, Mcap, rl, partial, M_pad, vout, s, prof); break;
+    case CDX_KERNEL_RBF: refine_launch_kt<CDX_KERNEL_RBF>(g, X, Mcap, rl, partial, M_pad, vout, s, prof); break;
+    default: refine_launch_kt<CDX_KERNEL_JOINT>(g, X, Mcap, rl, partial, M_pad, vout, s, prof); break;
   }
   if (partial_out) *partial_out = partial;
   if (M_pad_out) *M_pad_out = M_pad;

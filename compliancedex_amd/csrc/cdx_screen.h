@@ -98,10 +98,10 @@ __device__ __host__ inline bool screen_failed(const int* st) {
   return (st[SS_MISS] | st[SS_AUDIT_MISS] | st[SS_AUDIT_FLIP] | st[SS_FAULT]) != 0;
 }
 
-// The audit's row budget per closure (CDX_SCREEN_AUDIT, default 64; 0 disables the audit): the
-// discarded rows are binned by z (8 bins per octave from z = 1) and the lowest bins are audited while
-// their count stays ≤ the budget, plus the bin that crosses it when the total stays ≤ 4× the budget.
-int screen_audit_rows();
+// The audit's row budget per closure: the discarded rows are binned by z (8 bins per octave from z = 1) and
+// the lowest bins are audited while their count stays ≤ the budget, plus the bin that crosses it when the
+// total stays ≤ 4× the budget.
+constexpr int SCREEN_AUDIT_ROWS = 64;
 constexpr int AUDIT_BINS = 256;
 constexpr unsigned Z_NONE = 0xFFFFFFFFu;  // zkey of a kept / leader row (not an audit candidate)
 __device__ __host__ inline int audit_bin(unsigned key) {

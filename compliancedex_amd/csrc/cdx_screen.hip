@@ -25,8 +25,6 @@
 // on the CPU (max |Δstd²|/k0 = 1.5e-6 on the config-2 workload).
 #include <hip/hip_runtime.h>
 
-#include "cdx_ab.h"
-
 #include <algorithm>
 #include <cmath>
 #include <cstdlib>
@@ -865,14 +863,6 @@ int screen_var_launch(const cdx_gpis& g, const double* X, int64_t M, double* var
 
 size_t screen_select_ws_bytes(const cdx_gpis& g, int64_t Ms) { return screen_ws_bytes(g, Ms); }
 
-int screen_audit_rows() {
-  static const int n = [] {
-    const char* e = cdx::ab_env("CDX_SCREEN_AUDIT");
-    return e ? std::max(0, atoi(e)) : 64;
-  }();
-  return n;
-}
-
 int screen_select_launch(const cdx_gpis& g, const double* X, int64_t G, int T, void* ws, double* sv2, double* std_,
                          int* vpos, int* rows, unsigned short* keep, unsigned* zkey, int* stats, hipStream_t s,
                          int (*after_screen)(void*), void* ctx) {
@@ -917,7 +907,7 @@ int screen_select_launch(const cdx_gpis& g, const double* X, int64_t G, int T, v
       break;
   }
   hipLaunchKernelGGL(screen_count_kernel, dim3((unsigned)ncb), dim3(CB_GROUPS), 0, s, G, T, nsel, (const int*)hist, keep,
-                     (const unsigned*)zkey, bcount, screen_audit_rows());
+                     (const unsigned*)zkey, bcount, SCREEN_AUDIT_ROWS);
   hipLaunchKernelGGL(screen_place_kernel, dim3((unsigned)ncb), dim3(CB_GROUPS), 0, s, G, T, (const unsigned short*)keep,
                      (const int*)bcount, vpos, rows, stats);
   return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;

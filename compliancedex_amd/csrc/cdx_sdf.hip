@@ -35,7 +35,6 @@
 // The choice is made on the device (no host sync).
 #include <hip/hip_runtime.h>
 
-#include "cdx_ab.h"
 #include <hipcub/hipcub.hpp>
 
 #include <algorithm>
@@ -957,23 +956,6 @@ __global__ __launch_bounds__(256) void sdf_backward_kernel(const float* __restri
   for (int c = 0; c < 3; ++c) gp[3 * i + c] = (points[3 * i + c] - clst[3 * i + c]) * g;
 }
 
-bool sched_on() {  // CDX_SDF_SCHED=0: a batch ignores its schedule (point order, the A/B base)
-  static const bool on = [] {
-    const char* e = cdx::ab_env("CDX_SDF_SCHED");
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
-int sdf_mode() {  // CDX_SDF_MODE=exact forces the brute-force kernel (benchmarks, A/B tests)
-  static const int m = [] {
-    const char* e = cdx::ab_env("CDX_SDF_MODE");
-    return (e && e[0] == 'e') ? 1 : 0;
-  }();
-  return m;
-}
-
-
 // (the mesh buffer's layout: cdx_sdf_mesh.h)
 // Records, slabs and nodes of the faces in `order` (device int[F]).
 void mesh_fill(const float* faces, int64_t F, const int* order, char* mesh, hipStream_t s) {
@@ -1178,12 +1160,6 @@ int cdx_sdf_forward(const float* points, int64_t P, const float* faces, int64_t 
   if (P == 0) return CDX_OK;
   if (!sdf_args_ok(P, points, faces, F, sqdist, sign, normals, clst)) return CDX_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (sdf_mode() == 1) {
-    hipLaunchKernelGGL(sdf_exact_kernel, dim3((unsigned)((P + SDF_BLOCK - 1) / SDF_BLOCK)), dim3(SDF_BLOCK), 0, s,
-                       points, P, faces, F, (const unsigned*)nullptr, sqdist, sign, normals, clst, face_idx,
-                       (int)g_sdf_count);
-    return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;
-  }
   char* mesh = nullptr;
   if (hipMallocAsync(reinterpret_cast<void**>(&mesh), mesh_bytes(F), s) != hipSuccess) return CDX_ELAUNCH;
   int rc = mesh_build_morton(faces, F, mesh, s);
@@ -1224,7 +1200,6 @@ int cdx_sdf_query(const void* mesh, const float* faces, int64_t F, const float* 
   if (P == 0) return CDX_OK;
   if (!sdf_args_ok(P, points, faces, F, sqdist, sign, normals, clst)) return CDX_EINVAL;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (sdf_mode() == 1) return cdx_sdf_forward(points, P, faces, F, sqdist, sign, normals, clst, face_idx, stream);
   return mesh_query_ws(static_cast<const char*>(mesh), faces, F, points, P, sqdist, sign, normals, clst, face_idx,
                        workspace, workspace_bytes, flags, s);
 }
@@ -1294,15 +1269,7 @@ int cdx_sdf_query_batch(int32_t n, const cdx_sdf_batch_query* qs, void* schedule
   b.n = m;
   b.count = (int)g_sdf_count;
   hipStream_t s = reinterpret_cast<hipStream_t>(stream);
-  if (sdf_mode() == 1) {  // (the exact-path debug mode: one call per query)
-    for (int i = 0; i < n; ++i) {
-      const cdx_sdf_batch_query& d = qs[i];
-      const int rc = cdx_sdf_forward(d.points, d.P, d.faces, d.F, d.sqdist, d.sign, d.normals, d.clst, d.face_idx, stream);
-      if (rc) return rc;
-    }
-    return CDX_OK;
-  }
-  if (schedule && sched_on()) {
+  if (schedule) {
     if (schedule_bytes < (size_t)(SDF_SCHED_HDR + 2 * (size_t)groups) * sizeof(unsigned)) return CDX_EINVAL;
     b.sched = static_cast<unsigned*>(schedule);
     b.cap = groups;

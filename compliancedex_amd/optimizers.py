@@ -307,7 +307,7 @@ class _FusedLoop(_LoopState):
         f32 = dict(dtype=torch.float32, device=dev)
         self.mesh, self.mesh_def = PreparedMesh(faces), PreparedMesh(faces_deflate)
         self.ws_tips, self.ws_tgt = QueryWorkspace(), QueryWorkspace()
-        # the batched launch's schedule (heaviest point groups of the last iteration first; CDX_SDF_SCHED=0: none)
+        # the batched launch's schedule (heaviest point groups of the last iteration first)
         self.sched = BatchSchedule()
         self.iteration = 0
         # iterations per point sort: 16 (A/B with the batched launch's schedule, profiles/r05ba_config4_resort_sched_ab.jsonl:

@@ -463,10 +463,8 @@ size_t cdx_closure_workspace(const cdx_problem* p, int64_t E);
  *   gradients of Σ total_loss: g_q [E*n_dofs], g_comp [E*n_tips], g_target [E*n_tips*3],
  *   g_palm_pos [E*3], g_palm_ori [E*3]; flip [n_levels*E] int32 Kabsch det<0 mask (nullable).
  * All work is ordered on `stream`; a screened call also runs the GPIS mean on a per-device side
- * stream forked from and joined back into `stream` by events (CDX_FORK_MEAN=0 disables it; 1–4
- * choose the fork point, CDX_SIDE_PRIO=-1/1 creates the side stream at the lowest / highest
- * priority — A/B switches, read once per process), so concurrent calls from several host threads
- * on one device are not supported. */
+ * stream forked from and joined back into `stream` by events, so concurrent calls from several
+ * host threads on one device are not supported. */
 int cdx_closure(const cdx_problem* p, int64_t E, const double* q, const double* comp,
                 const double* target, const double* palm_pos, const double* palm_ori,
                 const double* kabsch_noise, uint64_t seed, void* workspace,
@@ -483,8 +481,8 @@ int cdx_closure_screen_stats(const cdx_problem* p, int64_t E, const void* worksp
 /* The screened closure's verification record.  Every screened closure runs the exact fp64 pass for
  * each group's leader, every fingertip the selection keeps, and an AUDIT of the fingertips it discards
  * nearest the keep threshold — smallest normalised gap z = (lo − a_f)/Δ_f, lo = max_g (a_g − Δ_g), the
- * margins by which the row's estimate sits below its group's keep floor (CDX_SCREEN_AUDIT rows, default
- * 64: the lowest 1/8-octave z bins within that budget) — and checks each of those estimates against its
+ * margins by which the row's estimate sits below its group's keep floor (64 rows:
+ * the lowest 1/8-octave z bins within that budget) — and checks each of those estimates against its
  * margin Δ_f.  The maximum of each group is taken over exact values.  If any check fails (a kept or
  * audited estimate off by more than Δ_f, an audited row that is its group's exact maximum, a maximum on
  * a row the exact pass did not run) the same closure REPAIRS itself: every all-tip row runs the exact
@@ -531,10 +529,6 @@ int cdx_closure_screen_reset(const cdx_problem* p, int64_t E, void* workspace, c
  * screen / selection and the side-stream fork, 2: after the exact pass, 3: after the ∇std pass; 0 clears),
  * through the error path of a failed launch — which joins the side stream before returning. */
 int cdx_debug_fail_next_closure(int32_t stage);
-/* 1 if this library was built with -DCDX_AB_SWITCHES (an A/B build: it reads the CDX_* run-time switches of
- * csrc/cdx_ab.h, including CDX_SCREEN_AUDIT / CDX_SCREEN_REPAIR / CDX_NO_SCREEN), 0 for the shipped build, which
- * ignores them: every screened closure audits its discarded rows and repairs itself on a failed check. */
-int cdx_ab_switches(void);
 
 /* ------------------------------------------------------------ survivor exchange ------
  * Multi-GPU record pack (no reference counterpart — the reference is single-GPU):

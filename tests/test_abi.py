@@ -160,21 +160,29 @@ def test_library_exports_every_declared_symbol():
     assert lib.cdx_version().startswith(b"compliancedex_amd")
 
 
-def test_shipped_library_ignores_ab_switches():
-    """the shipped libcdx.so is built without -DCDX_AB_SWITCHES, so CDX_SCREEN_AUDIT / CDX_SCREEN_REPAIR /
-    CDX_NO_SCREEN and the schedule switches in a user's environment are ignored (csrc/cdx_ab.h); the default build's
-    -D list carries no A/B switch.  (tests/test_screen.py::test_env_switches_cannot_disable_the_repair runs the
-    closure with them set on the GPU.)"""
-    from compliancedex_amd import _native
-    from compliancedex_amd.build import DEFAULT_DEFINES
-    assert _native.load().cdx_ab_switches() == 0
-    assert "CDX_AB_SWITCHES" not in DEFAULT_DEFINES
+def test_native_sources_read_only_the_two_oracle_switches():
+    """No variable in a user's environment changes what the native library computes or how it schedules it: over
+    every file of csrc/, the only reads of the environment are the getenv calls for CDX_KABSCH_AHEAD and CDX_VAR_LATE
+    (the two bit-parity oracle switches of tests/test_screen.py), each naming its variable by a string literal, and
+    no other function whose name holds "env" (a gated or secure reader, a wrapper, setenv / putenv) is defined or
+    called.  (tests/test_screen.py::test_env_switches_cannot_disable_the_repair runs the closure with the retired
+    screen switches set on the GPU.)"""
+    from compliancedex_amd.build import CSRC
+    read, calls = set(), 0
+    for name in sorted(os.listdir(CSRC)):
+        text = open(os.path.join(CSRC, name), encoding="utf-8").read()
+        assert set(re.findall(r"\b(\w*env\w*)\s*\(", text, re.I)) <= {"getenv"}, name
+        assert "environ" not in text, name
+        calls += len(re.findall(r"\bgetenv\b", text))
+        read |= set(re.findall(r'\bgetenv\s*\(\s*"([^"]*)"\s*\)', text))
+    assert read == {"CDX_KABSCH_AHEAD", "CDX_VAR_LATE"}
+    assert calls == 2  # (no call with a computed name, no second reader of either, no mention elsewhere)
 
 
 def test_build_macros_are_the_documented_ones():
     """The product is a plain compile of csrc/ (no -D), and the only CDX_* macros a preprocessor conditional there
-    tests are the ones DESIGN.md §2a lists under "Build macros": CDX_AB_SWITCHES and the timing-only diagnostic
-    builds.  A measured-and-lost variant kept behind a new macro fails here."""
+    tests are the ones DESIGN.md §2a lists under "Build macros": the timing-only diagnostic builds.  A
+    measured-and-lost variant kept behind a new macro fails here."""
     from compliancedex_amd.build import CSRC, DEFAULT_DEFINES
     assert tuple(DEFAULT_DEFINES) == ()
     used = set()
@@ -188,7 +196,6 @@ def test_build_macros_are_the_documented_ones():
     for row in section.splitlines():
         if row.startswith("| `CDX_"):
             documented |= set(re.findall(r"`(CDX_[A-Z0-9_]+)`", row.split("|")[1]))
-    assert "CDX_AB_SWITCHES" in documented
     assert used == documented, (sorted(used - documented), sorted(documented - used))
 
 

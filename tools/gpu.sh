@@ -15,7 +15,7 @@
 #   c4trace          rocprofv3 --kernel-trace --stats over tools/c4_kin.py (prof_c4_TAG/)
 #   sdfpmc           tools/pmc_sdf.sh: PMC passes over tools/sdf_child.py (the config-4 queries), sdf_tree_kernel
 #   ab=SPEC,SPEC,..  interleaved bench A/B (R rounds, env R=3): SPEC = lib name ("base" = libcdx.so) with
-#                    optional +VAR=VAL settings, e.g. ab=base,base+CDX_SCREEN_REPAIR=0
+#                    optional +VAR=VAL settings, e.g. ab=base,base+CDX_VAR_LATE=0
 set -u
 ROOT=${GRAFT_REPO_ROOT:-$(pwd)}
 cd "$ROOT"
