@@ -57,6 +57,7 @@ from .sampling import (SurfaceSampler, sample_points_poisson_disk, sample_points
                        surface_sampler)
 from .robot_model import DifferentiableRobotModel  # noqa: F401
 from .ik import IKPoseResult, IKResult, solve_ik, solve_ik_pose  # noqa: F401
+from .dynamics import HoldingReport, holding_torques, impedance_torques  # noqa: F401
 from .wrench import (MinWrenchResult, compute_margin, min_wrench, minimum_wrench_reward,  # noqa: F401
                      solve_minimum_wrench)
 from .hand import HandSpheres, HandTerm, hand_collision, penetration_report, spheres_from_urdf  # noqa: F401

@@ -24,6 +24,9 @@ _SIGS = {
     "cdxh_fk_jacobian": (C.c_int, [_CHAIN, _P, _I64, _P, _P]),
     "cdxh_ik_solve": (C.c_int, [_CHAIN, C.POINTER(CdxIkParams), _I64, _P, _I32] + [_P] * 8),
     "cdxh_ik_solve_pose": (C.c_int, [_CHAIN, C.POINTER(CdxIkParams), _I64, _P, _I32] + [_P] * 11),
+    "cdxh_dyn_inverse": (C.c_int, [_CHAIN, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P]),
+    "cdxh_dyn_inertia": (C.c_int, [_CHAIN, _P, _I64, _P, _I32, _P]),
+    "cdxh_dyn_forward": (C.c_int, [_CHAIN, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P]),
     "cdxh_min_wrench": (C.c_int, [C.POINTER(CdxWrenchParams), _I64] + [_P] * 10),
     "cdxh_hand_prepare": (C.c_int, [_I32, _I32, _P, _P, _P, _I32, _P, _P, _HAND]),
     "cdxh_hand_spheres": (C.c_int, [_CHAIN, _HAND, _I64] + [_P] * 5),

@@ -56,6 +56,11 @@ class CdxIkParams(C.Structure):
                 ("mu_max", C.c_double), ("nu", C.c_double), ("max_iters", C.c_int32), ("_pad", C.c_int32)]
 
 
+class CdxDyn(C.Structure):
+    _fields_ = [("mass", C.c_double * MAX_BODIES), ("mcom", (C.c_double * 3) * MAX_BODIES),
+                ("inertia", (C.c_double * 6) * MAX_BODIES), ("damping", C.c_double * MAX_DOFS)]
+
+
 class CdxWrenchParams(C.Structure):
     _fields_ = [("n_tips", C.c_int32), ("max_iters", C.c_int32), ("check_every", C.c_int32), ("_pad", C.c_int32),
                 ("mu", C.c_double), ("min_force", C.c_double), ("reg", C.c_double), ("rho", C.c_double),
@@ -232,6 +237,11 @@ _SIGS = {
     "cdx_ik_solve_pose": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxIkParams), _I64, _P, C.c_int32, _P, _P, _P,
                                     C.POINTER(C.c_double)] + [_P] * 9),
     "cdx_ik_pose_rows_per_block": (C.c_int32, [C.c_int32, C.c_int32]),
+    "cdx_dyn_inverse": (C.c_int, [C.POINTER(CdxChain), _P, _I64, _P, _P, _P] + [C.c_int32] * 3 + [_P, C.c_int32, _P, _P, _P]),
+    "cdx_dyn_inertia": (C.c_int, [C.POINTER(CdxChain), _P, _I64, _P, C.c_int32, _P, _P]),
+    "cdx_dyn_forward": (C.c_int, [C.POINTER(CdxChain), _P, _I64, _P, _P, _P] + [C.c_int32] * 3 + [_P, C.c_int32, _P, _P]),
+    "cdx_dyn_rows_per_block": (C.c_int32, [C.c_int32] * 3),
+    "cdx_dyn_abi_size": (C.c_size_t, []),
     "cdx_min_wrench": (C.c_int, [C.POINTER(CdxWrenchParams), _I64] + [_P] * 11),
     "cdx_wrench_rows_per_block": (C.c_int32, [C.c_int32]),
     "cdx_wrench_abi_size": (C.c_size_t, []),
@@ -313,6 +323,7 @@ _ABI_SIZES = [
                        CdxScreenReport, CdxKinParams, CdxKinOpt, CdxKinOptBuffers, CdxSdfBatchQuery], "core"),
     ("cdx_gpis_mode_abi_sizes", [CdxGpisModeParams, CdxGpisModeOpt, CdxGpisModeBuffers], "GPIS mode"),
     ("cdx_ik_abi_size", [CdxIkParams], "IK"),
+    ("cdx_dyn_abi_size", [CdxDyn], "dynamics"),
     ("cdx_wrench_abi_size", [CdxWrenchParams], "wrench"),
     ("cdx_hand_abi_sizes", [CdxHand, CdxHandParams], "hand"),
 ]

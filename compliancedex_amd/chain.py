@@ -5,7 +5,7 @@ import ctypes
 
 import torch
 
-from ._native import MAX_BODIES, MAX_DEPTH, MAX_DOFS, MAX_TIPS, CdxChain
+from ._native import MAX_BODIES, MAX_DEPTH, MAX_DOFS, MAX_TIPS, CdxChain, CdxDyn
 
 
 def _axis_rot_f32(axis, angle):
@@ -78,8 +78,47 @@ class Chain:
     def config(self):
         return self.desc.get("config", {})
 
-    def descriptor(self, link_names, offsets=None):
-        """cdx_chain with the requested tips (and optional per-tip offsets)."""
+    @property
+    def no_inertial(self):
+        """Links whose URDF has no ``<inertial>``: they carry the reference's stand-in (mass 1, identity inertia)."""
+        return list(self.desc.get("no_inertial", []))
+
+    @property
+    def has_dynamics(self):
+        return all("mass" in b and "inertia" in b and "com" in b for b in self.bodies)
+
+    def dynamics_descriptor(self):
+        """cdx_dyn: per body mass, mass·com and the inertia about the body frame's origin I + m·[c]ₓ[c]ₓᵀ, per DOF the
+        damping.  Every URDF value is rounded to float32 first, as the reference reads it (urdf_utils.py:85-113); the
+        products are float64."""
+        if not self.has_dynamics:
+            raise ValueError("this chain carries no inertial data (mass / com / inertia per body): load it from a URDF, "
+                             "or regenerate its JSON with tools/import_assets.py")
+        f32 = lambda v: float(torch.tensor(float(v), dtype=torch.float32))  # noqa: E731
+        d = CdxDyn()
+        for i, b in enumerate(self.bodies):
+            m, c = f32(b["mass"]), [f32(v) for v in b["com"]]
+            xx, xy, xz, yy, yz, zz = (f32(v) for v in b["inertia"])
+            d.mass[i] = m
+            for k in range(3):
+                d.mcom[i][k] = m * c[k]
+            # [c]ₓ[c]ₓᵀ = |c|²·1 − c·cᵀ
+            cc = c[0] * c[0] + c[1] * c[1] + c[2] * c[2]
+            full = (xx + m * (cc - c[0] * c[0]), xy - m * (c[0] * c[1]), xz - m * (c[0] * c[2]),
+                    yy + m * (cc - c[1] * c[1]), yz - m * (c[1] * c[2]), zz + m * (cc - c[2] * c[2]))
+            for k in range(6):
+                d.inertia[i][k] = full[k]
+            if self.dof[i] >= 0:
+                d.damping[self.dof[i]] = f32(b.get("damping", 0.0))
+        return d
+
+    def effort_limits(self):
+        """The URDF's ``limit effort`` per DOF (N·m), in DOF order."""
+        return [float(b.get("effort", 0.0)) for i, b in enumerate(self.bodies) if self.dof[i] >= 0]
+
+    def descriptor(self, link_names, offsets=None, check_depth=True):
+        """cdx_chain with the requested tips (and optional per-tip offsets).  ``check_depth=False``: for the dynamics
+        entries, which walk bodies, not levels, and take a tip at any depth."""
         if len(link_names) > MAX_TIPS:
             raise ValueError(f"at most {MAX_TIPS} tips")
         if offsets is not None and len(offsets) != len(link_names):
@@ -95,7 +134,7 @@ class Chain:
             depth, b = 0, self.index[name]
             while b > 0:
                 depth, b = depth + 1, self.bodies[b]["parent"]
-            if depth > MAX_DEPTH:
+            if check_depth and depth > MAX_DEPTH:
                 raise ValueError(f"tip {name!r} lies {depth} bodies below the root; the FK walks at most {MAX_DEPTH} "
                                  f"(CDX_MAX_DEPTH)")
             if offsets is not None:

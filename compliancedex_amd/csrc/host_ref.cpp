@@ -13,6 +13,7 @@
 
 #include "cdx_collision.h"
 #include "cdx_cost.h"
+#include "cdx_dyn.h"
 #include "cdx_field.h"
 #include "cdx_fps.h"
 #include "cdx_gpis_mode.h"
@@ -434,6 +435,71 @@ int cdxh_ik_solve_pose(const cdx_chain* c, const cdx_ik_params* params, int64_t 
         ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : m.q[d];
     }
     status[e] = st;
+  }
+  return CDX_OK;
+}
+
+// Rigid-body dynamics (cdx_dyn.h) row by row, with the device entries' argument checks; every pointer is host memory.
+int cdxh_dyn_inverse(const cdx_chain* c, const cdx_dyn* dyn, int64_t B, const void* q, const void* qd, const void* qdd,
+                     int32_t dtype, int32_t include_gravity, int32_t use_damping, const double* gravity,
+                     int32_t gravity_per_row, const double* tip_forces, void* tau) {
+  const int rc = cdx::dyn_chain_code(c, dyn);
+  if (rc) return rc;
+  if (B < 0 || (dtype != CDX_DTYPE_F32 && dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
+  if (B == 0) return CDX_OK;
+  if (!q || !tau) return CDX_ECHAIN;
+  const int n = c->n_bodies, D = c->n_dofs, T = c->n_tips, f64 = dtype == CDX_DTYPE_F64;
+  std::vector<double> mem((cdx::dyn_mem_bytes(n, D, 0) + 7) / 8);
+  const cdx::DynMem m = cdx::dyn_mem_at(mem.data(), n, D, 0, 0, 1);
+  const size_t w = f64 ? 8 : 4;
+  for (int64_t e = 0; e < B; ++e) {
+    double g[3];
+    cdx::dyn_gravity(include_gravity != 0, gravity ? gravity + (gravity_per_row ? e * 3 : 0) : nullptr, g);
+    const size_t off = (size_t)e * D * w;
+    cdx::dyn_inverse_row(*c, *dyn, m, cdx::DynVec{(const char*)q + off, f64},
+                         cdx::DynVec{qd ? (const char*)qd + off : nullptr, f64},
+                         cdx::DynVec{qdd ? (const char*)qdd + off : nullptr, f64}, g, use_damping != 0,
+                         tip_forces && T > 0 ? tip_forces + e * T * 3 : nullptr, cdx::DynOut{(char*)tau + off, f64});
+  }
+  return CDX_OK;
+}
+
+int cdxh_dyn_inertia(const cdx_chain* c, const cdx_dyn* dyn, int64_t B, const void* q, int32_t dtype, void* H) {
+  const int rc = cdx::dyn_chain_code(c, dyn);
+  if (rc) return rc;
+  if (B < 0 || (dtype != CDX_DTYPE_F32 && dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
+  if (B == 0) return CDX_OK;
+  if (!q || !H) return CDX_ECHAIN;
+  const int n = c->n_bodies, D = c->n_dofs, f64 = dtype == CDX_DTYPE_F64;
+  std::vector<double> mem((cdx::dyn_mem_bytes(n, D, 0) + 7) / 8);
+  const cdx::DynMem m = cdx::dyn_mem_at(mem.data(), n, D, 0, 0, 1);
+  const size_t w = f64 ? 8 : 4;
+  for (int64_t e = 0; e < B; ++e)
+    cdx::dyn_inertia_row(*c, *dyn, m, cdx::DynVec{(const char*)q + (size_t)e * D * w, f64},
+                         cdx::DynOut{(char*)H + (size_t)e * D * D * w, f64});
+  return CDX_OK;
+}
+
+int cdxh_dyn_forward(const cdx_chain* c, const cdx_dyn* dyn, int64_t B, const void* q, const void* qd, const void* f,
+                     int32_t dtype, int32_t include_gravity, int32_t use_damping, const double* gravity,
+                     int32_t gravity_per_row, void* qdd) {
+  const int rc = cdx::dyn_chain_code(c, dyn);
+  if (rc) return rc;
+  if (B < 0 || (dtype != CDX_DTYPE_F32 && dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
+  if (cdx::dyn_has_dead_joint(*c)) return CDX_EINVAL;
+  if (B == 0) return CDX_OK;
+  if (!q || !f || !qdd) return CDX_ECHAIN;
+  const int n = c->n_bodies, D = c->n_dofs, f64 = dtype == CDX_DTYPE_F64;
+  std::vector<double> mem((cdx::dyn_mem_bytes(n, D, 1) + 7) / 8);
+  const cdx::DynMem m = cdx::dyn_mem_at(mem.data(), n, D, 1, 0, 1);
+  const size_t w = f64 ? 8 : 4;
+  for (int64_t e = 0; e < B; ++e) {
+    double g[3];
+    cdx::dyn_gravity(include_gravity != 0, gravity ? gravity + (gravity_per_row ? e * 3 : 0) : nullptr, g);
+    const size_t off = (size_t)e * D * w;
+    cdx::dyn_forward_row(*c, *dyn, m, cdx::DynVec{(const char*)q + off, f64},
+                         cdx::DynVec{qd ? (const char*)qd + off : nullptr, f64}, cdx::DynVec{(const char*)f + off, f64}, g,
+                         use_damping != 0, cdx::DynOut{(char*)qdd + off, f64});
   }
   return CDX_OK;
 }

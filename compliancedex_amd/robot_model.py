@@ -1,9 +1,12 @@
 """Drop-in for ``DifferentiableRobotModel`` FK (thirdparty/differentiable-robot-model/
 differentiable_robot_model/robot_model.py) on MI355X: ``compute_forward_kinematics``
 (:224-264) with the reference's float32 arithmetic and gradient (cdx_fk_forward /
-cdx_fk_backward), ``compute_endeffector_jacobian`` (:643-683, cdx_fk_jacobian) and, beyond the
-reference, batched inverse kinematics (cdx_ik_solve, ik.py).  Dynamics (ID/FD/ABA, :266-806) are
-not on the path.
+cdx_fk_backward), ``compute_endeffector_jacobian`` (:643-683, cdx_fk_jacobian), beyond the
+reference batched inverse kinematics (cdx_ik_solve, ik.py), and the dynamics block (:266-640):
+``compute_inverse_dynamics``, ``compute_non_linear_effects``, ``compute_lagrangian_inertia_matrix``,
+``compute_forward_dynamics`` on the device (cdx_dyn_inverse / cdx_dyn_inertia / cdx_dyn_forward, csrc/cdx_dyn.h), with
+``gravity_compensation`` and ``get_joint_effort_limits`` beside them.  The dynamics carry no autograd (the
+reference's learnable-parameter variants, :686-806, are not provided).
 """
 from __future__ import annotations
 
@@ -55,6 +58,7 @@ class DifferentiableRobotModel(torch.nn.Module):
         self._n_dofs = self.chain.n_dofs
         self._name_to_idx_map = dict(self.chain.index)
         self._desc_cache = {}
+        self._dyn_cache = {}
 
     def _descriptor(self, link_names, offsets):
         key = (tuple(link_names), None if offsets is None else tuple(tuple(float(v) for v in o) for o in offsets))
@@ -65,6 +69,121 @@ class DifferentiableRobotModel(torch.nn.Module):
 
     def get_joint_limits(self):
         return [dict(lower=b["lower"], upper=b["upper"]) for i, b in enumerate(self.chain.bodies) if self.chain.dof[i] >= 0]
+
+    def get_joint_effort_limits(self):
+        """The URDF's ``limit effort`` per joint (N·m), in DOF order."""
+        return self.chain.effort_limits()
+
+    # ---------------------------------------------------------------- dynamics (no autograd through any of them)
+    def _dyn(self, device):
+        """(host cdx_dyn, its device copy): the kernels read the constants from device memory (include/cdx.h)."""
+        key = str(device)
+        hit = self._dyn_cache.get(key)
+        if hit is None:
+            host = self.chain.dynamics_descriptor()
+            dev = torch.frombuffer(bytearray(bytes(host)), dtype=torch.uint8).to(device)
+            hit = self._dyn_cache[key] = (host, dev)
+        return hit
+
+    def _dyn_descriptor(self, link_names, offsets):
+        if not link_names:
+            link_names, offsets = [], None
+        key = ("dyn", tuple(link_names), None if offsets is None else tuple(tuple(float(v) for v in o) for o in offsets))
+        d = self._desc_cache.get(key)
+        if d is None:
+            d = self._desc_cache[key] = self.chain.descriptor(list(link_names), offsets, check_depth=False)
+        return d
+
+    def _dyn_rows(self, q, *others):
+        """q and its companions as detached contiguous [B, D] tensors of q's dtype (float32 or float64)."""
+        self._check_q(q)
+        dtype = q.dtype if q.dtype in (torch.float32, torch.float64) else torch.float64
+        out = []
+        for t in (q,) + others:
+            if t is None:
+                out.append(None)
+                continue
+            t = torch.as_tensor(t, device=q.device).detach().to(dtype)
+            t = t.unsqueeze(0) if t.ndim == 1 else t
+            if t.ndim != 2 or t.shape[1] != self._n_dofs or t.shape[0] != (out[0].shape[0] if out else t.shape[0]):
+                raise AssertionError(f"expected [batch_size, {self._n_dofs}] like q, got {tuple(t.shape)}")
+            out.append(t.contiguous())
+        return out, (N.DTYPE_F64 if dtype == torch.float64 else N.DTYPE_F32), q.ndim == 1
+
+    @staticmethod
+    def _gravity_arg(gravity, B, device):
+        """(tensor | None, per_row) of a gravity [3] or [B, 3] in the base frame."""
+        if gravity is None:
+            return None, 0
+        g = torch.as_tensor(gravity, dtype=torch.float64, device=device).detach()
+        if g.shape not in ((3,), (B, 3)):
+            raise ValueError(f"gravity must have shape (3,) or ({B}, 3), got {tuple(g.shape)}")
+        return g.contiguous(), int(g.ndim == 2)
+
+    def compute_inverse_dynamics(self, q, qd, qdd_des, include_gravity=True, use_damping=True, *, gravity=None,
+                                 tip_forces=None, link_names=None, offsets=None):
+        """→ tau [B, D] of q's dtype: the joint torques that give ``qdd_des`` at (q, qd) (robot_model.py:322-391;
+        recursive Newton–Euler in one launch, cdx_dyn_inverse).  ``use_damping`` adds damping·qd.  Beyond the
+        reference: ``gravity`` [3] or [B, 3], the gravity vector in the base frame (None: (0, 0, −9.81)), and
+        ``tip_forces`` [B, T, 3], external forces in the base frame acting at ``link_names`` (+ ``offsets``, points in
+        the links' frames) — tau is then what the joints must supply, τ − Σ JᵀF.  ``qd`` / ``qdd_des`` None: zero.
+        No autograd: inputs are detached."""
+        (q2, qd2, qdd2), dtype, squeeze = self._dyn_rows(q, qd, qdd_des)
+        lib = N.load()
+        B = q2.shape[0]
+        tf = None
+        if tip_forces is not None:
+            if not link_names:
+                raise ValueError("tip_forces needs link_names")
+            tf = torch.as_tensor(tip_forces, dtype=torch.float64, device=q.device).detach()
+            if tf.shape != (B, len(link_names), 3):
+                raise ValueError(f"tip_forces must have shape {(B, len(link_names), 3)}, got {tuple(tf.shape)}")
+            tf = tf.contiguous()
+        g, per_row = self._gravity_arg(gravity, B, q.device)
+        tau = torch.empty_like(q2)
+        N.check(lib.cdx_dyn_inverse(self._dyn_descriptor(link_names if tf is not None else None, offsets),
+                                    N.ptr(self._dyn(q.device)[1]), B, N.ptr(q2), N.ptr(qd2), N.ptr(qdd2), dtype,
+                                    int(bool(include_gravity)), int(bool(use_damping)), N.ptr(g), per_row, N.ptr(tf),
+                                    N.ptr(tau), N.stream_ptr(q.device)), "cdx_dyn_inverse")
+        return tau[0] if squeeze else tau
+
+    def compute_non_linear_effects(self, q, qd, include_gravity=True, use_damping=True):
+        """→ [B, D]: Coriolis, centrifugal, gravity and damping torques — the inverse dynamics at zero acceleration
+        (robot_model.py:394-416).  No autograd."""
+        return self.compute_inverse_dynamics(q, qd, None, include_gravity, use_damping)
+
+    def gravity_compensation(self, q, gravity=None):
+        """→ [B, D]: the torques that hold the chain still at q against ``gravity`` (base frame; None: (0, 0, −9.81)).
+        No autograd."""
+        return self.compute_inverse_dynamics(q, None, None, True, False, gravity=gravity)
+
+    def compute_lagrangian_inertia_matrix(self, q, include_gravity=True, use_damping=True):
+        """→ H [B, D, D] of q's dtype, symmetric bit for bit (robot_model.py:419-466; cdx_dyn_inertia).  The two flags
+        cancel in the reference (H is a difference of two passes that share them) and are accepted.  No autograd."""
+        (q2,), dtype, squeeze = self._dyn_rows(q)
+        lib = N.load()
+        B, D = q2.shape
+        H = torch.empty(B, D, D, dtype=q2.dtype, device=q.device)
+        N.check(lib.cdx_dyn_inertia(self._dyn_descriptor(None, None), N.ptr(self._dyn(q.device)[1]), B, N.ptr(q2), dtype,
+                                    N.ptr(H), N.stream_ptr(q.device)), "cdx_dyn_inertia")
+        return H[0] if squeeze else H
+
+    def compute_forward_dynamics(self, q, qd, f, include_gravity=True, use_damping=False, *, gravity=None):
+        """→ qdd [B, D] of q's dtype: the accelerations the torques ``f`` cause at (q, qd) (robot_model.py:504-640;
+        cdx_dyn_forward solves H·qdd = f − damping·qd − nle, what the reference's articulated-body sweep solves).
+        ``use_damping`` takes damping·qd from a copy: the caller's ``f`` is not written (the reference edits it in
+        place, :537).  No autograd."""
+        (q2, qd2, f2), dtype, squeeze = self._dyn_rows(q, qd, f)
+        if f2 is None:
+            raise ValueError("f is required")
+        lib = N.load()
+        B = q2.shape[0]
+        g, per_row = self._gravity_arg(gravity, B, q.device)
+        qdd = torch.empty_like(q2)
+        N.check(lib.cdx_dyn_forward(self._dyn_descriptor(None, None), N.ptr(self._dyn(q.device)[1]), B, N.ptr(q2),
+                                    N.ptr(qd2), N.ptr(f2), dtype, int(bool(include_gravity)), int(bool(use_damping)),
+                                    N.ptr(g), per_row, N.ptr(qdd), N.stream_ptr(q.device)), "cdx_dyn_forward")
+        return qdd[0] if squeeze else qdd
 
     def compute_forward_kinematics(self, q: torch.Tensor, link_names: list, recursive: bool = False, offsets=None):
         """→ (pos [B, 3L], quat [B, 4L] xyzw), float32 (robot_model.py:224-264).

@@ -380,6 +380,50 @@ int cdx_ik_solve_pose(const cdx_chain* chain, const cdx_ik_params* params, int64
 /* Rows per workgroup of cdx_ik_solve_pose for a chain of these sizes (for tests of its seams). */
 int32_t cdx_ik_pose_rows_per_block(int32_t n_tips, int32_t n_dofs);
 
+/* Rigid-body dynamics of a chain (compute_inverse_dynamics, compute_lagrangian_inertia_matrix and
+ * compute_forward_dynamics, robot_model.py:266-640; the rule is csrc/cdx_dyn.h): recursive Newton–Euler in body
+ * coordinates, B independent rows, one launch each, per-row state in LDS.  The inertial constants travel in a descriptor
+ * of their own, next to the chain (bodies and DOFs in the chain's order):
+ *   mass; mcom = mass·(centre of mass, body frame); inertia = xx, xy, xz, yy, yz, zz of I + mass·[c]ₓ[c]ₓᵀ, the rotational
+ *   inertia about the body frame's ORIGIN (spatial_vector_algebra.py:321-372); damping per DOF (N·m·s/rad). */
+typedef struct {
+  double mass[CDX_MAX_BODIES];
+  double mcom[CDX_MAX_BODIES][3];
+  double inertia[CDX_MAX_BODIES][6];
+  double damping[CDX_MAX_DOFS];
+} cdx_dyn;
+/* Unlike the other descriptors, `dyn` is a DEVICE pointer: a copy of the struct in device memory, made once per robot
+ * by the caller and read by the kernels (chain and constants together exceed a kernel's argument block); the chain stays
+ * a host pointer.  q rounds to float32 and its sine / cosine are float32 like the FK's; everything after that is
+ * float64.  q, qd, qdd, f [B*D] and the outputs are float32 or float64 (dtype = CDX_DTYPE_*); gravity and tip_forces are
+ * float64.
+ *   gravity: the gravity vector in the BASE frame, [3] (gravity_per_row = 0) or [B*3] (1), a device array; NULL:
+ *     (0, 0, −9.81), the reference's base acceleration of +9.81 z (:360-366).  include_gravity = 0: none.
+ *   use_damping: cdx_dyn_inverse adds damping·qd to tau (:383-389); cdx_dyn_forward takes it from a copy of f (:532-537
+ *     without the reference's write into the caller's f).
+ * cdx_dyn_inverse: tau [B*D], the torques that give qdd at (q, qd); qd / qdd NULL: zero.  tip_forces [B*n_tips*3]
+ *   (nullable): external forces in the base frame acting at the chain's tips (with their offsets); tau is then what the
+ *   joints must supply, τ_RNEA − Σ_t J_tᵀ·F_t, the forces entering the backward sweep (no Jacobian is formed).
+ * cdx_dyn_inertia: H [B*D*D], symmetric bit for bit (one triangle computed, then mirrored).
+ * cdx_dyn_forward: qdd [B*D] = H⁻¹·(f − damping·qd − nle), H factored by Cholesky in LDS; qd NULL: zero.
+ * A moving joint whose sign is 0 (it never moves): its tau is damping·qd alone, its row and column of H are 0, and
+ *   cdx_dyn_forward returns CDX_EINVAL.  A chain needs no tip here, and no depth limit applies (state is per body).
+ * Return codes: NULL chain, dyn or required array → CDX_ECHAIN; sizes outside the descriptor's capacity, B < 0, an
+ *   unknown dtype → CDX_EINVAL; a malformed tree → CDX_ECHAIN; nothing is launched or written on any of them.  B = 0 is
+ *   a no-op.
+ * cdx_dyn_rows_per_block: rows per workgroup of entry 0 (inverse), 1 (inertia), 2 (forward) for a chain of these sizes
+ *   (for tests of its seams; 0 for sizes out of range);  cdx_dyn_abi_size: sizeof(cdx_dyn). */
+int cdx_dyn_inverse(const cdx_chain* chain, const cdx_dyn* dyn, int64_t B, const void* q, const void* qd,
+                    const void* qdd, int32_t dtype, int32_t include_gravity, int32_t use_damping, const double* gravity,
+                    int32_t gravity_per_row, const double* tip_forces, void* tau, cdx_stream_t stream);
+int cdx_dyn_inertia(const cdx_chain* chain, const cdx_dyn* dyn, int64_t B, const void* q, int32_t dtype, void* H,
+                    cdx_stream_t stream);
+int cdx_dyn_forward(const cdx_chain* chain, const cdx_dyn* dyn, int64_t B, const void* q, const void* qd, const void* f,
+                    int32_t dtype, int32_t include_gravity, int32_t use_damping, const double* gravity,
+                    int32_t gravity_per_row, void* qdd, cdx_stream_t stream);
+int32_t cdx_dyn_rows_per_block(int32_t n_bodies, int32_t n_dofs, int32_t entry);
+size_t cdx_dyn_abi_size(void);
+
 /* Batched minimum-wrench contact forces (what the reference asks of cvxpy in math_utils.py:6-57; the rule is
  * csrc/cdx_wrench.h): per candidate row, the forces F [T][3] inside their friction cones (n̂·F ≤ −‖F‖/sqrt(1 + mu²))
  * that press at least min_force along the normal (n̂·F ≤ −min_force) and minimise

@@ -95,6 +95,13 @@ def config3_surfaces(n=1936):
 def main():
     if sys.argv[1:] == ["config3"]:
         return config3_surfaces()
+    robots()
+    if sys.argv[1:] == ["robots"]:  # only the robot JSONs (no other packaged file is touched)
+        return
+    data_files()
+
+
+def robots():
     os.makedirs(os.path.join(PKG, "robots"), exist_ok=True)
     for robot, rel in URDFS.items():
         chain = parse_urdf(os.path.join(REF, rel))
@@ -107,6 +114,8 @@ def main():
             json.dump(chain, f, indent=1)
         print("robot", robot, len(chain["bodies"]))
 
+
+def data_files():
     gdir = os.path.join(PKG, "data", "gpis_states")
     os.makedirs(gdir, exist_ok=True)
     for obj in ["banana", "coffeebottle", "hammer", "lego", "mug", "mug2", "dummy"]:
