@@ -37,6 +37,10 @@ Drop-in operators (same names / arguments as the reference):
                                the whole hand as spheres on its links: penetration of the object, of itself and of
                                the floor for E candidates with the gradient in joint space (PyBullet in
                                verify_pregrasp.py and cuRobo's collision spheres in traj_gen.py there; parity unpinned)
+  TrajectoryOptimizer / plan_approach / ApproachPlan / trajectory_report / seed_trajectories / interpolate / retime
+                               cuRobo's MotionGen in traj_gen.py: batched CHOMP on joint-space paths from a start to
+                               the grasp against the sphere model's penetration cost, a swept clearance report and
+                               seed selection on the device; parity with cuRobo unpinned
   HandTerm                     that cost as a term of the joint-space optimisers' loss: optimize(..., hand_term=…)
 All compute runs in libcdx.so (HIP, gfx950); importing works without a GPU, calling does not.
 """
@@ -61,6 +65,8 @@ from .dynamics import HoldingReport, holding_torques, impedance_torques  # noqa:
 from .wrench import (MinWrenchResult, compute_margin, min_wrench, minimum_wrench_reward,  # noqa: F401
                      solve_minimum_wrench)
 from .hand import HandSpheres, HandTerm, hand_collision, penetration_report, spheres_from_urdf  # noqa: F401
+from .trajectory import (ApproachPlan, TrajectoryOptimizer, TrajectoryResult, interpolate, plan_approach,  # noqa: F401
+                         retime, seed_trajectories, trajectory_report)
 from .torchsdf import PreparedMesh, compute_sdf, compute_sdf_with_faces, index_vertices_by_faces  # noqa: F401
 
 __version__ = "0.1.0"

@@ -9,7 +9,7 @@ import os
 import threading
 
 from ._native import (LIB_DIR, CdxChain, CdxCollision, CdxForceEq, CdxGpisModeBuffers, CdxGpisModeOpt,
-                      CdxGpisModeParams, CdxHand, CdxHandParams, CdxIkParams, CdxProblem, CdxWrenchParams)
+                      CdxGpisModeParams, CdxHand, CdxHandParams, CdxIkParams, CdxProblem, CdxTrajParams, CdxWrenchParams)
 
 _P = C.c_void_p
 _I32 = C.c_int32
@@ -33,6 +33,9 @@ _SIGS = {
     "cdxh_hand_cost": (C.c_int, [_HAND, _HAND_PARAMS, _I64] + [_P] * 7),
     "cdxh_hand_pullback": (C.c_int, [_CHAIN, _HAND, _I64] + [_P] * 6),
     "cdxh_hand_term": (C.c_int, [_CHAIN, _HAND, _HAND_PARAMS, _I64] + [_P] * 5 + [_F64, _I32] + [_P] * 6),
+    "cdxh_traj_seed": (C.c_int, [_I64, _I32, _I32, _I32, _P, _P, _F64, _U64, _P]),
+    "cdxh_traj_step": (C.c_int, [C.POINTER(CdxTrajParams), _I64, _P, _P, _P, _I32, _P, _P, _P, _P]),
+    "cdxh_traj_gradient": (C.c_int, [C.POINTER(CdxTrajParams), _I64, _P, _P, _P]),
     "cdxh_hand_bytes": (C.c_size_t, [_I32, _I32]),
     "cdxh_hand_sincos": (None, [_P, _I64, _P, _P]),
     "cdxh_n_queries": (_I64, [C.POINTER(CdxProblem), _I64]),

@@ -82,6 +82,15 @@ class CdxHandParams(C.Structure):
                 ("_pad", C.c_int32)]
 
 
+TRAJ_MAX_T, TRAJ_LANES = 64, 32  # CDX_TRAJ_MAX_T, CDX_TRAJ_LANES
+
+
+class CdxTrajParams(C.Structure):
+    _fields_ = [("lower", C.c_double * MAX_DOFS), ("upper", C.c_double * MAX_DOFS), ("w_smooth", C.c_double),
+                ("w_col", C.c_double), ("w_lim", C.c_double), ("m_lim", C.c_double), ("step", C.c_double),
+                ("T", C.c_int32), ("n_dofs", C.c_int32)]
+
+
 class CdxProblem(C.Structure):
     _fields_ = [("chain", CdxChain), ("gpis", CdxGpis), ("n_levels", C.c_int32), ("n_query_levels", C.c_int32),
                 ("level_query", C.c_int32 * MAX_LEVELS), ("coeff", (C.c_float * MAX_TIPS) * MAX_LEVELS),
@@ -253,6 +262,9 @@ _SIGS = {
     "cdx_hand_pullback": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxHand), _I64] + [_P] * 7),
     "cdx_hand_term": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxHand), C.POINTER(CdxHandParams), _I64] + [_P] * 5 +
                       [C.c_double, C.c_int32] + [_P] * 7),
+    "cdx_traj_seed": (C.c_int, [_I64, C.c_int32, C.c_int32, C.c_int32, _P, _P, C.c_double, C.c_uint64, _P, _P]),
+    "cdx_traj_step": (C.c_int, [C.POINTER(CdxTrajParams), _I64, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    "cdx_traj_abi_sizes": (None, [C.POINTER(C.c_size_t)]),
     "cdx_force_eq_forward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
                                        _P]),
     "cdx_force_eq_backward": (C.c_int, [C.POINTER(CdxForceEq), _I64, _P, _P, _P, _P, _P, C.c_uint64, _P, _P, _P, _P,
@@ -326,6 +338,7 @@ _ABI_SIZES = [
     ("cdx_dyn_abi_size", [CdxDyn], "dynamics"),
     ("cdx_wrench_abi_size", [CdxWrenchParams], "wrench"),
     ("cdx_hand_abi_sizes", [CdxHand, CdxHandParams], "hand"),
+    ("cdx_traj_abi_sizes", [CdxTrajParams], "trajectory"),
 ]
 
 _lib = None

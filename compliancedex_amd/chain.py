@@ -116,6 +116,10 @@ class Chain:
         """The URDF's ``limit effort`` per DOF (N·m), in DOF order."""
         return [float(b.get("effort", 0.0)) for i, b in enumerate(self.bodies) if self.dof[i] >= 0]
 
+    def velocity_limits(self):
+        """The URDF's ``limit velocity`` per DOF (rad/s), in DOF order; 0 where the URDF gives none."""
+        return [float(b.get("velocity", 0.0)) for i, b in enumerate(self.bodies) if self.dof[i] >= 0]
+
     def descriptor(self, link_names, offsets=None, check_depth=True):
         """cdx_chain with the requested tips (and optional per-tip offsets).  ``check_depth=False``: for the dynamics
         entries, which walk bodies, not levels, and take a tip at any depth."""

@@ -1,6 +1,6 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
 // cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h / cdx_sample.h / cdx_knn.h /
-// cdx_wrench.h / cdx_hand.h.
+// cdx_wrench.h / cdx_hand.h / cdx_traj.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
@@ -24,6 +24,7 @@
 #include "cdx_ray.h"
 #include "cdx_sample.h"
 #include "cdx_sdf.h"
+#include "cdx_traj.h"
 #include "cdx_wrench.h"
 
 namespace {
@@ -604,6 +605,48 @@ size_t cdxh_hand_bytes(int32_t S, int32_t P) { return cdx::hand_bytes(S, P); }
 // cdx::hand_sincos on n angles.
 void cdxh_hand_sincos(const double* x, int64_t n, double* s, double* c) {
   for (int64_t i = 0; i < n; ++i) cdx::hand_sincos(x[i], s + i, c + i);
+}
+
+// The trajectory rule (cdx_traj.h) row by row, with the device entries' argument checks.
+int cdxh_traj_seed(int64_t G, int32_t seeds, int32_t T, int32_t n_dofs, const double* q_start, const double* q_goal,
+                   double amp, uint64_t seed, double* traj) {
+  const int rc = cdx::traj_seed_code(G, seeds, T, n_dofs, q_start, q_goal, amp, traj);
+  if (rc || G == 0) return rc;
+  for (int64_t row = 0; row < G * seeds; ++row) {
+    const int64_t g = row / seeds;
+    cdx::traj_seed_row(row, (int32_t)(row - g * seeds), T, n_dofs, q_start + g * n_dofs, q_goal + g * n_dofs, amp, seed,
+                       traj + row * T * n_dofs);
+  }
+  return CDX_OK;
+}
+
+int cdxh_traj_step(const cdx_traj_params* p, int64_t E, double* traj, const double* g_c, const double* cost_t,
+                   int32_t iteration, double* cost, double* best_cost, int32_t* best_iter, double* best_traj) {
+  const int rc = cdx::traj_step_code(p, E, traj, g_c, cost_t, cost, best_cost, best_iter, best_traj);
+  if (rc || E == 0) return rc;
+  cdx::TrajFactor F;
+  cdx::traj_factor(p->T - 2, &F);
+  const int64_t n = (int64_t)p->T * p->n_dofs;
+  for (int64_t e = 0; e < E; ++e)
+    cdx::traj_step_row(*p, F, traj + e * n, g_c ? g_c + e * n : nullptr, cost_t ? cost_t + e * p->T : nullptr, iteration,
+                       cost + 3 * e, best_cost + e, best_iter + e, best_traj + e * n);
+  return CDX_OK;
+}
+
+// The gradient g of cdx_traj.h alone (the step's first half): g [E*T*n_dofs], its two endpoint rows 0.
+int cdxh_traj_gradient(const cdx_traj_params* p, int64_t E, const double* traj, const double* g_c, double* g) {
+  if (cdx::traj_params_code(p) || E < 0 || !traj || !g) return CDX_EINVAL;
+  const int T = p->T, D = p->n_dofs;
+  for (int64_t e = 0; e < E; ++e) {
+    double* x = g + e * T * D;
+    for (int i = 0; i < T * D; ++i) x[i] = g_c ? g_c[e * T * D + i] : 0.0;
+    double us, ul;
+    for (int d = 0; d < D; ++d) {
+      cdx::traj_gradient_column(*p, d, traj + e * T * D, x, &us, &ul);
+      x[d] = x[(T - 1) * D + d] = 0.0;
+    }
+  }
+  return CDX_OK;
 }
 
 int64_t cdxh_n_queries(const cdx_problem* P, int64_t E) { return cdx::n_queries(*P, E); }

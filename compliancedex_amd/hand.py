@@ -182,6 +182,27 @@ class HandSpheres:
         hs.skipped = skipped
         return hs
 
+    @classmethod
+    def along_links(cls, robot, radius, **kw):
+        """Spheres of one radius along the skeleton: one at every body's origin and, on the segment from a body's origin
+        to each child's origin (length L), ceil(L / 2r) − 1 more at equal spacing, so neighbours touch or overlap.  For
+        chains whose ``<collision>`` geometry is meshes (``spheres_from_urdf`` skips those: iiwa7_allegro's arm would
+        have no volume)."""
+        desc = robot if isinstance(robot, dict) else load_robot(robot)
+        r = float(radius)
+        if not (math.isfinite(r) and r > 0.0):
+            raise ValueError(f"radius must be finite and > 0, got {radius!r}")
+        bodies = desc["bodies"]
+        spheres = {b["name"]: [((0.0, 0.0, 0.0), r)] for b in bodies}
+        for i, b in enumerate(bodies):
+            if i == 0:
+                continue
+            v = np.array([float(x) for x in b["xyz"]], np.float64)
+            k = math.ceil(float(np.linalg.norm(v)) / (2.0 * r) - 1e-9)
+            parent = bodies[b["parent"]]["name"]
+            spheres[parent] += [(tuple(float(x) for x in v * (j / k)), r) for j in range(1, k)]
+        return cls(desc, spheres, **kw)
+
     @property
     def n_spheres(self):
         return len(self.body)

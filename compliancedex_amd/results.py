@@ -137,3 +137,19 @@ def hand_pose_from_contacts(robot_model, hand_config, contact, starts=8, spread=
     info = {k: v.cpu().numpy() for k, v in info.items()}
     info["all"] = every
     return joint_angle, wrist, st, info
+
+
+def approach_for_results(robot_model, hand, q_start, results, obj, floor_z=None, exp_name=None, data_dir="data", **plan):
+    """Approach paths from ``q_start`` [D] (or [E, D]) to every stored grasp: ``results`` is ``load_results``' dict (or
+    None: loaded from ``exp_name`` / ``data_dir``); the goal of grasp e is its ``joint_angle`` row, the chain's root
+    stands at its ``wrist`` row.  → trajectory.ApproachPlan; ``plan``: options of trajectory.plan_approach."""
+    import torch
+    from .trajectory import plan_approach
+    if results is None:
+        results = load_results(exp_name, data_dir)
+    dev = hand.device
+    goal = torch.as_tensor(_np(results["joint_angle"]), dtype=torch.float64, device=dev)
+    wrist = results.get("wrist")
+    wrist = None if wrist is None else torch.as_tensor(_np(wrist), dtype=torch.float64, device=dev)
+    return plan_approach(robot_model, hand, torch.as_tensor(_np(q_start), dtype=torch.float64, device=dev), goal, obj,
+                         palm_pose=wrist, floor_z=floor_z, **plan)

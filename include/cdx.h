@@ -890,6 +890,48 @@ int cdx_hand_term(const cdx_chain* chain, const cdx_hand* h, const cdx_hand_para
 /* sizeof(cdx_hand), sizeof(cdx_hand_params). */
 void cdx_hand_abi_sizes(size_t* out2);
 
+/* ------------------------------------------------------ approach trajectories -------
+ * Batched CHOMP (Ratliff et al., ICRA 2009) on joint-space trajectories: what the reference asks of cuRobo's MotionGen
+ * (traj_gen.py); parity with cuRobo is unpinned and not attempted.  The rule — every formula and the order of every
+ * sum — is csrc/cdx_traj.h.  A trajectory row is q [T*n_dofs] f64, waypoint-major; q[0] and q[T−1] are given and no
+ * entry writes them; 3 ≤ T ≤ CDX_TRAJ_MAX_T, 1 ≤ n_dofs ≤ CDX_MAX_DOFS.
+ *
+ * cdx_traj_seed: q_start, q_goal [G*n_dofs] → traj [G*seeds*T*n_dofs]: row g·seeds + s is the straight line plus
+ *   a_d·16u²(1−u)² per joint d, u = t/(T−1), a_d = amp·(2·U01 − 1) from Philox4x32-10 keyed by `seed` and counted by
+ *   (g·seeds + s)·n_dofs + d; a_d = 0 for s = 0.  A row depends on (seed, g, s) alone.  A non-finite start or goal makes
+ *   the whole row NaN.
+ * cdx_traj_step: one covariant step on E rows, in place.  g_c [E*T*n_dofs] and cost_t [E*T] are the collision term per
+ *   waypoint (cdx_hand_term at weight 1, accumulate 0, over E·T rows; both NULL: no collision term; the two endpoint
+ *   rows of g_c do not enter the gradient).  cost [E*3] = (U_s, U_c, U_l) unweighted at the iterate the step starts
+ *   from; U = w_smooth·U_s + w_col·U_c + w_lim·U_l replaces the row's best when U < best_cost (strict; a NaN never
+ *   wins): then best_cost [E] = U, best_iter [E] = iteration and best_traj [E*T*n_dofs] = the whole row before the
+ *   step.  The caller presets best_cost to +inf.  Then the interior becomes ξ − step·A_T⁻¹g per joint.  One workgroup
+ *   per row, no atomics: a row's bits depend neither on E nor on its position nor on the run.  A row with a non-finite
+ *   value in traj, g_c or cost_t gets NaN in its interior and in cost, and its best_* entries stay as they are.
+ * CDX_EINVAL, with nothing written: T or n_dofs out of range, lower > upper or a NaN bound (±inf: unbounded), a
+ *   non-finite weight, margin, step or amp, seeds < 1, a NULL required pointer, only one of g_c / cost_t, G or E < 0.
+ *   G = 0 or E = 0 is a no-op. */
+#define CDX_TRAJ_MAX_T 64
+#define CDX_TRAJ_LANES 32 /* width of the tree that joins the per-joint sums (fixes their order) */
+
+typedef struct {
+  double lower[CDX_MAX_DOFS];
+  double upper[CDX_MAX_DOFS];
+  double w_smooth, w_col, w_lim; /* weights of U_s, U_c, U_l */
+  double m_lim;                  /* the limit hinge starts m_lim inside the bounds */
+  double step;                   /* ξ ← ξ − step·A_T⁻¹g */
+  int32_t T;
+  int32_t n_dofs;
+} cdx_traj_params;
+
+int cdx_traj_seed(int64_t G, int32_t seeds, int32_t T, int32_t n_dofs, const double* q_start, const double* q_goal,
+                  double amp, uint64_t seed, double* traj, cdx_stream_t stream);
+int cdx_traj_step(const cdx_traj_params* p, int64_t E, double* traj, const double* g_c, const double* cost_t,
+                  int32_t iteration, double* cost, double* best_cost, int32_t* best_iter, double* best_traj,
+                  cdx_stream_t stream);
+/* sizeof(cdx_traj_params). */
+void cdx_traj_abi_sizes(size_t* out1);
+
 /* ------------------------------------------------------- fused optimizer step ------
  * One launch per iteration of ProbabilisticGraspOptimizer.optimize (optimize_pregrasp.py:805-836)
  * after the closure: best-iterate update (:821-829, before the step, only when s > best_after),
