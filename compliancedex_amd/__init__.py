@@ -9,6 +9,10 @@ Drop-in operators (same names / arguments as the reference):
   solve_ik_pose / IKPoseResult / inverse_kinematics(solve_palm=True) / results.hand_pose_from_contacts
                                the same with the wrist an unknown: fingertips → joint angles and palm pose, for the
                                fingertip-space optimisers' results (the reference's writer cannot finish those)
+  solve_ik_frames / IKFrameResult / inverse_kinematics(target_rot=…) / results.arm_goal_for_results
+                               PyBullet's calculateInverseKinematics with a position AND an orientation
+                               (verify_grasp_robot.py:48-63): link poses → joint angles with some joints held, the
+                               arm's goal configuration for a stored grasp
   compute_sdf                  torchsdf/sdf.py
   ProbabilisticGraspOptimizer  optimize_pregrasp.py:614-839
   KinGraspOptimizer / SDFGraspOptimizer / GPISGraspOptimizer / KinGPISGraspOptimizer / WCKinGPISGraspOptimizer
@@ -60,7 +64,7 @@ from .raycast import (Camera, cast_rays, depth_to_pointcloud, observable_pointcl
 from .sampling import (SurfaceSampler, sample_points_poisson_disk, sample_points_uniformly,  # noqa: F401
                        surface_sampler)
 from .robot_model import DifferentiableRobotModel  # noqa: F401
-from .ik import IKPoseResult, IKResult, solve_ik, solve_ik_pose  # noqa: F401
+from .ik import IKFrameResult, IKPoseResult, IKResult, solve_ik, solve_ik_frames, solve_ik_pose  # noqa: F401
 from .dynamics import HoldingReport, holding_torques, impedance_torques  # noqa: F401
 from .wrench import (MinWrenchResult, compute_margin, min_wrench, minimum_wrench_reward,  # noqa: F401
                      solve_minimum_wrench)

@@ -24,6 +24,7 @@ _SIGS = {
     "cdxh_fk_jacobian": (C.c_int, [_CHAIN, _P, _I64, _P, _P]),
     "cdxh_ik_solve": (C.c_int, [_CHAIN, C.POINTER(CdxIkParams), _I64, _P, _I32] + [_P] * 8),
     "cdxh_ik_solve_pose": (C.c_int, [_CHAIN, C.POINTER(CdxIkParams), _I64, _P, _I32] + [_P] * 11),
+    "cdxh_ik_solve_frames": (C.c_int, [_CHAIN, C.POINTER(CdxIkParams), _I64, _P, _I32] + [_P] * 6 + [_U64] * 2 + [_P] * 5 + [_I32]),
     "cdxh_dyn_inverse": (C.c_int, [_CHAIN, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P, _P]),
     "cdxh_dyn_inertia": (C.c_int, [_CHAIN, _P, _I64, _P, _I32, _P]),
     "cdxh_dyn_forward": (C.c_int, [_CHAIN, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P]),

@@ -246,6 +246,9 @@ _SIGS = {
     "cdx_ik_solve_pose": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxIkParams), _I64, _P, C.c_int32, _P, _P, _P,
                                     C.POINTER(C.c_double)] + [_P] * 9),
     "cdx_ik_pose_rows_per_block": (C.c_int32, [C.c_int32, C.c_int32]),
+    "cdx_ik_solve_frames": (C.c_int, [C.POINTER(CdxChain), C.POINTER(CdxIkParams), _I64, _P, C.c_int32, _P, _P, _P,
+                                      C.POINTER(C.c_double), _P, _P, C.c_uint64, C.c_uint64] + [_P] * 7),
+    "cdx_ik_frames_rows_per_block": (C.c_int32, [C.c_int32, C.c_int32, C.c_uint64]),
     "cdx_dyn_inverse": (C.c_int, [C.POINTER(CdxChain), _P, _I64, _P, _P, _P] + [C.c_int32] * 3 + [_P, C.c_int32, _P, _P, _P]),
     "cdx_dyn_inertia": (C.c_int, [C.POINTER(CdxChain), _P, _I64, _P, C.c_int32, _P, _P]),
     "cdx_dyn_forward": (C.c_int, [C.POINTER(CdxChain), _P, _I64, _P, _P, _P] + [C.c_int32] * 3 + [_P, C.c_int32, _P, _P]),

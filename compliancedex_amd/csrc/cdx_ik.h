@@ -1,5 +1,6 @@
 // Fingertip Jacobians and batched inverse kinematics: the rule shared by the kernels (cdx_ik.hip) and the host build
-// (host_ref.cpp: cdxh_fk_jacobian, cdxh_ik_solve, cdxh_ik_solve_pose, the CPU yardsticks of those kernels).  The
+// (host_ref.cpp: cdxh_fk_jacobian, cdxh_ik_solve, cdxh_ik_solve_pose, cdxh_ik_solve_frames, the CPU yardsticks of those
+// kernels).  The
 // reference turns fingertips back into a hand pose with PyBullet's calculateInverseKinematics (verify_pregrasp.py:50-53,
 // bullet_robot.py:262-280) and has compute_endeffector_jacobian (robot_model.py:643-683); parity with PyBullet's solver
 // is unpinned.
@@ -71,6 +72,37 @@
 //   Outputs: q, palm_pos = pp, palm_rot = Rp, err (unweighted, at the returned q and pose), iters, status.
 //   Storage: IkMem of (T, D + 6): J has row stride D + 6, g has D + 6 entries (q / qn use their first D).  The pose and
 //   its trial copy (2 × 12 doubles) are indexed by constants only and live in registers.
+//
+// Pose targets and held joints (frame_ik_row).  The fixed-palm solve (ik_row) with two additions; whatever is not named
+//   here is ik_row's: the start, the bounds rounded inward, the μ schedule, the accept test on the true cost, the
+//   statuses.  Per call (64-bit words at the C ABI, 32 bits here once checked): rot_mask (bit k: tip k carries
+//   orientation rows) and dof_mask (bit d: joint d is solved).  Per row besides ik_row's inputs (`palm` is the pose of
+//   the chain's root — for an arm its base): target_rot [T][9]
+//   (row-major, world frame; an orthogonal matrix is the caller's contract; may be null where rot_mask is 0) and wr [T]
+//   in metres per radian, ≥ 0 (null: all 0.1).  A non-finite entry anywhere in target_rot or wr gives status 2 as well,
+//   and rot_err is then NaN like err.
+//   Target quaternions.  Once per row, for every tip in rot_mask: Rt′ = Rpᵀ·Rt (the products summed as mat3_mul's) becomes
+//     a unit quaternion t (xyzw) in float64 by Shepperd's rule (shepperd_quat: the branch on the largest of the trace and
+//     the three diagonal entries, ties to the first; one sqrt, no trigonometric function).
+//   Orientation residual, at every evaluation: the FK's float32 quaternion c of the tip's link, widened, divided by its
+//     float64 norm sqrt(((x² + y²) + z²) + w²);  e = t ⊗ conj(c):
+//       e_w = ((t_w·c_w + t_x·c_x) + t_y·c_y) + t_z·c_z,   e_xyz = (c_w·t_v − t_w·c_v) − t_v × c_v;
+//     ρ_k = 2·s·e_xyz with s = −1 if e_w < 0, else +1: the rotation vector from the current onto the target frame in the
+//     root's frame, of length 2·sin(θ/2);  rot_err_k = sqrt((ρx² + ρy²) + ρz²), a chord ≤ 2.
+//     cost = ½·(Σ_k |w_k·d_k|² + Σ_{k∈mask} |wr_k·ρ_k|²) + ½·ρ·Σ_{d∈dof_mask} (q_d − ref_d)²,
+//     emax = max(max_k w_k·e_k, max_{k∈mask} wr_k·rot_err_k): the one tol stops both, wr carrying the units.
+//   Rows.  M = 3T + 3·popcount(rot_mask), packed: the 3T position rows, then three rows per tip of the mask in tip order,
+//     holding the tip's float32 `ang` columns (fk_tip_columns) as they are — the exact Jacobian of ρ at θ = 0, a
+//     Gauss–Newton model elsewhere; the accept test keeps the cost from rising.  Row weights: w_k on a position row,
+//     wr_k on an orientation row.  y (ik_row's u) is w_k·Rpᵀ·(w_k·d_k) on the position rows and wr_k·(wr_k·ρ_k) on the
+//     orientation rows (ρ is already in the root's frame).  g, A, b, the Cholesky, the substitutions, δ and the trial
+//     point are ik_row's with M for 3T and these row weights.
+//   Held joints.  A joint outside dof_mask keeps clamp(float(q0_d)) to the end: in every iteration its column of Jl is
+//     zeroed and g_d = 0 (as for a joint fixed on a bound), its trial value is its value, and it is left out of the
+//     rest-pose sum of the cost and of g.
+//   With rot_mask = 0 and every joint in dof_mask the row is ik_row's bit for bit.
+//   Outputs: q, err, rot_err [T] (the chord; 0 for a tip outside rot_mask), iters, status.
+//   Storage: IkFrameMem — IkMem over M rows, the target quaternions [4·popcount] and the row weights [M].
 //
 // Storage.  Every per-row array (IkMem) is addressed as base[i·s]: s = 1 on the host, and on the device the arrays of
 // the lanes of a workgroup are interleaved in LDS (s = lanes, base shifted by the lane), so no array indexed at run time
@@ -237,14 +269,25 @@ CDX_HD double ik_eval(const cdx_chain& c, const cdx_ik_params& p, const Q& q, co
 
 // The damped system of one step over the first D columns of every row of m.J (row stride D): A = W·J·Jᵀ·W + κI and
 // b = W·J·g, A = L·Lᵀ in place, y = A⁻¹·b by two substitutions, then y ← w·y in m.y (the header's order of operations).
-// False if a pivot was not > 0.
-CDX_HD bool ik_gram_solve(const IkMem& m, const double* w, int n, int D, double kappa) {
+// False if a pivot was not > 0.  rw(a) is the weight of row a: IkTipW for three rows per tip (null: all 1), IkRowW for
+// the packed rows of frame_ik_row.
+struct IkTipW {
+  const double* w;
+  CDX_HDM double operator()(int a) const { return w ? w[a / 3] : 1.0; }
+};
+struct IkRowW {
+  const double* p;
+  int s;
+  CDX_HDM double operator()(int a) const { return p[(size_t)a * s]; }
+};
+template <class RW>
+CDX_HD bool ik_gram_solve(const IkMem& m, const RW& rw, int n, int D, double kappa) {
   const int s = m.s;
   // A and b
   for (int a = 0; a < n; ++a) {
-    const double wa = w ? w[a / 3] : 1.0;
+    const double wa = rw(a);
     for (int b = 0; b <= a; ++b) {
-      const double wb = w ? w[b / 3] : 1.0;
+      const double wb = rw(b);
       double acc = 0.0;
       CDX_IK_UNROLL
       for (int d = 0; d < D; ++d) acc += (double)m.J[(size_t)(a * D + d) * s] * (double)m.J[(size_t)(b * D + d) * s];
@@ -283,7 +326,7 @@ CDX_HD bool ik_gram_solve(const IkMem& m, const double* w, int n, int D, double 
     for (int k = i + 1; k < n; ++k) sum -= m.A[(size_t)(k * (k + 1) / 2 + i) * s] * m.y[(size_t)k * s];
     m.y[(size_t)i * s] = sum / m.A[(size_t)(i * (i + 1) / 2 + i) * s];
   }
-  for (int a = 0; a < n; ++a) m.y[(size_t)a * s] = (w ? w[a / 3] : 1.0) * m.y[(size_t)a * s];
+  for (int a = 0; a < n; ++a) m.y[(size_t)a * s] = rw(a) * m.y[(size_t)a * s];
   return pd;
 }
 
@@ -359,7 +402,7 @@ CDX_HD int ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, 
       m.g[(size_t)d * s] = g;
     }
     const double kappa = mu + p.rho;
-    const bool pd = ik_gram_solve(m, w, n, D, kappa);
+    const bool pd = ik_gram_solve(m, IkTipW{w}, n, D, kappa);
     // the trial point
     for (int d = 0; d < D; ++d) {
       double acc = 0.0;
@@ -532,7 +575,7 @@ CDX_HD int ik_pose_row(const cdx_chain& c, const cdx_ik_params& p, const double*
       m.g[(size_t)d * s] = g;
     }
     const double kappa = mu + p.rho;
-    const bool pd = ik_gram_solve(m, w, n, Dp, kappa);
+    const bool pd = ik_gram_solve(m, IkTipW{w}, n, Dp, kappa);
     // the trial point
     for (int d = 0; d < D; ++d) {
       double acc = 0.0;
@@ -587,6 +630,300 @@ CDX_HD int ik_pose_row(const cdx_chain& c, const cdx_ik_params& p, const double*
   }
   for (int i = 0; i < 3; ++i) palm_pos[i] = pp[i];
   for (int i = 0; i < 9; ++i) palm_rot[i] = Rp[i];
+  *iters = it;
+  return status;
+}
+
+// ---- pose targets and held joints (frame_ik_row, stated at the top of this file) ----
+
+// Per-row storage of frame_ik_row: IkMem over M = 3T + 3R packed rows (R = popcount(rot_mask)) for 3T, then
+// tq [4·R] (the oriented tips' target quaternions, xyzw) and rw [M] (the row weights), all at stride m.s.
+struct IkFrameMem {
+  IkMem m;
+  double *tq, *rw;
+};
+CDX_HD int ik_popcount(uint32_t v) {
+  int n = 0;
+  for (; v; v &= v - 1) ++n;
+  return n;
+}
+CDX_HD int ik_frames_rows(int T, uint32_t rot_mask) { return 3 * T + 3 * ik_popcount(rot_mask); }
+CDX_HD int ik_frames_doubles(int M, int D, int R) { return M * (M + 1) / 2 + D + M + 2 * M + 4 * R + M; }
+CDX_HD int ik_frames_floats(int M, int D) { return M * D + 2 * D; }
+CDX_HD size_t ik_frames_bytes(int T, int D, uint32_t rot_mask) {
+  const int M = ik_frames_rows(T, rot_mask);
+  return (size_t)ik_frames_doubles(M, D, ik_popcount(rot_mask)) * 8 + (size_t)ik_frames_floats(M, D) * 4;
+}
+CDX_HD IkFrameMem ik_frames_mem_at(void* base, int T, int D, uint32_t rot_mask, int lane, int s) {
+  const int R = ik_popcount(rot_mask), M = 3 * T + 3 * R;
+  IkFrameMem f;
+  double* d = (double*)base + lane;
+  f.m.A = d;
+  d += (size_t)(M * (M + 1) / 2) * s;
+  f.m.g = d;
+  d += (size_t)D * s;
+  f.m.y = d;
+  d += (size_t)M * s;
+  f.m.dv = d;
+  d += (size_t)(2 * M) * s;
+  f.tq = d;
+  d += (size_t)(4 * R) * s;
+  f.rw = d;
+  float* x = (float*)((double*)base + (size_t)ik_frames_doubles(M, D, R) * s) + lane;
+  f.m.J = x;
+  x += (size_t)(M * D) * s;
+  f.m.q = x;
+  x += (size_t)D * s;
+  f.m.qn = x;
+  f.m.s = s;
+  return f;
+}
+
+// The masks of a call: 0, or CDX_EINVAL for a rot_mask bit at or above T, a dof_mask with no bit below D or one at or
+// above D.
+CDX_HD int ik_frames_mask_code(int T, int D, uint64_t rot_mask, uint64_t dof_mask) {
+  if ((rot_mask >> T) || (dof_mask >> D)) return CDX_EINVAL;
+  if (!dof_mask) return CDX_EINVAL;
+  return CDX_OK;
+}
+
+// Shepperd's rule: the unit quaternion (x, y, z, w) of an orthogonal R (row-major entries r00 … r22) in float64.  The
+// branch is on the largest of the trace tr = (r00 + r11) + r22 and the three diagonal entries, ties to the first.  Trace:
+// r = sqrt(1 + tr), w = ½·r, (x, y, z) = (r21 − r12, r02 − r20, r10 − r01)·(½/r).  Entry ii, with (i, j, k) the cyclic
+// order from i: r = sqrt(((1 + r_ii) − r_jj) − r_kk), q_i = ½·r, q_j = (r_ij + r_ji)·(½/r), q_k = (r_ik + r_ki)·(½/r),
+// w = (r_kj − r_jk)·(½/r).  One sqrt, one division; written with selects on scalars only, so nothing is indexed at run
+// time.
+CDX_HD void shepperd_quat(double r00, double r01, double r02, double r10, double r11, double r12, double r20, double r21,
+                          double r22, double& x, double& y, double& z, double& w) {
+  const double tr = (r00 + r11) + r22;
+  int br = -1;
+  double best = tr;
+  if (r00 > best) { br = 0; best = r00; }
+  if (r11 > best) { br = 1; best = r11; }
+  if (r22 > best) { br = 2; }
+  const double dii = br == 0 ? r00 : (br == 1 ? r11 : r22), djj = br == 0 ? r11 : (br == 1 ? r22 : r00),
+               dkk = br == 0 ? r22 : (br == 1 ? r00 : r11);
+  const double rad = br < 0 ? 1.0 + tr : ((1.0 + dii) - djj) - dkk;
+  const double r = sqrt(rad), f = 0.5 / r, h = 0.5 * r;
+  const double s01 = (r01 + r10) * f, s12 = (r12 + r21) * f, s20 = (r20 + r02) * f;
+  const double a0 = (r21 - r12) * f, a1 = (r02 - r20) * f, a2 = (r10 - r01) * f;
+  x = br < 0 ? a0 : (br == 0 ? h : (br == 1 ? s01 : s20));
+  y = br < 0 ? a1 : (br == 0 ? s01 : (br == 1 ? h : s12));
+  z = br < 0 ? a2 : (br == 0 ? s20 : (br == 1 ? s12 : h));
+  w = br < 0 ? h : (br == 0 ? a0 : (br == 1 ? a1 : a2));
+}
+
+// ik_eval with the orientation rows: d into dv [0, 3T), ρ_k of the oriented tips into dv [3T, M) in mask order; the
+// cost and emax of frame_ik_row.
+template <class Q>
+CDX_HD double ik_frames_eval(const cdx_chain& c, const cdx_ik_params& p, const Q& q, const double* target,
+                             const double* w, const double* wr, uint32_t rot_mask, uint32_t dof_mask, const double* Rp,
+                             const double* pp, const double* po, const double* tq, double* dv, int s, double* emax) {
+  const int T = c.n_tips;
+  double ss = 0.0, sr = 0.0, em = 0.0;
+  int j = 0;
+  for (int k = 0; k < T; ++k) {
+    float pf[3], cf[4];
+    fk_tip(c, k, q, pf, cf);
+    const double v[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
+    double x[3];
+    mat3_vec(Rp, v, x);
+    const double wk = w ? w[k] : 1.0;
+    double d[3];
+    for (int i = 0; i < 3; ++i) {
+      d[i] = target[3 * k + i] - ((x[i] + pp[i]) + po[i]);
+      dv[(size_t)(3 * k + i) * s] = d[i];
+    }
+    const double e = wk * sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    em = e > em ? e : em;
+    const double r[3] = {wk * d[0], wk * d[1], wk * d[2]};
+    ss += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+    if ((rot_mask >> k) & 1u) {
+      const double cx = (double)cf[0], cy = (double)cf[1], cz = (double)cf[2], cw = (double)cf[3];
+      const double nn = sqrt(((cx * cx + cy * cy) + cz * cz) + cw * cw);
+      const double ax = cx / nn, ay = cy / nn, az = cz / nn, aw = cw / nn;
+      const double tx = tq[(size_t)(4 * j) * s], ty = tq[(size_t)(4 * j + 1) * s], tz = tq[(size_t)(4 * j + 2) * s],
+                   tw = tq[(size_t)(4 * j + 3) * s];
+      const double ew = ((tw * aw + tx * ax) + ty * ay) + tz * az;
+      const double ex = (aw * tx - tw * ax) - (ty * az - tz * ay);
+      const double ey = (aw * ty - tw * ay) - (tz * ax - tx * az);
+      const double ez = (aw * tz - tw * az) - (tx * ay - ty * ax);
+      const double sg = ew < 0.0 ? -2.0 : 2.0;
+      const double ro[3] = {sg * ex, sg * ey, sg * ez};
+      for (int i = 0; i < 3; ++i) dv[(size_t)(3 * T + 3 * j + i) * s] = ro[i];
+      const double wrk = wr ? wr[k] : 0.1;
+      const double er = wrk * sqrt((ro[0] * ro[0] + ro[1] * ro[1]) + ro[2] * ro[2]);
+      em = er > em ? er : em;
+      const double rr[3] = {wrk * ro[0], wrk * ro[1], wrk * ro[2]};
+      sr += (rr[0] * rr[0] + rr[1] * rr[1]) + rr[2] * rr[2];
+      ++j;
+    }
+  }
+  double sq = 0.0;
+  for (int d = 0; d < c.n_dofs; ++d) {
+    if (!((dof_mask >> d) & 1u)) continue;
+    const double dq = (double)q[d] - p.ref_q[d];
+    sq += dq * dq;
+  }
+  *emax = em;
+  return 0.5 * (ss + sr) + (0.5 * p.rho) * sq;
+}
+
+// One row of the pose-target solve (p: after ik_prepare; po: 3 doubles; the masks: after ik_frames_mask_code; f:
+// ik_frames_mem_at of (T, D, rot_mask)).  target_rot may be null where rot_mask is 0.  Leaves q in f.m.q, writes err [T],
+// rot_err [T] (0 for a tip outside rot_mask) and *iters, returns the status.  Status 2 leaves f untouched.
+CDX_HD int frame_ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0,
+                        const double* target, const double* target_rot, const double* palm, const double* w,
+                        const double* wr, uint32_t rot_mask, uint32_t dof_mask, const IkFrameMem& f, double* err,
+                        double* rot_err, int32_t* iters) {
+  const IkMem& m = f.m;
+  const int T = c.n_tips, D = c.n_dofs, n = ik_frames_rows(T, rot_mask), s = m.s;
+  bool fin = true;
+  for (int d = 0; d < D; ++d) {
+    const double v = q0[d];
+    fin = fin && __builtin_isfinite(v) && __builtin_isfinite((float)v);
+  }
+  for (int i = 0; i < 3 * T; ++i) fin = fin && __builtin_isfinite(target[i]);
+  if (palm)
+    for (int i = 0; i < 6; ++i) fin = fin && __builtin_isfinite(palm[i]);
+  if (w)
+    for (int k = 0; k < T; ++k) fin = fin && __builtin_isfinite(w[k]);
+  if (target_rot)
+    for (int i = 0; i < 9 * T; ++i) fin = fin && __builtin_isfinite(target_rot[i]);
+  if (wr)
+    for (int k = 0; k < T; ++k) fin = fin && __builtin_isfinite(wr[k]);
+  *iters = 0;
+  if (!fin) {
+    for (int k = 0; k < T; ++k) err[k] = rot_err[k] = NAN;
+    return 2;
+  }
+  double Rp[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, pp[3] = {0.0, 0.0, 0.0};
+  if (palm) {
+    euler_xyz(palm + 3, Rp, nullptr, nullptr, nullptr);
+    for (int i = 0; i < 3; ++i) pp[i] = palm[i];
+  }
+  // the target quaternions and the row weights, once
+  {
+    int j = 0;
+    for (int k = 0; k < T; ++k) {
+      const double wk = w ? w[k] : 1.0;
+      for (int i = 0; i < 3; ++i) f.rw[(size_t)(3 * k + i) * s] = wk;
+      if ((rot_mask >> k) & 1u) {
+        // (Rpᵀ·Rt entry by entry, indexed by constants only: the matrix stays in registers)
+        const double* B = target_rot + 9 * k;
+        auto el = [&](int i, int c3) { return (Rp[i] * B[c3] + Rp[3 + i] * B[3 + c3]) + Rp[6 + i] * B[6 + c3]; };
+        double t[4];
+        shepperd_quat(el(0, 0), el(0, 1), el(0, 2), el(1, 0), el(1, 1), el(1, 2), el(2, 0), el(2, 1), el(2, 2), t[0], t[1],
+                      t[2], t[3]);
+        const double wrk = wr ? wr[k] : 0.1;
+        f.tq[(size_t)(4 * j) * s] = t[0];
+        f.tq[(size_t)(4 * j + 1) * s] = t[1];
+        f.tq[(size_t)(4 * j + 2) * s] = t[2];
+        f.tq[(size_t)(4 * j + 3) * s] = t[3];
+        for (int i = 0; i < 3; ++i) f.rw[(size_t)(3 * T + 3 * j + i) * s] = wrk;
+        ++j;
+      }
+    }
+  }
+  for (int d = 0; d < D; ++d) {
+    const float v = (float)q0[d], lo = (float)p.lower[d], hi = (float)p.upper[d];
+    m.q[(size_t)d * s] = v < lo ? lo : (v > hi ? hi : v);
+  }
+  const QStride q{m.q, s}, qn{m.qn, s};
+  const IkRowW rw{f.rw, s};
+  int cur = 0;
+  double emax;
+  double cost = ik_frames_eval(c, p, q, target, w, wr, rot_mask, dof_mask, Rp, pp, po, f.tq, m.dv, s, &emax);
+  double mu = p.mu0;
+  int it = 0, status;
+  for (;;) {
+    if (emax <= p.tol) { status = 0; break; }
+    if (it >= p.max_iters) { status = 1; break; }
+    ++it;
+    // Jl at q: lin of every tip, then ang of the oriented tips
+    CDX_IK_UNROLL
+    for (int i = 0; i < n * D; ++i) m.J[(size_t)i * s] = 0.f;
+    {
+      int j = 0;
+      for (int k = 0; k < T; ++k) {
+        const bool rot = (rot_mask >> k) & 1u;
+        float pf[3];
+        fk_tip(c, k, q, pf, nullptr);
+        fk_tip_columns(c, k, q, pf, [&](int d, const float* l, const float* a) {
+          for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * k + i) * D + d) * s] = l[i];
+          if (rot)
+            for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * T + 3 * j + i) * D + d) * s] = a[i];
+        });
+        j += rot ? 1 : 0;
+      }
+    }
+    // u = w·Rpᵀ·(w·d) of the position rows and wr·(wr·ρ) of the orientation rows into y
+    const double* dc = m.dv + (size_t)(cur * n) * s;
+    for (int k = 0; k < T; ++k) {
+      const double wk = w ? w[k] : 1.0;
+      const double r[3] = {wk * dc[(size_t)(3 * k) * s], wk * dc[(size_t)(3 * k + 1) * s], wk * dc[(size_t)(3 * k + 2) * s]};
+      double u[3];
+      mat3t_vec(Rp, r, u);
+      for (int i = 0; i < 3; ++i) m.y[(size_t)(3 * k + i) * s] = wk * u[i];
+    }
+    for (int a = 3 * T; a < n; ++a) {
+      const double wa = rw(a);
+      m.y[(size_t)a * s] = wa * (wa * dc[(size_t)a * s]);
+    }
+    // g, the held joints, and the joints fixed on their bounds
+    for (int d = 0; d < D; ++d) {
+      double acc = 0.0;
+      CDX_IK_UNROLL
+      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * D + d) * s] * m.y[(size_t)a * s];
+      const double qd = (double)q[d];
+      double g = acc + p.rho * (p.ref_q[d] - qd);
+      if (!((dof_mask >> d) & 1u) || (qd <= p.lower[d] && g < 0.0) || (qd >= p.upper[d] && g > 0.0)) {
+        g = 0.0;
+        for (int a = 0; a < n; ++a) m.J[(size_t)(a * D + d) * s] = 0.f;
+      }
+      m.g[(size_t)d * s] = g;
+    }
+    const double kappa = mu + p.rho;
+    const bool pd = ik_gram_solve(m, rw, n, D, kappa);
+    // the trial point
+    for (int d = 0; d < D; ++d) {
+      double acc = 0.0;
+      CDX_IK_UNROLL
+      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * D + d) * s] * m.y[(size_t)a * s];
+      const double v = (double)q[d] + (m.g[(size_t)d * s] - acc) / kappa;
+      const float vn = (float)(v < p.lower[d] ? p.lower[d] : (v > p.upper[d] ? p.upper[d] : v));
+      m.qn[(size_t)d * s] = ((dof_mask >> d) & 1u) ? vn : m.q[(size_t)d * s];
+    }
+    double emn;
+    const double cn = ik_frames_eval(c, p, qn, target, w, wr, rot_mask, dof_mask, Rp, pp, po, f.tq,
+                                     m.dv + (size_t)((1 - cur) * n) * s, s, &emn);
+    if (pd && cn < cost) {
+      for (int d = 0; d < D; ++d) m.q[(size_t)d * s] = m.qn[(size_t)d * s];
+      cur = 1 - cur;
+      cost = cn;
+      emax = emn;
+      mu = mu / p.nu;
+      mu = mu > p.mu_min ? mu : p.mu_min;
+    } else {
+      mu = mu * p.nu;
+      mu = mu < p.mu_max ? mu : p.mu_max;
+    }
+  }
+  const double* dc = m.dv + (size_t)(cur * n) * s;
+  {
+    int j = 0;
+    for (int k = 0; k < T; ++k) {
+      const double d[3] = {dc[(size_t)(3 * k) * s], dc[(size_t)(3 * k + 1) * s], dc[(size_t)(3 * k + 2) * s]};
+      err[k] = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+      rot_err[k] = 0.0;
+      if ((rot_mask >> k) & 1u) {
+        const double* ro = dc + (size_t)(3 * T + 3 * j) * s;
+        const double a = ro[0], b = ro[(size_t)s], cc = ro[(size_t)2 * s];
+        rot_err[k] = sqrt((a * a + b * b) + cc * cc);
+        ++j;
+      }
+    }
+  }
   *iters = it;
   return status;
 }

@@ -13,6 +13,9 @@
 //   ik_pose_kernel      the same layout for the free-wrist solve (ik_pose_row): six more columns per row of Jl (a hand's
 //                       row needs 2.3 KB, still 16 rows a workgroup; iiwa7_allegro 2.8 KB, 8 rows), the palm pose and
 //                       its trial copy in registers.
+//   ik_frames_kernel    the same layout for pose targets and held joints (frame_ik_row): three more rows of Jl per
+//                       oriented tip, the target quaternions and the row weights in LDS as well (iiwa7_allegro's palm
+//                       link, one oriented tip: 1.3 KB a row, 16 rows a workgroup).
 #include <hip/hip_runtime.h>
 
 #include "cdx_ik.h"
@@ -98,14 +101,46 @@ __global__ __launch_bounds__(64) void ik_pose_kernel(IkArgs a, int64_t E, const 
   status[e] = st;
 }
 
-// Lanes (rows) per workgroup: the largest power of two ≤ 64 whose rows fit in 40 KB of LDS (four workgroups on a
-// compute unit's 160 KB), at least 1.
-int ik_lanes(int T, int D) {
-  const size_t row = cdx::ik_mem_bytes(T, D);
+// The pose-target solve (frame_ik_row): the layout of ik_solve_kernel over M = 3T + 3·popcount(rot_mask) packed rows,
+// with the target quaternions and the row weights next to them in LDS (IkFrameMem).
+__global__ __launch_bounds__(64) void ik_frames_kernel(IkArgs a, int64_t E, const void* __restrict__ q0, int q_f64,
+                                                       const double* __restrict__ target,
+                                                       const double* __restrict__ target_rot,
+                                                       const double* __restrict__ palm, const double* __restrict__ w,
+                                                       const double* __restrict__ wr, uint32_t rot_mask,
+                                                       uint32_t dof_mask, void* __restrict__ q, double* __restrict__ err,
+                                                       double* __restrict__ rot_err, int32_t* __restrict__ iters,
+                                                       int32_t* __restrict__ status) {
+  const IkArgs& ka = *(const IkArgs*)(__builtin_amdgcn_kernarg_segment_ptr());
+  const int lanes = (int)blockDim.x, lane = (int)threadIdx.x;
+  const int64_t e = (int64_t)blockIdx.x * lanes + lane;
+  if (e >= E) return;
+  const int T = ka.c.n_tips, D = ka.c.n_dofs;
+  const cdx::IkFrameMem f = cdx::ik_frames_mem_at(ik_lds, T, D, rot_mask, lane, lanes);
+  const cdx::Q0Row q0r{q_f64 ? (const void*)((const double*)q0 + e * D) : (const void*)((const float*)q0 + e * D), q_f64};
+  int32_t it;
+  const int st = cdx::frame_ik_row(ka.c, ka.p, ka.po, q0r, target + e * T * 3,
+                                   target_rot ? target_rot + e * T * 9 : nullptr, palm ? palm + e * 6 : nullptr,
+                                   w ? w + e * T : nullptr, wr ? wr + e * T : nullptr, rot_mask, dof_mask, f,
+                                   err + e * T, rot_err + e * T, &it);
+  for (int d = 0; d < D; ++d) {
+    if (q_f64)
+      ((double*)q)[e * D + d] = st == 2 ? ((const double*)q0)[e * D + d] : (double)f.m.q[(size_t)d * lanes];
+    else
+      ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : f.m.q[(size_t)d * lanes];
+  }
+  iters[e] = it;
+  status[e] = st;
+}
+
+// Lanes (rows) per workgroup: the largest power of two ≤ 64 whose rows of `row` bytes fit in 40 KB of LDS (four
+// workgroups on a compute unit's 160 KB), at least 1.
+int ik_lanes_bytes(size_t row) {
   int lanes = 64;
   while (lanes > 1 && row * lanes > 40960) lanes >>= 1;
   return lanes;
 }
+int ik_lanes(int T, int D) { return ik_lanes_bytes(cdx::ik_mem_bytes(T, D)); }
 
 }  // namespace
 
@@ -189,6 +224,46 @@ int cdx_ik_solve_pose(const cdx_chain* chain, const cdx_ik_params* params, int64
   hipLaunchKernelGGL(ik_pose_kernel, dim3((unsigned)blocks), dim3((unsigned)lanes), lds,
                      reinterpret_cast<hipStream_t>(stream), a, E, q0, (int)(q_dtype == CDX_DTYPE_F64), target, palm0_pos,
                      palm0_rot, w, q, palm_pos, palm_rot, err, iters, status);
+  return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;
+}
+
+int32_t cdx_ik_frames_rows_per_block(int32_t n_tips, int32_t n_dofs, uint64_t rot_mask) {
+  if (n_tips <= 0 || n_tips > CDX_MAX_TIPS || n_dofs < 0 || n_dofs > CDX_MAX_DOFS || (rot_mask >> n_tips)) return 0;
+  const size_t row = cdx::ik_frames_bytes(n_tips, n_dofs, (uint32_t)rot_mask);
+  return row > 65536 ? 0 : ik_lanes_bytes(row);
+}
+
+int cdx_ik_solve_frames(const cdx_chain* chain, const cdx_ik_params* params, int64_t E, const void* q0, int32_t q_dtype,
+                        const double* target_pos, const double* target_rot, const double* palm,
+                        const double* palm_offset, const double* w, const double* wr, uint64_t rot_mask64,
+                        uint64_t dof_mask64, void*, void* q, double* err, double* rot_err, int32_t* iters, int32_t* status,
+                        cdx_stream_t stream) {
+  int rc = cdx::ik_chain_code(chain);
+  if (rc) return rc;
+  IkArgs a;
+  rc = cdx::ik_prepare(params, chain->n_dofs, &a.p);
+  if (rc) return rc;
+  if (E < 0 || (q_dtype != CDX_DTYPE_F32 && q_dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
+  const int T = chain->n_tips, D = chain->n_dofs;
+  rc = cdx::ik_frames_mask_code(T, D, rot_mask64, dof_mask64);
+  if (rc) return rc;
+  const uint32_t rot_mask = (uint32_t)rot_mask64, dof_mask = (uint32_t)dof_mask64;
+  const size_t row = cdx::ik_frames_bytes(T, D, rot_mask);
+  if (row > 65536) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (!q0 || !target_pos || !q || !err || !rot_err || !iters || !status || (rot_mask && !target_rot)) return CDX_ECHAIN;
+  a.c = *chain;
+  for (int i = 0; i < 3; ++i) {
+    a.po[i] = palm_offset ? palm_offset[i] : 0.0;
+    if (!__builtin_isfinite(a.po[i])) return CDX_EINVAL;
+  }
+  const int lanes = ik_lanes_bytes(row);
+  const size_t lds = row * lanes;
+  const int64_t blocks = (E + lanes - 1) / lanes;
+  if (blocks > 0x7fffffff || lds > 65536) return CDX_EINVAL;
+  hipLaunchKernelGGL(ik_frames_kernel, dim3((unsigned)blocks), dim3((unsigned)lanes), lds,
+                     reinterpret_cast<hipStream_t>(stream), a, E, q0, (int)(q_dtype == CDX_DTYPE_F64), target_pos,
+                     target_rot, palm, w, wr, rot_mask, dof_mask, q, err, rot_err, iters, status);
   return hipGetLastError() == hipSuccess ? CDX_OK : CDX_ELAUNCH;
 }
 

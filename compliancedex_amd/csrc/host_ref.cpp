@@ -440,6 +440,51 @@ int cdxh_ik_solve_pose(const cdx_chain* c, const cdx_ik_params* params, int64_t 
   return CDX_OK;
 }
 
+// The pose-target solve (frame_ik_row), with cdx_ik_solve_frames' argument checks.  device_trig = 0: the FK's sines
+// are this build's (the row is cdxh_ik_solve's bit for bit without the additions); 1: the device's definition of them
+// (cdx_hd.h), with which the kernel is held to this build bit for bit.
+int cdxh_ik_solve_frames(const cdx_chain* c, const cdx_ik_params* params, int64_t E, const void* q0, int32_t q_dtype,
+                         const double* target_pos, const double* target_rot, const double* palm,
+                         const double* palm_offset, const double* w, const double* wr, uint64_t rot_mask64,
+                         uint64_t dof_mask64, void* q, double* err, double* rot_err, int32_t* iters, int32_t* status,
+                         int32_t device_trig) {
+  const cdx::HostDeviceTrig trig(device_trig ? 1 : 0);
+  int rc = cdx::ik_chain_code(c);
+  if (rc) return rc;
+  cdx_ik_params p;
+  rc = cdx::ik_prepare(params, c->n_dofs, &p);
+  if (rc) return rc;
+  if (E < 0 || (q_dtype != CDX_DTYPE_F32 && q_dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
+  const int T = c->n_tips, D = c->n_dofs, f64 = q_dtype == CDX_DTYPE_F64;
+  rc = cdx::ik_frames_mask_code(T, D, rot_mask64, dof_mask64);
+  if (rc) return rc;
+  const uint32_t rot_mask = (uint32_t)rot_mask64, dof_mask = (uint32_t)dof_mask64;
+  if (cdx::ik_frames_bytes(T, D, rot_mask) > 65536) return CDX_EINVAL;
+  if (E == 0) return CDX_OK;
+  if (!q0 || !target_pos || !q || !err || !rot_err || !iters || !status || (rot_mask && !target_rot)) return CDX_ECHAIN;
+  double po[3];
+  for (int i = 0; i < 3; ++i) {
+    po[i] = palm_offset ? palm_offset[i] : 0.0;
+    if (!__builtin_isfinite(po[i])) return CDX_EINVAL;
+  }
+  std::vector<double> mem((cdx::ik_frames_bytes(T, D, rot_mask) + 7) / 8);
+  const cdx::IkFrameMem f = cdx::ik_frames_mem_at(mem.data(), T, D, rot_mask, 0, 1);
+  for (int64_t e = 0; e < E; ++e) {
+    const cdx::Q0Row q0r{f64 ? (const void*)((const double*)q0 + e * D) : (const void*)((const float*)q0 + e * D), f64};
+    const int st = cdx::frame_ik_row(*c, p, po, q0r, target_pos + e * T * 3, target_rot ? target_rot + e * T * 9 : nullptr,
+                                     palm ? palm + e * 6 : nullptr, w ? w + e * T : nullptr, wr ? wr + e * T : nullptr,
+                                     rot_mask, dof_mask, f, err + e * T, rot_err + e * T, iters + e);
+    for (int d = 0; d < D; ++d) {
+      if (f64)
+        ((double*)q)[e * D + d] = st == 2 ? ((const double*)q0)[e * D + d] : (double)f.m.q[d];
+      else
+        ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : f.m.q[d];
+    }
+    status[e] = st;
+  }
+  return CDX_OK;
+}
+
 // Rigid-body dynamics (cdx_dyn.h) row by row, with the device entries' argument checks; every pointer is host memory.
 int cdxh_dyn_inverse(const cdx_chain* c, const cdx_dyn* dyn, int64_t B, const void* q, const void* qd, const void* qdd,
                      int32_t dtype, int32_t include_gravity, int32_t use_damping, const double* gravity,

@@ -1,5 +1,6 @@
 """Batched inverse kinematics on the device: fingertip positions → joint angles (cdx_ik_solve; the rule is
-csrc/cdx_ik.h).  The reference leaves this to PyBullet's calculateInverseKinematics (verify_pregrasp.py:50-53,
+csrc/cdx_ik.h), with the palm's pose as an unknown (solve_ik_pose), or with link orientations as targets and some
+joints held (solve_ik_frames).  The reference leaves this to PyBullet's calculateInverseKinematics (verify_pregrasp.py:50-53,
 bullet_robot.py:262-280); here it is one launch for E candidates: Levenberg–Marquardt within the joint limits, float32
 FK (the fingertips are ``compute_forward_kinematics``'s bit for bit) and float64 algebra, with the TRUE geometric
 Jacobian — not the FK module's autograd gradient, which keeps the reference's detached quaternion scale.
@@ -24,6 +25,11 @@ IKPoseResult.__doc__ = """The free-wrist solve's result: q, err, iters, status a
 [E, 3, 3] float64, the palm pose the solve returns (fingertips = palm_rot·FK(q) + palm_pos + palm_offset), and
 palm_pose [E, 6] = palm_pos + the XYZ Euler angles of palm_rot, the form the optimisers and ``forward_kinematics`` take.
 A status-2 row has NaN in the three pose fields.  Device tensors."""
+
+IKFrameResult = namedtuple("IKFrameResult", ["q", "err", "rot_err", "iters", "status"])
+IKFrameResult.__doc__ = """The pose-target solve's result: q, err, iters, status as IKResult (status 0: every weighted
+position AND orientation error ≤ tol); rot_err [E, T] float64, the angle in radians left between each oriented link's
+frame and its target (0 for a link without an orientation target, NaN in a status-2 row).  Device tensors."""
 
 LM_DEFAULTS = dict(mu0=1e-3, mu_min=1e-9, mu_max=1e6, nu=4.0)
 
@@ -233,3 +239,121 @@ def solve_ik_pose(robot_model, target, link_names, offsets=None, q0=None, palm_p
                                   N.ptr(iters), N.ptr(status), N.stream_ptr(dev)), "cdx_ik_solve_pose")
     palm_pose = torch.cat([palm_pos, matrix_to_euler_xyz(palm_rot)], 1)
     return IKPoseResult(q, palm_pose, palm_pos, palm_rot, err, iters, status)
+
+
+def quaternion_matrix(quat):
+    """Rotation matrices [..., 3, 3] float64 of xyzw quaternions [..., 4] (the convention of
+    ``compute_forward_kinematics``), normalised first.  Any device, batched."""
+    q = torch.as_tensor(quat).to(torch.float64)
+    q = q / q.norm(dim=-1, keepdim=True)
+    x, y, z, w = q.unbind(-1)
+    rows = [1.0 - 2.0 * (y * y + z * z), 2.0 * (x * y - z * w), 2.0 * (x * z + y * w),
+            2.0 * (x * y + z * w), 1.0 - 2.0 * (x * x + z * z), 2.0 * (y * z - x * w),
+            2.0 * (x * z - y * w), 2.0 * (y * z + x * w), 1.0 - 2.0 * (x * x + y * y)]
+    return torch.stack(rows, -1).reshape(*q.shape[:-1], 3, 3)
+
+
+def joint_indices(robot_model, joints):
+    """DOF indices of ``joints``: integers, joint names or the names of the links the joints move."""
+    chain = robot_model.chain
+    by_name = {}
+    for i, b in enumerate(chain.bodies):
+        if chain.dof[i] >= 0:
+            by_name.setdefault(b["name"], chain.dof[i])
+            if b.get("joint_name"):
+                by_name[b["joint_name"]] = chain.dof[i]
+    out = []
+    for j in joints:
+        if isinstance(j, str):
+            if j not in by_name:
+                raise KeyError(f"no moving joint named {j!r}")
+            j = by_name[j]
+        j = int(j)
+        if not 0 <= j < chain.n_dofs:
+            raise ValueError(f"joint index {j} outside [0, {chain.n_dofs})")
+        out.append(j)
+    return out
+
+
+def solve_ik_frames(robot_model, target_pos, target_rot, link_names, offsets=None, q0=None, base_pose=None,
+                    palm_offset=None, weights=None, rot_weights=0.1, oriented=None, joints=None, ref_q=None, rho=0.0,
+                    max_iters=100, tol=1e-5, **lm):
+    """Joint angles with which the links ``link_names`` (+ ``offsets``) reach positions ``target_pos`` [E, T, 3] AND
+    orientations ``target_rot`` → IKFrameResult (cdx_ik_solve_frames; the rule is frame_ik_row in csrc/cdx_ik.h).  What
+    the reference asks of PyBullet's calculateInverseKinematics with a position and an orientation
+    (verify_grasp_robot.py:48-63).
+
+    ``target_rot`` [E, T, 3, 3] rotation matrices or [E, T, 4] xyzw quaternions (the convention of
+    ``compute_forward_kinematics``), world frame, converted with torch operators on the device; ``oriented``: one bool
+    per link, whether it has an orientation target (default all); ``rot_weights`` a float, [T] or [E, T] in metres per
+    radian: the one ``tol`` stops a link when its position error ≤ tol AND rot_weights × its chord ≤ tol (1e-5 m at
+    0.1 is 1e-4 rad).  ``joints``: the joints that are solved, by name or index (default all); the others keep their
+    ``q0`` (clamped to the limits) and take no part in the ``rho`` term.  ``base_pose`` [E, 6] or [6]: the pose of the
+    chain's root (position + XYZ Euler angles; None: identity).  The other arguments are ``solve_ik``'s.  Runs on the
+    current stream without waiting for it."""
+    lib = N.load()
+    dev = robot_model._device
+    T, D = len(link_names), robot_model._n_dofs
+    target = torch.as_tensor(target_pos, dtype=torch.float64, device=dev)
+    if target.ndim == 2 and target.shape == (T, 3):
+        target = target.unsqueeze(0)
+    if target.ndim != 3 or target.shape[1:] != (T, 3):
+        raise ValueError(f"target_pos must have shape [E, {T}, 3], got {tuple(target.shape)}")
+    if not target.is_cuda:
+        raise RuntimeError("compliancedex_amd IK runs on the GPU only")
+    E = target.shape[0]
+    target = target.contiguous()
+    rot = torch.as_tensor(target_rot, device=dev)
+    if rot.shape[-1] == 4 and rot.shape[-2:] != (3, 3):
+        rot = quaternion_matrix(rot)
+    rot = rot.to(torch.float64)
+    if rot.shape == (T, 3, 3):
+        rot = rot.expand(E, T, 3, 3)
+    if rot.shape != (E, T, 3, 3):
+        raise ValueError(f"target_rot must have shape [E, {T}, 3, 3] or [E, {T}, 4], got {tuple(rot.shape)}")
+    rot = rot.contiguous()
+    oriented = [True] * T if oriented is None else [bool(v) for v in oriented]
+    if len(oriented) != T:
+        raise ValueError(f"oriented must have {T} entries")
+    rot_mask = sum(1 << k for k, v in enumerate(oriented) if v)
+    solved = range(D) if joints is None else joint_indices(robot_model, joints)
+    dof_mask = 0
+    for d in solved:
+        dof_mask |= 1 << d
+    if not dof_mask:
+        raise ValueError("joints: at least one joint must be solved")
+    lower, upper = joint_box(robot_model.get_joint_limits())
+    params = ik_params(lower, upper, _host_list(ref_q), rho, max_iters, tol, **lm)
+    if q0 is None:
+        q0 = torch.tensor([params.ref_q[d] for d in range(D)], dtype=torch.float64, device=dev)
+    else:
+        q0 = torch.as_tensor(q0, device=dev)
+        if q0.dtype not in (torch.float32, torch.float64):
+            q0 = q0.to(torch.float64)
+    if q0.shape == (D,):
+        q0 = q0.expand(E, D)
+    if q0.shape != (E, D):
+        raise ValueError(f"q0 must have shape {(E, D)} or {(D,)}, got {tuple(q0.shape)}")
+    q0 = q0.detach().contiguous()
+    base = _rows(base_pose, E, (6,), "base_pose", dev)
+    w = _rows(weights, E, (T,), "weights", dev)
+    if isinstance(rot_weights, (int, float)):
+        rot_weights = [float(rot_weights)] * T
+    wr = _rows(rot_weights, E, (T,), "rot_weights", dev)
+    po = _host_list(palm_offset)
+    if po is not None and len(po) != 3:
+        raise ValueError("palm_offset must have 3 entries")
+    po_c = (C.c_double * 3)(*po) if po is not None else None
+    q = torch.empty_like(q0)
+    err = torch.empty(E, T, dtype=torch.float64, device=dev)
+    chord = torch.empty(E, T, dtype=torch.float64, device=dev)
+    iters = torch.empty(E, dtype=torch.int32, device=dev)
+    status = torch.empty(E, dtype=torch.int32, device=dev)
+    chain = robot_model._descriptor(link_names, offsets)
+    dtype = N.DTYPE_F64 if q0.dtype == torch.float64 else N.DTYPE_F32
+    N.check(lib.cdx_ik_solve_frames(chain, C.byref(params), E, N.ptr(q0), dtype, N.ptr(target), N.ptr(rot), N.ptr(base),
+                                    po_c, N.ptr(w), N.ptr(wr), rot_mask, dof_mask, None, N.ptr(q), N.ptr(err),
+                                    N.ptr(chord), N.ptr(iters), N.ptr(status), N.stream_ptr(dev)),
+            "cdx_ik_solve_frames")
+    rot_err = 2.0 * torch.asin(torch.clamp(0.5 * chord, max=1.0))
+    return IKFrameResult(q, err, rot_err, iters, status)

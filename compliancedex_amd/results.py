@@ -153,3 +153,196 @@ def approach_for_results(robot_model, hand, q_start, results, obj, floor_z=None,
     wrist = None if wrist is None else torch.as_tensor(_np(wrist), dtype=torch.float64, device=dev)
     return plan_approach(robot_model, hand, torch.as_tensor(_np(q_start), dtype=torch.float64, device=dev), goal, obj,
                          palm_pose=wrist, floor_z=floor_z, **plan)
+
+
+# ------------------------------------------------------------------ from a stored grasp to the arm
+def _chain_of(model):
+    return model.chain if hasattr(model, "chain") else model
+
+
+def _np_fk(desc, q):
+    """Float64 FK of a cdx_chain descriptor on the host → (tip positions [B, T, 3], tip-link rotations [B, T, 3, 3]):
+    R′ = R·F·A(sign·q), t′ = R·t_b + t, the tip offset rotated by the link.  Set-up arithmetic of ``hand_mount``; the
+    solves themselves run on the device."""
+    q = np.asarray(q, np.float64)
+    B, T = q.shape[0], desc.n_tips
+    pos, rot = np.zeros((B, T, 3)), np.zeros((B, T, 3, 3))
+    for k in range(T):
+        path, b = [], desc.tip_body[k]
+        while b > 0:
+            path.append(b)
+            b = desc.bodies[b].parent
+        R, t = np.broadcast_to(np.eye(3), (B, 3, 3)).copy(), np.zeros((B, 3))
+        for bi in reversed(path):
+            body = desc.bodies[bi]
+            t = t + R @ np.array(list(body.t), np.float64)
+            R = R @ np.array(list(body.F), np.float64).reshape(3, 3)
+            if body.dof >= 0:
+                th = float(body.sign) * q[:, body.dof]
+                A = np.zeros((B, 3, 3))
+                i, j = [(1, 2), (2, 0), (0, 1)][body.axis]
+                A[:, body.axis, body.axis] = 1.0
+                A[:, i, i] = A[:, j, j] = np.cos(th)
+                A[:, i, j], A[:, j, i] = -np.sin(th), np.sin(th)
+                R = R @ A
+        if desc.has_offsets:
+            t = t + R @ np.array(list(desc.tip_offset[k]), np.float64)
+        pos[:, k], rot[:, k] = t, R
+    return pos, rot
+
+
+def hand_mount(arm_model, hand_model, hand_config, palm_link="palm_link", rows=4, seed=0, residual=False):
+    """How the hand-only model sits in the arm model → (R_x [3, 3], t_x [3], joint_map [D_hand]): a point p of the hand
+    model's root frame lies at R_x·p + t_x in the arm model's ``palm_link`` frame, and hand joint d is the arm model's
+    joint joint_map[d] (matched by the name of the body it moves — the two models order their fingers differently).
+
+    The transform is the Kabsch fit of the hand model's fingertips (``hand_config``'s ee_link_name / ee_link_offset, root
+    frame) onto the arm model's fingertips seen from ``palm_link``, over ``rows`` seeded joint rows inside the hand's
+    limits, in float64 on the host.  A fit whose largest residual exceeds 1e-6 m raises ValueError: the two models are
+    then not the same hand.  ``residual=True`` appends that residual (metres).  The models may be
+    DifferentiableRobotModels or Chains."""
+    from .ik import joint_box
+    arm, hnd = _chain_of(arm_model), _chain_of(hand_model)
+    links, offsets = list(hand_config["ee_link_name"]), hand_config.get("ee_link_offset")
+    if palm_link not in arm.index:
+        raise KeyError(palm_link)
+    jmap = []
+    for i, b in enumerate(hnd.bodies):
+        if hnd.dof[i] < 0:
+            continue
+        j = arm.index.get(b["name"])
+        if j is None or arm.dof[j] < 0:
+            raise ValueError(f"the arm model has no moving body named {b['name']!r}")
+        jmap.append(arm.dof[j])
+    lower, upper = joint_box([dict(lower=b["lower"], upper=b["upper"]) for i, b in enumerate(hnd.bodies) if hnd.dof[i] >= 0])
+    lo = np.where(np.isfinite(lower), lower, -np.pi)
+    hi = np.where(np.isfinite(upper), upper, np.pi)
+    qh = lo + (hi - lo) * np.random.default_rng(seed).random((int(rows), hnd.n_dofs))
+    qa = np.zeros((int(rows), arm.n_dofs))
+    qa[:, jmap] = qh
+    tips_h = _np_fk(hnd.descriptor(links, offsets), qh)[0]
+    tips_a = _np_fk(arm.descriptor(links, offsets, check_depth=False), qa)[0]
+    pp, Rp = _np_fk(arm.descriptor([palm_link], None, check_depth=False), qa)
+    seen = np.einsum("bji,btj->bti", Rp[:, 0], tips_a - pp)  # Rpᵀ·(tip − p_palm)
+    a, b = tips_h.reshape(-1, 3), seen.reshape(-1, 3)
+    ca, cb = a.mean(0), b.mean(0)
+    U, _, Vt = np.linalg.svd((a - ca).T @ (b - cb))
+    d = np.sign(np.linalg.det(Vt.T @ U.T))
+    R = Vt.T @ np.diag([1.0, 1.0, d]) @ U.T
+    t = cb - R @ ca
+    worst = float(np.linalg.norm(a @ R.T + t - b, axis=1).max())
+    if not worst <= 1e-6:
+        raise ValueError(f"hand_mount: the fingertips of the two models differ by {worst:.3g} m after the best rigid fit "
+                         f"(limit 1e-6 m): they do not describe the same hand")
+    out = (R, t, jmap)
+    return out + (worst,) if residual else out
+
+
+def arm_goal_for_results(arm_model, hand_model, hand_config, results, palm_link="palm_link", base_pose=None, q_rest=None,
+                         starts=8, spread=0.25, seed=0, hand=None, obj=None, floor_z=None, allow=0.0, lift=None, **ik):
+    """Arm-and-hand goal configurations for stored grasps → (q_goal [E, D_arm] float64, status [E] int32, info): what
+    the reference asks of PyBullet's calculateInverseKinematics with a position and an orientation
+    (verify_grasp_robot.py:48-63, :192-228).
+
+    ``results``: ``load_results``' dict; a grasp is its ``wrist`` row (position + XYZ Euler angles of the hand model's
+    root) and its ``joint_angle`` row in the hand-only model.  Through ``hand_mount`` the wrist becomes the target pose
+    of the arm model's ``palm_link``, (Rp·R_xᵀ, palm_pos + palm_offset − Rp·R_xᵀ·t_x); the finger joints go into the
+    start through the joint map and are HELD, the other joints are solved by ik.solve_ik_frames.  ``base_pose`` [6] or
+    [E, 6]: where the arm's root stands.  All E·``starts`` rows run in one launch: start 0 is ``q_rest`` (default: the
+    middle of the limits), start k is q_rest + spread·(upper − lower)·u, u uniform in [−1, 1) from a torch.Generator
+    seeded with ``seed``, clamped — as ``hand_pose_from_contacts`` seeds its own.  With ``hand`` (the arm model's
+    HandSpheres) and ``obj`` / ``floor_z``, ``penetration_report`` runs on every row; ``pick_start`` keeps one start
+    per grasp.  ``lift`` = (dx, dy, dz) adds info["lift_goal"] / info["lift_status"]: a second solve, started at each
+    kept goal, for the same orientation with the position shifted (the reference's 0.1 m lift, :225-228).
+
+    ``info`` as ``hand_pose_from_contacts``': start, n_converged, n_clear, err / rot_err [E] of the kept rows, ``all`` =
+    dict(q [E, S, D], status, werr, clear [E, S] (+ depth)) device tensors; with ``hand`` also depth / clear of the kept
+    rows.  ``ik``: options of ik.solve_ik_frames (palm_offset, rot_weights, rho, max_iters, tol, …); ``palm_offset``
+    is the hand-only model's, added to the wrist position.  Only the final copy to numpy waits for the device."""
+    import torch
+    from .ik import euler_xyz_matrix, joint_box, solve_ik_frames
+    dev = arm_model._device
+    R_x, t_x, jmap = hand_mount(arm_model, hand_model, hand_config, palm_link)
+    wrist = torch.as_tensor(_np(results["wrist"]), dtype=torch.float64, device=dev).reshape(-1, 6)
+    fingers = torch.as_tensor(_np(results["joint_angle"]), dtype=torch.float64, device=dev)
+    E, S, D = wrist.shape[0], int(starts), arm_model._n_dofs
+    if S < 1:
+        raise ValueError("starts must be at least 1")
+    if fingers.shape != (E, len(jmap)):
+        raise ValueError(f"joint_angle must have shape {(E, len(jmap))}, got {tuple(fingers.shape)}")
+    po = ik.pop("palm_offset", None)
+    po = torch.zeros(3, dtype=torch.float64) if po is None else torch.as_tensor(_np(po), dtype=torch.float64).reshape(3)
+    Rx = torch.as_tensor(R_x, dtype=torch.float64, device=dev)
+    R_l = torch.matmul(euler_xyz_matrix(wrist[:, 3:]), Rx.T)
+    p_l = wrist[:, :3] + po.to(dev) - torch.matmul(R_l, torch.as_tensor(t_x, dtype=torch.float64, device=dev))
+    lower, upper = joint_box(arm_model.get_joint_limits())
+    lo, hi = torch.tensor(lower, dtype=torch.float64), torch.tensor(upper, dtype=torch.float64)
+    if q_rest is None:
+        q_rest = [0.5 * (a + b) if np.isfinite(a) and np.isfinite(b) else 0.0 for a, b in zip(lower, upper)]
+    rest = torch.as_tensor(np.asarray(_np(q_rest), np.float64).reshape(-1))
+    span = torch.where(torch.isfinite(hi - lo), hi - lo, torch.full_like(lo, 2.0 * np.pi))
+    u = 2.0 * torch.rand(E, S, D, generator=torch.Generator().manual_seed(int(seed)), dtype=torch.float64) - 1.0
+    u[:, 0] = 0.0
+    q0 = torch.minimum(torch.maximum(rest + float(spread) * span * u, lo), hi).to(dev)
+    q0[:, :, jmap] = fingers[:, None, :]
+    q0 = q0.reshape(E * S, D)
+    solved = [d for d in range(D) if d not in set(jmap)]
+    wr = ik.get("rot_weights", 0.1)
+    base = None if base_pose is None else torch.as_tensor(_np(base_pose), dtype=torch.float64, device=dev)
+    base_rows = None if base is None else (base.expand(E, 6) if base.ndim == 1 else base).repeat_interleave(S, 0)
+    ref_q = ik.pop("ref_q", rest.tolist())
+
+    def run(q_start, pos, rot, palm):
+        return solve_ik_frames(arm_model, pos.unsqueeze(1), rot.unsqueeze(1), [palm_link], q0=q_start, base_pose=palm,
+                               joints=solved, ref_q=ref_q, **ik)
+    res = run(q0, p_l.repeat_interleave(S, 0), R_l.repeat_interleave(S, 0), base_rows)
+    werr = torch.maximum(res.err[:, 0], float(wr) * res.rot_err[:, 0]).view(E, S) if isinstance(wr, (int, float)) \
+        else torch.maximum(res.err[:, 0], res.rot_err[:, 0]).view(E, S)
+    status = res.status.view(E, S)
+    every = dict(q=res.q.view(E, S, D), status=status, werr=werr, err=res.err.view(E, S), rot_err=res.rot_err.view(E, S))
+    if hand is not None:
+        from .hand import penetration_report
+        good = (res.status != 2).unsqueeze(1)
+        root = torch.zeros(E * S, 6, dtype=torch.float64, device=dev) if base_rows is None else base_rows
+        rep = penetration_report(hand, torch.where(good, res.q, q0), root, obj, floor_z, allow)
+        every["depth"] = rep["depth"].view(E, S, 3)
+        every["clear"] = (rep["clear"] & good[:, 0]).view(E, S)
+    else:
+        every["clear"] = torch.ones(E, S, dtype=torch.bool, device=dev)
+    pick = pick_start(status, every["clear"], werr)
+    rows = torch.arange(E, device=dev)
+    goal = every["q"][rows, pick].double()
+    info = dict(start=pick, n_converged=(status == 0).sum(1), n_clear=every["clear"].sum(1), err=every["err"][rows, pick],
+                rot_err=every["rot_err"][rows, pick])
+    if hand is not None:
+        info["depth"], info["clear"] = every["depth"][rows, pick], every["clear"][rows, pick]
+    if lift is not None:
+        shift = torch.as_tensor(np.asarray(_np(lift), np.float64).reshape(3), device=dev)
+        up = run(goal, p_l + shift, R_l, None if base is None else (base.expand(E, 6) if base.ndim == 1 else base))
+        info["lift_goal"], info["lift_status"] = up.q.double(), up.status
+    q_goal, st = goal.cpu().numpy(), status[rows, pick].cpu().numpy()
+    info = {k: v.cpu().numpy() for k, v in info.items()}
+    info["all"] = every
+    return q_goal, st, info
+
+
+def arm_approach_for_results(arm_model, hand_model, hand_config, hand_spheres, q_start, results, obj, floor_z=None,
+                             base_pose=None, exp_name=None, data_dir="data", goal=None, **plan):
+    """Approach paths of the whole arm from ``q_start`` [D_arm] (or [E, D_arm]) to every stored grasp:
+    ``arm_goal_for_results`` (options in the dict ``goal``; ``hand_spheres``, ``obj`` and ``floor_z`` rank its starts
+    as well) chained into trajectory.plan_approach with the arm's root at ``base_pose`` → (ApproachPlan, q_goal [E, D_arm],
+    status [E], info).  A grasp whose goal has status ≠ 0 has ``success`` False, whatever its path looks like.
+    ``results`` None: loaded from ``exp_name`` / ``data_dir``; ``plan``: options of plan_approach."""
+    import torch
+    from .trajectory import plan_approach
+    if results is None:
+        results = load_results(exp_name, data_dir)
+    q_goal, status, info = arm_goal_for_results(arm_model, hand_model, hand_config, results, base_pose=base_pose,
+                                                hand=hand_spheres, obj=obj, floor_z=floor_z, **(goal or {}))
+    dev = hand_spheres.device
+    base = None if base_pose is None else torch.as_tensor(_np(base_pose), dtype=torch.float64, device=dev)
+    out = plan_approach(arm_model, hand_spheres, torch.as_tensor(_np(q_start), dtype=torch.float64, device=dev),
+                        torch.as_tensor(q_goal, dtype=torch.float64, device=dev), obj, palm_pose=base, floor_z=floor_z,
+                        **plan)
+    out.success = out.success & torch.as_tensor(status == 0, device=dev)
+    return out, q_goal, status, info

@@ -233,11 +233,24 @@ class DifferentiableRobotModel(torch.nn.Module):
         return lin[:, 0], ang[:, 0]
 
     def inverse_kinematics(self, target, link_names, offsets=None, q0=None, palm_pose=None, palm_offset=None,
-                           weights=None, ref_q=None, rho=0.0, max_iters=None, tol=1e-5, solve_palm=False, **lm):
+                           weights=None, ref_q=None, rho=0.0, max_iters=None, tol=1e-5, solve_palm=False,
+                           target_rot=None, oriented=None, joints=None, rot_weights=0.1, **lm):
         """Joint angles whose fingertips reach ``target`` [E, T, 3] → IKResult(q, err, iters, status); see
         ik.solve_ik.  ``solve_palm=True`` solves the palm's pose with the joints → IKPoseResult (ik.solve_ik_pose);
-        ``palm_pose`` is then only the start (None: the Kabsch start).  ``max_iters`` None: 50, or 100 with the palm."""
-        from .ik import solve_ik, solve_ik_pose
+        ``palm_pose`` is then only the start (None: the Kabsch start).  ``target_rot`` [E, T, 3, 3] or [E, T, 4] (xyzw)
+        also asks for the links' orientations → IKFrameResult (ik.solve_ik_frames, which explains ``oriented``,
+        ``joints`` and ``rot_weights``); ``palm_pose`` is then the pose of the chain's root.  ``max_iters`` None: 50, or
+        100 with the palm or with orientations."""
+        from .ik import solve_ik, solve_ik_frames, solve_ik_pose
+        if target_rot is not None:
+            if solve_palm:
+                raise ValueError("target_rot and solve_palm=True exclude each other: the free-wrist solve takes "
+                                 "positions only")
+            return solve_ik_frames(self, target, target_rot, link_names, offsets, q0, palm_pose, palm_offset, weights,
+                                   rot_weights, oriented, joints, ref_q, rho, 100 if max_iters is None else max_iters,
+                                   tol, **lm)
+        if oriented is not None or joints is not None:
+            raise ValueError("oriented / joints need target_rot")
         if solve_palm:
             return solve_ik_pose(self, target, link_names, offsets, q0, palm_pose, palm_offset, weights, ref_q, rho,
                                  100 if max_iters is None else max_iters, tol, **lm)

@@ -380,6 +380,28 @@ int cdx_ik_solve_pose(const cdx_chain* chain, const cdx_ik_params* params, int64
 /* Rows per workgroup of cdx_ik_solve_pose for a chain of these sizes (for tests of its seams). */
 int32_t cdx_ik_pose_rows_per_block(int32_t n_tips, int32_t n_dofs);
 
+/* Pose-target inverse kinematics: cdx_ik_solve with orientation targets on chosen tips and chosen joints held at their
+ * start (the rule is frame_ik_row in csrc/cdx_ik.h; one launch, no workspace, `workspace` may be NULL).  Arguments as
+ * cdx_ik_solve (`palm` is the pose of the chain's root: for an arm its base), but:
+ *   rot_mask: bit k set — tip k also has to reach the orientation target_rot [E*T*9] f64 (row-major, world frame,
+ *     orthogonal by the caller's contract; may be NULL where rot_mask is 0);
+ *   wr [E*T] f64 ≥ 0 in metres per radian (nullable: 0.1): the weight of a tip's orientation error, so that the one
+ *     `tol` (metres) stops both errors — 1e-5 m at 0.1 m/rad is 1e-4 rad;
+ *   dof_mask: bit d set — joint d is solved; the others keep clamp(float(q0)) and take no part in the rho term.
+ * Outputs besides q / err / iters / status: rot_err [E*T] f64, the chord 2·sin(θ/2) of the angle left between a tip's
+ *   frame and its target (0 for a tip outside rot_mask).  Status 2 also for a non-finite target_rot or wr; rot_err is
+ *   then NaN like err.  With rot_mask = 0 and every joint in dof_mask the results are cdx_ik_solve's bit for bit.
+ * Return codes as cdx_ik_solve; besides: a rot_mask bit at or above n_tips, a dof_mask bit at or above n_dofs or no
+ * bit at all, or a row whose storage exceeds 64 KB of LDS → CDX_EINVAL; target_rot NULL with rot_mask ≠ 0 → CDX_ECHAIN. */
+int cdx_ik_solve_frames(const cdx_chain* chain, const cdx_ik_params* params, int64_t E, const void* q0, int32_t q_dtype,
+                        const double* target_pos, const double* target_rot, const double* palm,
+                        const double* palm_offset, const double* w, const double* wr, uint64_t rot_mask,
+                        uint64_t dof_mask, void* workspace, void* q, double* err, double* rot_err, int32_t* iters,
+                        int32_t* status, cdx_stream_t stream);
+/* Rows per workgroup of cdx_ik_solve_frames for a chain of these sizes and this rot_mask (for tests of its seams);
+ * 0 for sizes or a mask the entry refuses. */
+int32_t cdx_ik_frames_rows_per_block(int32_t n_tips, int32_t n_dofs, uint64_t rot_mask);
+
 /* Rigid-body dynamics of a chain (compute_inverse_dynamics, compute_lagrangian_inertia_matrix and
  * compute_forward_dynamics, robot_model.py:266-640; the rule is csrc/cdx_dyn.h): recursive Newton–Euler in body
  * coordinates, B independent rows, one launch each, per-row state in LDS.  The inertial constants travel in a descriptor

@@ -16,6 +16,12 @@ once with the Kabsch start; its own torch statement (``torch_ik_pose``) and its 
 (cdxh_ik_solve_pose) are the yardsticks, and ``pose_over_fixed`` is its time over the fixed-palm solve's at the same E.
 Iteration medians and the share of rows that use all ``max_iters`` iterations (status 1) are kept for every path.
 
+The pose-target solve (cdx_ik_solve_frames, ``solve_ik_frames``) is the ``frames`` shape: on iiwa7_allegro the one link
+``palm_link`` with its orientation, the seven arm joints solved and the sixteen finger joints held — the arm goal of a
+stored grasp —, on the Allegro hand its four fingertips with the first one oriented; targets the FK pose of q*, starts
+q* ± 0.3 rad.  Its yardsticks are the same rule in torch operators (``torch_ik_frames``) and the host build on one core
+(cdxh_ik_solve_frames).
+
 Device times are HIP events around one call after a warm-up call of every path, the paths alternating within each
 repeat; the median of --reps and the spread (max − min)/median are kept.
 
@@ -23,7 +29,8 @@ Without --robot the tool is the driver: every shape runs in a child process of i
 other, and the first that fails, faults or runs out of time ends the run.  One JSON line per shape is printed and
 appended to the record (default profiles/ik.jsonl).  Needs a GPU: there is no fallback.
 
-  python tools/ik.py [--reps 7] [--rows 4096,16384,65536] [--robots allegro,iiwa7_allegro] [--out PATH]
+  python tools/ik.py [--reps 7] [--rows 4096,16384,65536] [--robots allegro,iiwa7_allegro] [--shapes fingertips,frames]
+                     [--out PATH]
 """
 import argparse
 import json
@@ -287,26 +294,164 @@ def run_shape(robot, E, args):
     return rec
 
 
+def frames_case(rm, robot, E, spread=0.3, seed=2):
+    """(links, offsets, oriented, solved joints, q0, target, rot, lo, hi) of the ``frames`` shape, tensors on the device."""
+    import torch
+    from compliancedex_amd.ik import quaternion_matrix
+    if robot == "iiwa7_allegro":
+        links, offsets, oriented, solved = ["palm_link"], None, [True], list(range(7))
+    else:
+        links, offsets = rm.chain.config["ee_link_name"], rm.chain.config["ee_link_offset"]
+        oriented, solved = [True] + [False] * (len(links) - 1), list(range(rm._n_dofs))
+    q0, target, lo, hi, qs = inputs(rm, links, offsets, E, spread, seed)
+    quat = rm.compute_forward_kinematics(qs.cuda().float(), links, offsets=offsets)[1].view(E, len(links), 4)
+    held = [d for d in range(rm._n_dofs) if d not in solved]
+    q0[:, held] = qs.cuda()[:, held]
+    return links, offsets, oriented, solved, q0, target, quaternion_matrix(quat).contiguous(), lo, hi
+
+
+def torch_ik_frames(rm, links, offsets, oriented, solved, q0, target, rot, lo, hi, wr=0.1, max_iters=100, tol=1e-5,
+                    mu0=1e-3, mu_min=1e-9, mu_max=1e6, nu=4.0):
+    """frame_ik_row of csrc/cdx_ik.h (ρ = 0, no base pose, unit position weights) with torch operators on the device; the
+    chord vector from the skew part of Rt·Rcᵀ over cos(θ/2), which is the rule's quaternion formula away from θ = π."""
+    import torch
+    from compliancedex_amd.ik import quaternion_matrix
+    E, D = q0.shape
+    T = len(links)
+    dev = q0.device
+    tips = [k for k in range(T) if oriented[k]]
+    M = 3 * T + 3 * len(tips)
+    lo32, hi32 = lo.float(), hi.float()
+    W = torch.cat([torch.ones(3 * T, dtype=torch.float64), torch.full((3 * len(tips),), wr, dtype=torch.float64)]).to(dev)
+    may = torch.zeros(D, dtype=torch.bool)
+    may[solved] = True
+    may = may.to(dev)
+
+    def residual(q32):
+        pos, quat = rm.compute_forward_kinematics(q32, links, offsets=offsets)
+        d = (target - pos.double().view(E, T, 3)).reshape(E, 3 * T)
+        Re = rot[:, tips] @ quaternion_matrix(quat.view(E, T, 4)[:, tips]).transpose(-1, -2)
+        v = 0.5 * torch.stack([Re[..., 2, 1] - Re[..., 1, 2], Re[..., 0, 2] - Re[..., 2, 0], Re[..., 1, 0] - Re[..., 0, 1]], -1)
+        cos = 0.5 * (Re.diagonal(dim1=-2, dim2=-1).sum(-1) - 1.0).clamp(-1.0, 1.0)
+        return torch.cat([d, (v / torch.sqrt(0.5 * (1.0 + cos)).unsqueeze(-1)).reshape(E, -1)], 1)
+
+    def emax(r):
+        return (W * r).view(E, M // 3, 3).norm(dim=2).amax(1)
+
+    q = torch.minimum(torch.maximum(q0.float(), lo32), hi32)
+    r = residual(q)
+    cost = 0.5 * ((W * r) ** 2).sum(1)
+    mu = torch.full((E,), mu0, dtype=torch.float64, device=dev)
+    iters = torch.zeros(E, dtype=torch.int32, device=dev)
+    eye = torch.eye(M, dtype=torch.float64, device=dev)
+    for _ in range(max_iters):
+        act = emax(r) > tol
+        if not bool(act.any()):
+            break
+        iters += act
+        lin, ang = rm.compute_fingertip_jacobians(q, links, offsets)
+        J = torch.cat([lin.double().view(E, 3 * T, D), ang.double()[:, tips].reshape(E, 3 * len(tips), D)], 1)
+        g = torch.bmm(J.transpose(1, 2), (W * W * r).unsqueeze(2)).squeeze(2)
+        qd = q.double()
+        free = may & ~(((qd <= lo) & (g < 0)) | ((qd >= hi) & (g > 0)))
+        J = J * free.unsqueeze(1) * W.view(1, M, 1)
+        g = g * free
+        A = torch.bmm(J, J.transpose(1, 2)) + mu.view(E, 1, 1) * eye
+        y, info = torch.linalg.solve_ex(A, torch.bmm(J, g.unsqueeze(2)))
+        delta = (g - torch.bmm(J.transpose(1, 2), y).squeeze(2)) / mu.view(E, 1)
+        qn = torch.where(may, torch.minimum(torch.maximum(qd + delta, lo), hi).float(), q)
+        rn = residual(qn)
+        cn = 0.5 * ((W * rn) ** 2).sum(1)
+        ok = act & (info == 0) & (cn < cost)
+        q = torch.where(ok.unsqueeze(1), qn, q)
+        r = torch.where(ok.unsqueeze(1), rn, r)
+        cost = torch.where(ok, cn, cost)
+        mu = torch.where(act, torch.where(ok, (mu / nu).clamp(min=mu_min), (mu * nu).clamp(max=mu_max)), mu)
+    return q, emax(r), iters
+
+
+def host_frames_seconds(rm, links, offsets, oriented, solved, q0, target, rot):
+    """Seconds of cdxh_ik_solve_frames on one core, and its status / iteration arrays."""
+    import numpy as np
+    from compliancedex_amd import _host, _native as N
+    from compliancedex_amd.ik import ik_params, joint_box
+    lib, p = _host.load(), _host.ptr
+    params = ik_params(*joint_box(rm.get_joint_limits()), max_iters=100)
+    desc = rm._descriptor(links, offsets)
+    q0, target, rot = (np.ascontiguousarray(t.cpu().numpy()) for t in (q0, target, rot))
+    E, T = q0.shape[0], len(links)
+    q, err, rerr = np.empty_like(q0), np.empty((E, T)), np.empty((E, T))
+    iters, status = np.empty(E, np.int32), np.empty(E, np.int32)
+    rot_mask = sum(1 << k for k, v in enumerate(oriented) if v)
+    dof_mask = sum(1 << d for d in solved)
+    t = time.perf_counter()
+    rc = lib.cdxh_ik_solve_frames(desc, params, E, p(q0), N.DTYPE_F64, p(target), p(rot), None, None, None, None, rot_mask,
+                                  dof_mask, p(q), p(err), p(rerr), p(iters), p(status), 0)
+    dt = time.perf_counter() - t
+    assert rc == 0
+    return dt, status, iters
+
+
+def run_frames(robot, E, args):
+    import numpy as np
+    import torch
+    from compliancedex_amd import DifferentiableRobotModel, solve_ik_frames
+    rm = DifferentiableRobotModel(robot, device="cuda")
+    links, offsets, oriented, solved, q0, target, rot, lo, hi = frames_case(rm, robot, E)
+    paths = {"frames_kernel": lambda: solve_ik_frames(rm, target, rot, links, offsets, q0=q0, oriented=oriented,
+                                                      joints=solved),
+             "frames_torch": lambda: torch_ik_frames(rm, links, offsets, oriented, solved, q0, target, rot, lo, hi)}
+    for f in paths.values():
+        f()
+    torch.cuda.synchronize()
+    ms = {n: [] for n in paths}
+    for _ in range(args.reps):
+        for n, f in paths.items():
+            ms[n].append(event_ms(f)[0])
+    rec = {"shape": "frames", "robot": robot, "E": E, "D": rm._n_dofs, "T": len(links), "oriented": sum(oriented),
+           "solved_joints": len(solved), **{n: stats(v) for n, v in ms.items()}}
+    res = paths["frames_kernel"]()
+    tq, terr, titers = paths["frames_torch"]()
+    rec["frames_kernel_converged"] = round(float((res.status == 0).double().mean()), 5)
+    rec["frames_kernel_all_iters_share"] = round(float((res.status == 1).double().mean()), 5)
+    rec["frames_kernel_iters_median_max"] = [int(res.iters.median()), int(res.iters.max())]
+    rec["frames_torch_converged"] = round(float((terr <= 1e-5).double().mean()), 5)
+    rec["frames_torch_iters_median_max"] = [int(titers.median()), int(titers.max())]
+    rec["frames_torch_q_max_abs_diff"] = float((tq.double() - res.q).abs().max())
+    rec["frames_torch_over_kernel"] = round(rec["frames_torch"]["median_ms"] / rec["frames_kernel"]["median_ms"], 1)
+    if E <= args.host_rows:
+        sec, hstatus, hiters = host_frames_seconds(rm, links, offsets, oriented, solved, q0, target, rot)
+        rec["frames_host_one_core_ms"] = round(sec * 1e3, 2)
+        rec["frames_host_converged"] = round(float((hstatus == 0).mean()), 5)
+        rec["frames_host_iters_median_max"] = [int(np.median(hiters)), int(hiters.max())]
+        rec["frames_host_over_kernel"] = round(sec * 1e3 / rec["frames_kernel"]["median_ms"], 1)
+    rec["device"] = torch.cuda.get_device_name(0)
+    return rec
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=7)
     ap.add_argument("--rows", default="4096,16384,65536")
     ap.add_argument("--robots", default="allegro,iiwa7_allegro")
     ap.add_argument("--robot", default=None, help="child mode: one shape in this process (with --rows one size)")
+    ap.add_argument("--shapes", default="fingertips,frames", help="driver: the shapes to run")
+    ap.add_argument("--shape", default="fingertips", help="child mode: fingertips (the two position solves) or frames")
     ap.add_argument("--host-rows", type=int, default=65536)
     ap.add_argument("--step-seconds", type=int, default=150, help="time limit of each shape's process")
     ap.add_argument("--out", default=os.path.join(REPO, "profiles", "ik.jsonl"))
     args = ap.parse_args()
     rows = [int(v) for v in args.rows.split(",")]
     if args.robot is None:
-        for robot in args.robots.split(","):
-            for E in rows:
-                cmd = ["timeout", "-k", "10", str(args.step_seconds), sys.executable, os.path.abspath(__file__), "--robot",
-                       robot, "--rows", str(E), "--reps", str(args.reps), "--host-rows", str(args.host_rows), "--out",
-                       args.out]
-                rc = subprocess.run(cmd).returncode
-                if rc != 0:
-                    raise SystemExit(f"{robot} E={E} ended with status {rc}: nothing more is started")
+        for shape in args.shapes.split(","):
+            for robot in args.robots.split(","):
+                for E in rows:
+                    cmd = ["timeout", "-k", "10", str(args.step_seconds), sys.executable, os.path.abspath(__file__),
+                           "--robot", robot, "--shape", shape, "--rows", str(E), "--reps", str(args.reps), "--host-rows",
+                           str(args.host_rows), "--out", args.out]
+                    rc = subprocess.run(cmd).returncode
+                    if rc != 0:
+                        raise SystemExit(f"{shape} {robot} E={E} ended with status {rc}: nothing more is started")
         return
     import torch
     if not torch.cuda.is_available():
@@ -314,7 +459,7 @@ def main():
     from compliancedex_amd import _native
     _native.load()
     os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-    rec = run_shape(args.robot, rows[0], args)
+    rec = (run_frames if args.shape == "frames" else run_shape)(args.robot, rows[0], args)
     line = json.dumps(rec)
     print(line, flush=True)
     with open(args.out, "a") as f:
