@@ -70,8 +70,7 @@
 //     Accepted as above (every pivot > 0 and cost(q′, Rp′, pp′) < cost): (q, Rp, pp) ← (q′, Rp′, pp′).  The μ schedule,
 //       the stop tests and the statuses are the fixed-palm ones.
 //   Outputs: q, palm_pos = pp, palm_rot = Rp, err (unweighted, at the returned q and pose), iters, status.
-//   Storage: IkMem of (T, D + 6): J has row stride D + 6, g has D + 6 entries (q / qn use their first D).  The pose and
-//   its trial copy (2 × 12 doubles) are indexed by constants only and live in registers.
+//   The pose and its trial copy (2 × 12 doubles) are indexed by constants only and live in registers.
 //
 // Pose targets and held joints (frame_ik_row).  The fixed-palm solve (ik_row) with two additions; whatever is not named
 //   here is ik_row's: the start, the bounds rounded inward, the μ schedule, the accept test on the true cost, the
@@ -102,11 +101,18 @@
 //     rest-pose sum of the cost and of g.
 //   With rot_mask = 0 and every joint in dof_mask the row is ik_row's bit for bit.
 //   Outputs: q, err, rot_err [T] (the chord; 0 for a tip outside rot_mask), iters, status.
-//   Storage: IkFrameMem — IkMem over M rows, the target quaternions [4·popcount] and the row weights [M].
 //
-// Storage.  Every per-row array (IkMem) is addressed as base[i·s]: s = 1 on the host, and on the device the arrays of
-// the lanes of a workgroup are interleaved in LDS (s = lanes, base shifted by the lane), so no array indexed at run time
-// lives in registers (it would go to scratch).
+// One loop.  The three solves are ik_lm_row<V>, written once; a variant V (IkFixed, IkPose, IkFrames) is two
+// compile-time flags, and everything stated above as a variant's own sits behind `if constexpr (V::pose)` or
+// `if constexpr (V::frames)` there and in ik_eval<V>.  ik_row, ik_pose_row and frame_ik_row name their inputs and call it.
+//
+// Storage.  One layout (ik_mem_at<V>) over n rows and Dc columns: n = 3T and Dc = D for the fixed palm, Dc = D + 6 for
+// the free wrist, n = M for pose targets.  Doubles: A [n(n+1)/2] (lower triangle, row-major), g [Dc], y [n], dv [2n]
+// (the residuals of the current and of the trial point), then for pose targets only tq [4·popcount(rot_mask)] (the
+// target quaternions, xyzw) and rw [M] (the row weights).  Floats after all doubles: J [n·Dc] (row-major), q [Dc],
+// qn [Dc] (the free wrist uses their first D).  Every array is addressed as base[i·s]: s = 1 on the host, and on the
+// device the arrays of the lanes of a workgroup are interleaved in LDS (s = lanes, base shifted by the lane), so no
+// array indexed at run time lives in registers (it would go to scratch).
 #pragma once
 #include "cdx_cost.h"
 
@@ -178,33 +184,63 @@ CDX_HD void fk_jacobian_tip(const cdx_chain& c, int k, const Q& q, float* lin, f
   });
 }
 
-// Per-row storage of the solve, element i at base[i·s].
+
+// The variants of the solve (see "One loop" above).
+struct IkFixed {
+  static constexpr bool pose = false, frames = false;
+};
+struct IkPose {
+  static constexpr bool pose = true, frames = false;
+};
+struct IkFrames {
+  static constexpr bool pose = false, frames = true;
+};
+template <class V>
+CDX_HD int ik_rows(int T, uint32_t rot_mask) {
+  return 3 * T + (V::frames ? 3 * __builtin_popcount(rot_mask) : 0);
+}
+template <class V>
+CDX_HD int ik_cols(int D) {
+  return D + (V::pose ? 6 : 0);
+}
+
+// Per-row storage of the solve (see "Storage" above), element i at base[i·s].  tq and rw: pose targets only.
 struct IkMem {
-  double *A, *g, *y, *dv;  // A: n(n+1)/2 (lower triangle, row-major), g: D, y: n, dv: 2·n (two d buffers)
-  float *J, *q, *qn;       // J: n·D (row-major), q / qn: D
+  double *A, *g, *y, *dv, *tq, *rw;
+  float *J, *q, *qn;
   int s;
 };
-CDX_HD int ik_mem_doubles(int T, int D) { return (3 * T) * (3 * T + 1) / 2 + D + 3 * T + 6 * T; }
-CDX_HD int ik_mem_floats(int T, int D) { return 3 * T * D + 2 * D; }
-CDX_HD size_t ik_mem_bytes(int T, int D) { return (size_t)ik_mem_doubles(T, D) * 8 + (size_t)ik_mem_floats(T, D) * 4; }
-// The arrays of `lane` among `s` lanes in a block of ik_mem_bytes(T, D)·s bytes (8-byte aligned).
-CDX_HD IkMem ik_mem_at(void* base, int T, int D, int lane, int s) {
-  const int n = 3 * T;
+template <class V>
+CDX_HD int ik_mem_doubles(int n, int Dc, int R) {
+  return n * (n + 1) / 2 + Dc + n + 2 * n + (V::frames ? 4 * R + n : 0);
+}
+template <class V>
+CDX_HD size_t ik_mem_bytes(int T, int D, uint32_t rot_mask) {
+  const int n = ik_rows<V>(T, rot_mask), Dc = ik_cols<V>(D);
+  return (size_t)ik_mem_doubles<V>(n, Dc, __builtin_popcount(rot_mask)) * 8 + (size_t)(n * Dc + 2 * Dc) * 4;
+}
+// The arrays of `lane` among `s` lanes in a block of ik_mem_bytes<V>(T, D, rot_mask)·s bytes (8-byte aligned).
+template <class V>
+CDX_HD IkMem ik_mem_at(void* base, int T, int D, uint32_t rot_mask, int lane, int s) {
+  const int n = ik_rows<V>(T, rot_mask), Dc = ik_cols<V>(D), R = __builtin_popcount(rot_mask);
   IkMem m;
   double* d = (double*)base + lane;
   m.A = d;
   d += (size_t)(n * (n + 1) / 2) * s;
   m.g = d;
-  d += (size_t)D * s;
+  d += (size_t)Dc * s;
   m.y = d;
   d += (size_t)n * s;
   m.dv = d;
   d += (size_t)(2 * n) * s;
-  float* f = (float*)((double*)base + (size_t)ik_mem_doubles(T, D) * s) + lane;
+  m.tq = d;
+  d += (size_t)(V::frames ? 4 * R : 0) * s;
+  m.rw = d;
+  float* f = (float*)((double*)base + (size_t)ik_mem_doubles<V>(n, Dc, R) * s) + lane;
   m.J = f;
-  f += (size_t)(n * D) * s;
+  f += (size_t)(n * Dc) * s;
   m.q = f;
-  f += (size_t)D * s;
+  f += (size_t)Dc * s;
   m.qn = f;
   m.s = s;
   return m;
@@ -232,39 +268,83 @@ CDX_HD int ik_prepare(const cdx_ik_params* in, int D, cdx_ik_params* out) {
   return CDX_OK;
 }
 
-// The chain checks of the two entries: null → CDX_ECHAIN, sizes over the descriptor's → CDX_EINVAL, a malformed
-// tree or an over-deep tip → CDX_ECHAIN (chain_code, cdx_fk.h).
-CDX_HD int ik_chain_code(const cdx_chain* c) { return chain_code(c); }
+// One row's inputs and outputs, as stated at the top.  A variant reads only the fields named for it.
+struct IkRow {
+  Q0Row q0;
+  const double *target, *w;
+  double* err;
+  const double* palm;                    // fixed palm, pose targets
+  const double *palm0_pos, *palm0_rot;   // free wrist
+  double *palm_pos, *palm_rot;           //
+  const double *target_rot, *wr;         // pose targets
+  uint32_t rot_mask, dof_mask;           //
+  double* rot_err;                       //
+};
 
-// d = target − tip(q) into dv (stride s), cost(q) and emax.
-template <class Q>
-CDX_HD double ik_eval(const cdx_chain& c, const cdx_ik_params& p, const Q& q, const double* target, const double* w,
-                      const double* Rp, const double* pp, const double* po, double* dv, int s, double* emax) {
-  double ss = 0.0, em = 0.0;
-  for (int k = 0; k < c.n_tips; ++k) {
-    float pf[3];
-    fk_tip(c, k, q, pf, nullptr);
+// Whether joint d is solved: the dof_mask of pose targets, every joint otherwise.
+template <class V>
+CDX_HD bool ik_solved(const IkRow& r, int d) {
+  if constexpr (V::frames)
+    return (r.dof_mask >> d) & 1u;
+  else
+    return true;
+}
+
+// d = target − tip(q) into dv [0, 3T) (stride s), cost(q) and emax at the pose (Rp, pp).  Pose targets: also ρ_k of
+// the oriented tips into dv [3T, M) in mask order, against the target quaternions tq.
+template <class V, class Q>
+CDX_HD double ik_eval(const cdx_chain& c, const cdx_ik_params& p, const Q& q, const IkRow& r, const double* Rp,
+                      const double* pp, const double* po, const double* tq, double* dv, int s, double* emax) {
+  const int T = c.n_tips;
+  double ss = 0.0, sr = 0.0, em = 0.0;
+  int j = 0;
+  for (int k = 0; k < T; ++k) {
+    float pf[3], cf[4];
+    fk_tip(c, k, q, pf, V::frames ? cf : nullptr);
     const double v[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
     double x[3];
     mat3_vec(Rp, v, x);
-    const double wk = w ? w[k] : 1.0;
+    const double wk = r.w ? r.w[k] : 1.0;
     double d[3];
     for (int i = 0; i < 3; ++i) {
-      d[i] = target[3 * k + i] - ((x[i] + pp[i]) + po[i]);
+      d[i] = r.target[3 * k + i] - ((x[i] + pp[i]) + po[i]);
       dv[(size_t)(3 * k + i) * s] = d[i];
     }
     const double e = wk * sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
     em = e > em ? e : em;
-    const double r[3] = {wk * d[0], wk * d[1], wk * d[2]};
-    ss += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
+    const double rd[3] = {wk * d[0], wk * d[1], wk * d[2]};
+    ss += (rd[0] * rd[0] + rd[1] * rd[1]) + rd[2] * rd[2];
+    if constexpr (V::frames) {
+      if ((r.rot_mask >> k) & 1u) {
+        const double cx = (double)cf[0], cy = (double)cf[1], cz = (double)cf[2], cw = (double)cf[3];
+        const double nn = sqrt(((cx * cx + cy * cy) + cz * cz) + cw * cw);
+        const double ax = cx / nn, ay = cy / nn, az = cz / nn, aw = cw / nn;
+        const double tx = tq[(size_t)(4 * j) * s], ty = tq[(size_t)(4 * j + 1) * s], tz = tq[(size_t)(4 * j + 2) * s],
+                     tw = tq[(size_t)(4 * j + 3) * s];
+        const double ew = ((tw * aw + tx * ax) + ty * ay) + tz * az;
+        const double ex = (aw * tx - tw * ax) - (ty * az - tz * ay);
+        const double ey = (aw * ty - tw * ay) - (tz * ax - tx * az);
+        const double ez = (aw * tz - tw * az) - (tx * ay - ty * ax);
+        const double sg = ew < 0.0 ? -2.0 : 2.0;
+        const double ro[3] = {sg * ex, sg * ey, sg * ez};
+        for (int i = 0; i < 3; ++i) dv[(size_t)(3 * T + 3 * j + i) * s] = ro[i];
+        const double wrk = r.wr ? r.wr[k] : 0.1;
+        const double er = wrk * sqrt((ro[0] * ro[0] + ro[1] * ro[1]) + ro[2] * ro[2]);
+        em = er > em ? er : em;
+        const double rr[3] = {wrk * ro[0], wrk * ro[1], wrk * ro[2]};
+        sr += (rr[0] * rr[0] + rr[1] * rr[1]) + rr[2] * rr[2];
+        ++j;
+      }
+    }
   }
   double sq = 0.0;
   for (int d = 0; d < c.n_dofs; ++d) {
+    if (!ik_solved<V>(r, d)) continue;
     const double dq = (double)q[d] - p.ref_q[d];
     sq += dq * dq;
   }
   *emax = em;
-  return 0.5 * ss + (0.5 * p.rho) * sq;
+  return 0.5 * (V::frames ? ss + sr : ss) + (0.5 * p.rho) * sq;
 }
 
 // The damped system of one step over the first D columns of every row of m.J (row stride D): A = W·J·Jᵀ·W + κI and
@@ -330,110 +410,6 @@ CDX_HD bool ik_gram_solve(const IkMem& m, const RW& rw, int n, int D, double kap
   return pd;
 }
 
-// One row of the solve (p: after ik_prepare; po: 3 doubles).  Leaves the result in m.q, writes err [T] and *iters,
-// returns the status.  Status 2 leaves m untouched.
-CDX_HD int ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0, const double* target,
-                  const double* palm, const double* w, const IkMem& m, double* err, int32_t* iters) {
-  const int T = c.n_tips, D = c.n_dofs, n = 3 * T, s = m.s;
-  bool fin = true;
-  for (int d = 0; d < D; ++d) {
-    const double v = q0[d];
-    fin = fin && __builtin_isfinite(v) && __builtin_isfinite((float)v);
-  }
-  for (int i = 0; i < n; ++i) fin = fin && __builtin_isfinite(target[i]);
-  if (palm)
-    for (int i = 0; i < 6; ++i) fin = fin && __builtin_isfinite(palm[i]);
-  if (w)
-    for (int k = 0; k < T; ++k) fin = fin && __builtin_isfinite(w[k]);
-  *iters = 0;
-  if (!fin) {
-    for (int k = 0; k < T; ++k) err[k] = NAN;
-    return 2;
-  }
-  double Rp[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, pp[3] = {0.0, 0.0, 0.0};
-  if (palm) {
-    euler_xyz(palm + 3, Rp, nullptr, nullptr, nullptr);
-    for (int i = 0; i < 3; ++i) pp[i] = palm[i];
-  }
-  for (int d = 0; d < D; ++d) {
-    const float f = (float)q0[d], lo = (float)p.lower[d], hi = (float)p.upper[d];
-    m.q[(size_t)d * s] = f < lo ? lo : (f > hi ? hi : f);
-  }
-  const QStride q{m.q, s}, qn{m.qn, s};
-  int cur = 0;
-  double emax;
-  double cost = ik_eval(c, p, q, target, w, Rp, pp, po, m.dv, s, &emax);
-  double mu = p.mu0;
-  int it = 0, status;
-  for (;;) {
-    if (emax <= p.tol) { status = 0; break; }
-    if (it >= p.max_iters) { status = 1; break; }
-    ++it;
-    // Jl at q
-    CDX_IK_UNROLL
-    for (int i = 0; i < n * D; ++i) m.J[(size_t)i * s] = 0.f;
-    for (int k = 0; k < T; ++k) {
-      float pf[3];
-      fk_tip(c, k, q, pf, nullptr);
-      fk_tip_columns(c, k, q, pf, [&](int d, const float* l, const float*) {
-        for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * k + i) * D + d) * s] = l[i];
-      });
-    }
-    // u = w·Rpᵀ·(w·d) into y
-    const double* dc = m.dv + (size_t)(cur * n) * s;
-    for (int k = 0; k < T; ++k) {
-      const double wk = w ? w[k] : 1.0;
-      const double r[3] = {wk * dc[(size_t)(3 * k) * s], wk * dc[(size_t)(3 * k + 1) * s], wk * dc[(size_t)(3 * k + 2) * s]};
-      double u[3];
-      mat3t_vec(Rp, r, u);
-      for (int i = 0; i < 3; ++i) m.y[(size_t)(3 * k + i) * s] = wk * u[i];
-    }
-    // g, and the joints fixed on their bounds
-    for (int d = 0; d < D; ++d) {
-      double acc = 0.0;
-      CDX_IK_UNROLL
-      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * D + d) * s] * m.y[(size_t)a * s];
-      const double qd = (double)q[d];
-      double g = acc + p.rho * (p.ref_q[d] - qd);
-      if ((qd <= p.lower[d] && g < 0.0) || (qd >= p.upper[d] && g > 0.0)) {
-        g = 0.0;
-        for (int a = 0; a < n; ++a) m.J[(size_t)(a * D + d) * s] = 0.f;
-      }
-      m.g[(size_t)d * s] = g;
-    }
-    const double kappa = mu + p.rho;
-    const bool pd = ik_gram_solve(m, IkTipW{w}, n, D, kappa);
-    // the trial point
-    for (int d = 0; d < D; ++d) {
-      double acc = 0.0;
-      CDX_IK_UNROLL
-      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * D + d) * s] * m.y[(size_t)a * s];
-      const double v = (double)q[d] + (m.g[(size_t)d * s] - acc) / kappa;
-      m.qn[(size_t)d * s] = (float)(v < p.lower[d] ? p.lower[d] : (v > p.upper[d] ? p.upper[d] : v));
-    }
-    double emn;
-    const double cn = ik_eval(c, p, qn, target, w, Rp, pp, po, m.dv + (size_t)((1 - cur) * n) * s, s, &emn);
-    if (pd && cn < cost) {
-      for (int d = 0; d < D; ++d) m.q[(size_t)d * s] = m.qn[(size_t)d * s];
-      cur = 1 - cur;
-      cost = cn;
-      emax = emn;
-      mu = mu / p.nu;
-      mu = mu > p.mu_min ? mu : p.mu_min;
-    } else {
-      mu = mu * p.nu;
-      mu = mu < p.mu_max ? mu : p.mu_max;
-    }
-  }
-  const double* dc = m.dv + (size_t)(cur * n) * s;
-  for (int k = 0; k < T; ++k) {
-    const double d[3] = {dc[(size_t)(3 * k) * s], dc[(size_t)(3 * k + 1) * s], dc[(size_t)(3 * k + 2) * s]};
-    err[k] = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-  }
-  *iters = it;
-  return status;
-}
-
 // The Kabsch start of ik_pose_row (see above): v [3T] (stride s) holds double(FK_f32(q)_k).
 CDX_HD void ik_pose_start(int T, const double* v, int s, const double* target, const double* po, const double* w,
                           double* Rp, double* pp) {
@@ -480,205 +456,6 @@ CDX_HD void ik_pose_start(int T, const double* v, int s, const double* target, c
   for (int i = 0; i < 3; ++i) pp[i] = ct[i] - x[i];
 }
 
-// One row of the free-wrist solve (p: after ik_prepare; po: 3 doubles; m: IkMem of (T, D + 6)).  Leaves q in m.q,
-// writes palm_pos [3], palm_rot [9], err [T] and *iters, returns the status.  Status 2 leaves m untouched.
-CDX_HD int ik_pose_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0,
-                       const double* target, const double* palm0_pos, const double* palm0_rot, const double* w,
-                       const IkMem& m, double* palm_pos, double* palm_rot, double* err, int32_t* iters) {
-  const int T = c.n_tips, D = c.n_dofs, Dp = D + 6, n = 3 * T, s = m.s;
-  bool fin = true;
-  for (int d = 0; d < D; ++d) {
-    const double v = q0[d];
-    fin = fin && __builtin_isfinite(v) && __builtin_isfinite((float)v);
-  }
-  for (int i = 0; i < n; ++i) fin = fin && __builtin_isfinite(target[i]);
-  if (palm0_pos) {
-    for (int i = 0; i < 3; ++i) fin = fin && __builtin_isfinite(palm0_pos[i]);
-    for (int i = 0; i < 9; ++i) fin = fin && __builtin_isfinite(palm0_rot[i]);
-  }
-  if (w)
-    for (int k = 0; k < T; ++k) fin = fin && __builtin_isfinite(w[k]);
-  *iters = 0;
-  if (!fin) {
-    for (int k = 0; k < T; ++k) err[k] = NAN;
-    for (int i = 0; i < 3; ++i) palm_pos[i] = NAN;
-    for (int i = 0; i < 9; ++i) palm_rot[i] = NAN;
-    return 2;
-  }
-  for (int d = 0; d < D; ++d) {
-    const float f = (float)q0[d], lo = (float)p.lower[d], hi = (float)p.upper[d];
-    m.q[(size_t)d * s] = f < lo ? lo : (f > hi ? hi : f);
-  }
-  const QStride q{m.q, s}, qn{m.qn, s};
-  double Rp[9], pp[3], Rn[9], pn[3];
-  if (palm0_pos) {
-    for (int i = 0; i < 9; ++i) Rp[i] = palm0_rot[i];
-    for (int i = 0; i < 3; ++i) pp[i] = palm0_pos[i];
-  } else {
-    double* v = m.dv + (size_t)n * s;  // (the second residual buffer: free until the first trial point)
-    for (int k = 0; k < T; ++k) {
-      float pf[3];
-      fk_tip(c, k, q, pf, nullptr);
-      for (int i = 0; i < 3; ++i) v[(size_t)(3 * k + i) * s] = (double)pf[i];
-    }
-    ik_pose_start(T, v, s, target, po, w, Rp, pp);
-  }
-  int cur = 0;
-  double emax;
-  double cost = ik_eval(c, p, q, target, w, Rp, pp, po, m.dv, s, &emax);
-  double mu = p.mu0;
-  int it = 0, status;
-  for (;;) {
-    if (emax <= p.tol) { status = 0; break; }
-    if (it >= p.max_iters) { status = 1; break; }
-    ++it;
-    // Jl at q: the joint columns, then t_b and ω_b
-    CDX_IK_UNROLL
-    for (int i = 0; i < n * Dp; ++i) m.J[(size_t)i * s] = 0.f;
-    for (int k = 0; k < T; ++k) {
-      float pf[3];
-      fk_tip(c, k, q, pf, nullptr);
-      fk_tip_columns(c, k, q, pf, [&](int d, const float* l, const float*) {
-        for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * k + i) * Dp + d) * s] = l[i];
-      });
-      float* r0 = m.J + (size_t)((3 * k) * Dp + D) * s;
-      float* r1 = m.J + (size_t)((3 * k + 1) * Dp + D) * s;
-      float* r2 = m.J + (size_t)((3 * k + 2) * Dp + D) * s;
-      r0[0] = 1.f; r1[(size_t)1 * s] = 1.f; r2[(size_t)2 * s] = 1.f;
-      r0[(size_t)4 * s] = pf[2];  r0[(size_t)5 * s] = -pf[1];
-      r1[(size_t)3 * s] = -pf[2]; r1[(size_t)5 * s] = pf[0];
-      r2[(size_t)3 * s] = pf[1];  r2[(size_t)4 * s] = -pf[0];
-    }
-    // u = w·Rpᵀ·(w·d) into y
-    const double* dc = m.dv + (size_t)(cur * n) * s;
-    for (int k = 0; k < T; ++k) {
-      const double wk = w ? w[k] : 1.0;
-      const double r[3] = {wk * dc[(size_t)(3 * k) * s], wk * dc[(size_t)(3 * k + 1) * s], wk * dc[(size_t)(3 * k + 2) * s]};
-      double u[3];
-      mat3t_vec(Rp, r, u);
-      for (int i = 0; i < 3; ++i) m.y[(size_t)(3 * k + i) * s] = wk * u[i];
-    }
-    // g: the joints with their ρ term and bounds, the pose columns bare
-    for (int d = 0; d < Dp; ++d) {
-      double acc = 0.0;
-      CDX_IK_UNROLL
-      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * Dp + d) * s] * m.y[(size_t)a * s];
-      double g = acc;
-      if (d < D) {
-        const double qd = (double)q[d];
-        g = acc + p.rho * (p.ref_q[d] - qd);
-        if ((qd <= p.lower[d] && g < 0.0) || (qd >= p.upper[d] && g > 0.0)) {
-          g = 0.0;
-          for (int a = 0; a < n; ++a) m.J[(size_t)(a * Dp + d) * s] = 0.f;
-        }
-      }
-      m.g[(size_t)d * s] = g;
-    }
-    const double kappa = mu + p.rho;
-    const bool pd = ik_gram_solve(m, IkTipW{w}, n, Dp, kappa);
-    // the trial point
-    for (int d = 0; d < D; ++d) {
-      double acc = 0.0;
-      CDX_IK_UNROLL
-      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * Dp + d) * s] * m.y[(size_t)a * s];
-      const double v = (double)q[d] + (m.g[(size_t)d * s] - acc) / kappa;
-      m.qn[(size_t)d * s] = (float)(v < p.lower[d] ? p.lower[d] : (v > p.upper[d] ? p.upper[d] : v));
-    }
-    double st[6];
-#if defined(__HIPCC__)
-#pragma unroll
-#endif
-    for (int j = 0; j < 6; ++j) {
-      double acc = 0.0;
-      CDX_IK_UNROLL
-      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * Dp + D + j) * s] * m.y[(size_t)a * s];
-      st[j] = (m.g[(size_t)(D + j) * s] - acc) / kappa;
-    }
-    {
-      double x[3];
-      mat3_vec(Rp, st, x);
-      for (int i = 0; i < 3; ++i) pn[i] = pp[i] + x[i];
-      const double a[3] = {0.5 * st[3], 0.5 * st[4], 0.5 * st[5]};
-      const double ss = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], den = 1.0 + ss, one = 1.0 - ss;
-      const double C[9] = {(one + 2.0 * (a[0] * a[0])) / den,        (2.0 * (a[0] * a[1]) - 2.0 * a[2]) / den,
-                           (2.0 * (a[0] * a[2]) + 2.0 * a[1]) / den, (2.0 * (a[1] * a[0]) + 2.0 * a[2]) / den,
-                           (one + 2.0 * (a[1] * a[1])) / den,        (2.0 * (a[1] * a[2]) - 2.0 * a[0]) / den,
-                           (2.0 * (a[2] * a[0]) - 2.0 * a[1]) / den, (2.0 * (a[2] * a[1]) + 2.0 * a[0]) / den,
-                           (one + 2.0 * (a[2] * a[2])) / den};
-      mat3_mul(Rp, C, Rn);
-    }
-    double emn;
-    const double cn = ik_eval(c, p, qn, target, w, Rn, pn, po, m.dv + (size_t)((1 - cur) * n) * s, s, &emn);
-    if (pd && cn < cost) {
-      for (int d = 0; d < D; ++d) m.q[(size_t)d * s] = m.qn[(size_t)d * s];
-      for (int i = 0; i < 9; ++i) Rp[i] = Rn[i];
-      for (int i = 0; i < 3; ++i) pp[i] = pn[i];
-      cur = 1 - cur;
-      cost = cn;
-      emax = emn;
-      mu = mu / p.nu;
-      mu = mu > p.mu_min ? mu : p.mu_min;
-    } else {
-      mu = mu * p.nu;
-      mu = mu < p.mu_max ? mu : p.mu_max;
-    }
-  }
-  const double* dc = m.dv + (size_t)(cur * n) * s;
-  for (int k = 0; k < T; ++k) {
-    const double d[3] = {dc[(size_t)(3 * k) * s], dc[(size_t)(3 * k + 1) * s], dc[(size_t)(3 * k + 2) * s]};
-    err[k] = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-  }
-  for (int i = 0; i < 3; ++i) palm_pos[i] = pp[i];
-  for (int i = 0; i < 9; ++i) palm_rot[i] = Rp[i];
-  *iters = it;
-  return status;
-}
-
-// ---- pose targets and held joints (frame_ik_row, stated at the top of this file) ----
-
-// Per-row storage of frame_ik_row: IkMem over M = 3T + 3R packed rows (R = popcount(rot_mask)) for 3T, then
-// tq [4·R] (the oriented tips' target quaternions, xyzw) and rw [M] (the row weights), all at stride m.s.
-struct IkFrameMem {
-  IkMem m;
-  double *tq, *rw;
-};
-CDX_HD int ik_popcount(uint32_t v) {
-  int n = 0;
-  for (; v; v &= v - 1) ++n;
-  return n;
-}
-CDX_HD int ik_frames_rows(int T, uint32_t rot_mask) { return 3 * T + 3 * ik_popcount(rot_mask); }
-CDX_HD int ik_frames_doubles(int M, int D, int R) { return M * (M + 1) / 2 + D + M + 2 * M + 4 * R + M; }
-CDX_HD int ik_frames_floats(int M, int D) { return M * D + 2 * D; }
-CDX_HD size_t ik_frames_bytes(int T, int D, uint32_t rot_mask) {
-  const int M = ik_frames_rows(T, rot_mask);
-  return (size_t)ik_frames_doubles(M, D, ik_popcount(rot_mask)) * 8 + (size_t)ik_frames_floats(M, D) * 4;
-}
-CDX_HD IkFrameMem ik_frames_mem_at(void* base, int T, int D, uint32_t rot_mask, int lane, int s) {
-  const int R = ik_popcount(rot_mask), M = 3 * T + 3 * R;
-  IkFrameMem f;
-  double* d = (double*)base + lane;
-  f.m.A = d;
-  d += (size_t)(M * (M + 1) / 2) * s;
-  f.m.g = d;
-  d += (size_t)D * s;
-  f.m.y = d;
-  d += (size_t)M * s;
-  f.m.dv = d;
-  d += (size_t)(2 * M) * s;
-  f.tq = d;
-  d += (size_t)(4 * R) * s;
-  f.rw = d;
-  float* x = (float*)((double*)base + (size_t)ik_frames_doubles(M, D, R) * s) + lane;
-  f.m.J = x;
-  x += (size_t)(M * D) * s;
-  f.m.q = x;
-  x += (size_t)D * s;
-  f.m.qn = x;
-  f.m.s = s;
-  return f;
-}
-
 // The masks of a call: 0, or CDX_EINVAL for a rot_mask bit at or above T, a dof_mask with no bit below D or one at or
 // above D.
 CDX_HD int ik_frames_mask_code(int T, int D, uint64_t rot_mask, uint64_t dof_mask) {
@@ -713,192 +490,211 @@ CDX_HD void shepperd_quat(double r00, double r01, double r02, double r10, double
   w = br < 0 ? h : (br == 0 ? a0 : (br == 1 ? a1 : a2));
 }
 
-// ik_eval with the orientation rows: d into dv [0, 3T), ρ_k of the oriented tips into dv [3T, M) in mask order; the
-// cost and emax of frame_ik_row.
-template <class Q>
-CDX_HD double ik_frames_eval(const cdx_chain& c, const cdx_ik_params& p, const Q& q, const double* target,
-                             const double* w, const double* wr, uint32_t rot_mask, uint32_t dof_mask, const double* Rp,
-                             const double* pp, const double* po, const double* tq, double* dv, int s, double* emax) {
-  const int T = c.n_tips;
-  double ss = 0.0, sr = 0.0, em = 0.0;
-  int j = 0;
-  for (int k = 0; k < T; ++k) {
-    float pf[3], cf[4];
-    fk_tip(c, k, q, pf, cf);
-    const double v[3] = {(double)pf[0], (double)pf[1], (double)pf[2]};
-    double x[3];
-    mat3_vec(Rp, v, x);
-    const double wk = w ? w[k] : 1.0;
-    double d[3];
-    for (int i = 0; i < 3; ++i) {
-      d[i] = target[3 * k + i] - ((x[i] + pp[i]) + po[i]);
-      dv[(size_t)(3 * k + i) * s] = d[i];
-    }
-    const double e = wk * sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-    em = e > em ? e : em;
-    const double r[3] = {wk * d[0], wk * d[1], wk * d[2]};
-    ss += (r[0] * r[0] + r[1] * r[1]) + r[2] * r[2];
-    if ((rot_mask >> k) & 1u) {
-      const double cx = (double)cf[0], cy = (double)cf[1], cz = (double)cf[2], cw = (double)cf[3];
-      const double nn = sqrt(((cx * cx + cy * cy) + cz * cz) + cw * cw);
-      const double ax = cx / nn, ay = cy / nn, az = cz / nn, aw = cw / nn;
-      const double tx = tq[(size_t)(4 * j) * s], ty = tq[(size_t)(4 * j + 1) * s], tz = tq[(size_t)(4 * j + 2) * s],
-                   tw = tq[(size_t)(4 * j + 3) * s];
-      const double ew = ((tw * aw + tx * ax) + ty * ay) + tz * az;
-      const double ex = (aw * tx - tw * ax) - (ty * az - tz * ay);
-      const double ey = (aw * ty - tw * ay) - (tz * ax - tx * az);
-      const double ez = (aw * tz - tw * az) - (tx * ay - ty * ax);
-      const double sg = ew < 0.0 ? -2.0 : 2.0;
-      const double ro[3] = {sg * ex, sg * ey, sg * ez};
-      for (int i = 0; i < 3; ++i) dv[(size_t)(3 * T + 3 * j + i) * s] = ro[i];
-      const double wrk = wr ? wr[k] : 0.1;
-      const double er = wrk * sqrt((ro[0] * ro[0] + ro[1] * ro[1]) + ro[2] * ro[2]);
-      em = er > em ? er : em;
-      const double rr[3] = {wrk * ro[0], wrk * ro[1], wrk * ro[2]};
-      sr += (rr[0] * rr[0] + rr[1] * rr[1]) + rr[2] * rr[2];
-      ++j;
-    }
-  }
-  double sq = 0.0;
-  for (int d = 0; d < c.n_dofs; ++d) {
-    if (!((dof_mask >> d) & 1u)) continue;
-    const double dq = (double)q[d] - p.ref_q[d];
-    sq += dq * dq;
-  }
-  *emax = em;
-  return 0.5 * (ss + sr) + (0.5 * p.rho) * sq;
+// The free wrist's trial pose (Rn, pn) from (Rp, pp) and the step st = (t_b, ω_b): see "Trial point" at the top.
+CDX_HD void ik_pose_trial(const double* Rp, const double* pp, const double* st, double* Rn, double* pn) {
+  double x[3];
+  mat3_vec(Rp, st, x);
+  for (int i = 0; i < 3; ++i) pn[i] = pp[i] + x[i];
+  const double a[3] = {0.5 * st[3], 0.5 * st[4], 0.5 * st[5]};
+  const double ss = (a[0] * a[0] + a[1] * a[1]) + a[2] * a[2], den = 1.0 + ss, one = 1.0 - ss;
+  const double C[9] = {(one + 2.0 * (a[0] * a[0])) / den,        (2.0 * (a[0] * a[1]) - 2.0 * a[2]) / den,
+                       (2.0 * (a[0] * a[2]) + 2.0 * a[1]) / den, (2.0 * (a[1] * a[0]) + 2.0 * a[2]) / den,
+                       (one + 2.0 * (a[1] * a[1])) / den,        (2.0 * (a[1] * a[2]) - 2.0 * a[0]) / den,
+                       (2.0 * (a[2] * a[0]) - 2.0 * a[1]) / den, (2.0 * (a[2] * a[1]) + 2.0 * a[0]) / den,
+                       (one + 2.0 * (a[2] * a[2])) / den};
+  mat3_mul(Rp, C, Rn);
 }
 
-// One row of the pose-target solve (p: after ik_prepare; po: 3 doubles; the masks: after ik_frames_mask_code; f:
-// ik_frames_mem_at of (T, D, rot_mask)).  target_rot may be null where rot_mask is 0.  Leaves q in f.m.q, writes err [T],
-// rot_err [T] (0 for a tip outside rot_mask) and *iters, returns the status.  Status 2 leaves f untouched.
-CDX_HD int frame_ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0,
-                        const double* target, const double* target_rot, const double* palm, const double* w,
-                        const double* wr, uint32_t rot_mask, uint32_t dof_mask, const IkFrameMem& f, double* err,
-                        double* rot_err, int32_t* iters) {
-  const IkMem& m = f.m;
-  const int T = c.n_tips, D = c.n_dofs, n = ik_frames_rows(T, rot_mask), s = m.s;
+// One row of the solve of variant V (p: after ik_prepare; po: 3 doubles; the masks: after ik_frames_mask_code;
+// m: ik_mem_at<V>).  Leaves the result in m.q, writes the variant's outputs and *iters, returns the status.  Status 2
+// leaves m untouched.
+template <class V>
+CDX_HD int ik_lm_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const IkRow& r, const IkMem& m,
+                     int32_t* iters) {
+  const int T = c.n_tips, D = c.n_dofs, Dc = ik_cols<V>(D), n = ik_rows<V>(T, r.rot_mask), s = m.s;
+  const double* w = r.w;
   bool fin = true;
   for (int d = 0; d < D; ++d) {
-    const double v = q0[d];
+    const double v = r.q0[d];
     fin = fin && __builtin_isfinite(v) && __builtin_isfinite((float)v);
   }
-  for (int i = 0; i < 3 * T; ++i) fin = fin && __builtin_isfinite(target[i]);
-  if (palm)
-    for (int i = 0; i < 6; ++i) fin = fin && __builtin_isfinite(palm[i]);
+  for (int i = 0; i < 3 * T; ++i) fin = fin && __builtin_isfinite(r.target[i]);
   if (w)
     for (int k = 0; k < T; ++k) fin = fin && __builtin_isfinite(w[k]);
-  if (target_rot)
-    for (int i = 0; i < 9 * T; ++i) fin = fin && __builtin_isfinite(target_rot[i]);
-  if (wr)
-    for (int k = 0; k < T; ++k) fin = fin && __builtin_isfinite(wr[k]);
+  if constexpr (V::pose) {
+    if (r.palm0_pos) {
+      for (int i = 0; i < 3; ++i) fin = fin && __builtin_isfinite(r.palm0_pos[i]);
+      for (int i = 0; i < 9; ++i) fin = fin && __builtin_isfinite(r.palm0_rot[i]);
+    }
+  } else {
+    if (r.palm)
+      for (int i = 0; i < 6; ++i) fin = fin && __builtin_isfinite(r.palm[i]);
+  }
+  if constexpr (V::frames) {
+    if (r.target_rot)
+      for (int i = 0; i < 9 * T; ++i) fin = fin && __builtin_isfinite(r.target_rot[i]);
+    if (r.wr)
+      for (int k = 0; k < T; ++k) fin = fin && __builtin_isfinite(r.wr[k]);
+  }
   *iters = 0;
   if (!fin) {
-    for (int k = 0; k < T; ++k) err[k] = rot_err[k] = NAN;
+    for (int k = 0; k < T; ++k) r.err[k] = NAN;
+    if constexpr (V::pose) {
+      for (int i = 0; i < 3; ++i) r.palm_pos[i] = NAN;
+      for (int i = 0; i < 9; ++i) r.palm_rot[i] = NAN;
+    }
+    if constexpr (V::frames)
+      for (int k = 0; k < T; ++k) r.rot_err[k] = NAN;
     return 2;
   }
-  double Rp[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, pp[3] = {0.0, 0.0, 0.0};
-  if (palm) {
-    euler_xyz(palm + 3, Rp, nullptr, nullptr, nullptr);
-    for (int i = 0; i < 3; ++i) pp[i] = palm[i];
+  for (int d = 0; d < D; ++d) {
+    const float f = (float)r.q0[d], lo = (float)p.lower[d], hi = (float)p.upper[d];
+    m.q[(size_t)d * s] = f < lo ? lo : (f > hi ? hi : f);
   }
-  // the target quaternions and the row weights, once
-  {
+  const QStride q{m.q, s}, qn{m.qn, s};
+  // the pose: given, or the free wrist's start; Rn / pn: the free wrist's trial copy
+  double Rp[9] = {1.0, 0.0, 0.0, 0.0, 1.0, 0.0, 0.0, 0.0, 1.0}, pp[3] = {0.0, 0.0, 0.0}, Rn[9], pn[3];
+  if constexpr (V::pose) {
+    if (r.palm0_pos) {
+      for (int i = 0; i < 9; ++i) Rp[i] = r.palm0_rot[i];
+      for (int i = 0; i < 3; ++i) pp[i] = r.palm0_pos[i];
+    } else {
+      double* v = m.dv + (size_t)n * s;  // (the second residual buffer: free until the first trial point)
+      for (int k = 0; k < T; ++k) {
+        float pf[3];
+        fk_tip(c, k, q, pf, nullptr);
+        for (int i = 0; i < 3; ++i) v[(size_t)(3 * k + i) * s] = (double)pf[i];
+      }
+      ik_pose_start(T, v, s, r.target, po, w, Rp, pp);
+    }
+  } else {
+    if (r.palm) {
+      euler_xyz(r.palm + 3, Rp, nullptr, nullptr, nullptr);
+      for (int i = 0; i < 3; ++i) pp[i] = r.palm[i];
+    }
+  }
+  // pose targets: the target quaternions and the row weights, once
+  if constexpr (V::frames) {
     int j = 0;
     for (int k = 0; k < T; ++k) {
       const double wk = w ? w[k] : 1.0;
-      for (int i = 0; i < 3; ++i) f.rw[(size_t)(3 * k + i) * s] = wk;
-      if ((rot_mask >> k) & 1u) {
+      for (int i = 0; i < 3; ++i) m.rw[(size_t)(3 * k + i) * s] = wk;
+      if ((r.rot_mask >> k) & 1u) {
         // (Rpᵀ·Rt entry by entry, indexed by constants only: the matrix stays in registers)
-        const double* B = target_rot + 9 * k;
+        const double* B = r.target_rot + 9 * k;
         auto el = [&](int i, int c3) { return (Rp[i] * B[c3] + Rp[3 + i] * B[3 + c3]) + Rp[6 + i] * B[6 + c3]; };
         double t[4];
         shepperd_quat(el(0, 0), el(0, 1), el(0, 2), el(1, 0), el(1, 1), el(1, 2), el(2, 0), el(2, 1), el(2, 2), t[0], t[1],
                       t[2], t[3]);
-        const double wrk = wr ? wr[k] : 0.1;
-        f.tq[(size_t)(4 * j) * s] = t[0];
-        f.tq[(size_t)(4 * j + 1) * s] = t[1];
-        f.tq[(size_t)(4 * j + 2) * s] = t[2];
-        f.tq[(size_t)(4 * j + 3) * s] = t[3];
-        for (int i = 0; i < 3; ++i) f.rw[(size_t)(3 * T + 3 * j + i) * s] = wrk;
+        const double wrk = r.wr ? r.wr[k] : 0.1;
+        m.tq[(size_t)(4 * j) * s] = t[0];
+        m.tq[(size_t)(4 * j + 1) * s] = t[1];
+        m.tq[(size_t)(4 * j + 2) * s] = t[2];
+        m.tq[(size_t)(4 * j + 3) * s] = t[3];
+        for (int i = 0; i < 3; ++i) m.rw[(size_t)(3 * T + 3 * j + i) * s] = wrk;
         ++j;
       }
     }
   }
-  for (int d = 0; d < D; ++d) {
-    const float v = (float)q0[d], lo = (float)p.lower[d], hi = (float)p.upper[d];
-    m.q[(size_t)d * s] = v < lo ? lo : (v > hi ? hi : v);
-  }
-  const QStride q{m.q, s}, qn{m.qn, s};
-  const IkRowW rw{f.rw, s};
   int cur = 0;
   double emax;
-  double cost = ik_frames_eval(c, p, q, target, w, wr, rot_mask, dof_mask, Rp, pp, po, f.tq, m.dv, s, &emax);
+  double cost = ik_eval<V>(c, p, q, r, Rp, pp, po, m.tq, m.dv, s, &emax);
   double mu = p.mu0;
   int it = 0, status;
   for (;;) {
     if (emax <= p.tol) { status = 0; break; }
     if (it >= p.max_iters) { status = 1; break; }
     ++it;
-    // Jl at q: lin of every tip, then ang of the oriented tips
+    // Jl at q: lin of every tip; the free wrist's t_b and ω_b columns; ang of the oriented tips
     CDX_IK_UNROLL
-    for (int i = 0; i < n * D; ++i) m.J[(size_t)i * s] = 0.f;
-    {
-      int j = 0;
-      for (int k = 0; k < T; ++k) {
-        const bool rot = (rot_mask >> k) & 1u;
-        float pf[3];
-        fk_tip(c, k, q, pf, nullptr);
-        fk_tip_columns(c, k, q, pf, [&](int d, const float* l, const float* a) {
-          for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * k + i) * D + d) * s] = l[i];
-          if (rot)
-            for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * T + 3 * j + i) * D + d) * s] = a[i];
-        });
-        j += rot ? 1 : 0;
+    for (int i = 0; i < n * Dc; ++i) m.J[(size_t)i * s] = 0.f;
+    for (int k = 0, j = 0; k < T; ++k) {
+      const bool rot = V::frames && ((r.rot_mask >> k) & 1u);
+      float pf[3];
+      fk_tip(c, k, q, pf, nullptr);
+      fk_tip_columns(c, k, q, pf, [&](int d, const float* l, const float* a) {
+        for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * k + i) * Dc + d) * s] = l[i];
+        if (rot)
+          for (int i = 0; i < 3; ++i) m.J[(size_t)((3 * T + 3 * j + i) * Dc + d) * s] = a[i];
+      });
+      if constexpr (V::pose) {
+        float* r0 = m.J + (size_t)((3 * k) * Dc + D) * s;
+        float* r1 = m.J + (size_t)((3 * k + 1) * Dc + D) * s;
+        float* r2 = m.J + (size_t)((3 * k + 2) * Dc + D) * s;
+        r0[0] = 1.f; r1[(size_t)1 * s] = 1.f; r2[(size_t)2 * s] = 1.f;
+        r0[(size_t)4 * s] = pf[2];  r0[(size_t)5 * s] = -pf[1];
+        r1[(size_t)3 * s] = -pf[2]; r1[(size_t)5 * s] = pf[0];
+        r2[(size_t)3 * s] = pf[1];  r2[(size_t)4 * s] = -pf[0];
       }
+      j += rot ? 1 : 0;
     }
-    // u = w·Rpᵀ·(w·d) of the position rows and wr·(wr·ρ) of the orientation rows into y
+    // u = w·Rpᵀ·(w·d) of the position rows, and wr·(wr·ρ) of the orientation rows, into y
     const double* dc = m.dv + (size_t)(cur * n) * s;
     for (int k = 0; k < T; ++k) {
       const double wk = w ? w[k] : 1.0;
-      const double r[3] = {wk * dc[(size_t)(3 * k) * s], wk * dc[(size_t)(3 * k + 1) * s], wk * dc[(size_t)(3 * k + 2) * s]};
+      const double rd[3] = {wk * dc[(size_t)(3 * k) * s], wk * dc[(size_t)(3 * k + 1) * s], wk * dc[(size_t)(3 * k + 2) * s]};
       double u[3];
-      mat3t_vec(Rp, r, u);
+      mat3t_vec(Rp, rd, u);
       for (int i = 0; i < 3; ++i) m.y[(size_t)(3 * k + i) * s] = wk * u[i];
     }
-    for (int a = 3 * T; a < n; ++a) {
-      const double wa = rw(a);
-      m.y[(size_t)a * s] = wa * (wa * dc[(size_t)a * s]);
-    }
-    // g, the held joints, and the joints fixed on their bounds
-    for (int d = 0; d < D; ++d) {
+    if constexpr (V::frames)
+      for (int a = 3 * T; a < n; ++a) {
+        const double wa = m.rw[(size_t)a * s];
+        m.y[(size_t)a * s] = wa * (wa * dc[(size_t)a * s]);
+      }
+    // g: the joints with their ρ term, held or fixed on their bounds; the free wrist's pose columns bare
+    for (int d = 0; d < Dc; ++d) {
       double acc = 0.0;
       CDX_IK_UNROLL
-      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * D + d) * s] * m.y[(size_t)a * s];
-      const double qd = (double)q[d];
-      double g = acc + p.rho * (p.ref_q[d] - qd);
-      if (!((dof_mask >> d) & 1u) || (qd <= p.lower[d] && g < 0.0) || (qd >= p.upper[d] && g > 0.0)) {
-        g = 0.0;
-        for (int a = 0; a < n; ++a) m.J[(size_t)(a * D + d) * s] = 0.f;
+      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * Dc + d) * s] * m.y[(size_t)a * s];
+      double g = acc;
+      if (d < D) {
+        const double qd = (double)q[d];
+        g = acc + p.rho * (p.ref_q[d] - qd);
+        if (!ik_solved<V>(r, d) || (qd <= p.lower[d] && g < 0.0) || (qd >= p.upper[d] && g > 0.0)) {
+          g = 0.0;
+          for (int a = 0; a < n; ++a) m.J[(size_t)(a * Dc + d) * s] = 0.f;
+        }
       }
       m.g[(size_t)d * s] = g;
     }
     const double kappa = mu + p.rho;
-    const bool pd = ik_gram_solve(m, rw, n, D, kappa);
+    bool pd;
+    if constexpr (V::frames)
+      pd = ik_gram_solve(m, IkRowW{m.rw, s}, n, Dc, kappa);
+    else
+      pd = ik_gram_solve(m, IkTipW{w}, n, Dc, kappa);
     // the trial point
     for (int d = 0; d < D; ++d) {
       double acc = 0.0;
       CDX_IK_UNROLL
-      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * D + d) * s] * m.y[(size_t)a * s];
+      for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * Dc + d) * s] * m.y[(size_t)a * s];
       const double v = (double)q[d] + (m.g[(size_t)d * s] - acc) / kappa;
       const float vn = (float)(v < p.lower[d] ? p.lower[d] : (v > p.upper[d] ? p.upper[d] : v));
-      m.qn[(size_t)d * s] = ((dof_mask >> d) & 1u) ? vn : m.q[(size_t)d * s];
+      m.qn[(size_t)d * s] = ik_solved<V>(r, d) ? vn : m.q[(size_t)d * s];
+    }
+    if constexpr (V::pose) {
+      double st[6];
+#if defined(__HIPCC__)
+#pragma unroll
+#endif
+      for (int j = 0; j < 6; ++j) {
+        double acc = 0.0;
+        CDX_IK_UNROLL
+        for (int a = 0; a < n; ++a) acc += (double)m.J[(size_t)(a * Dc + D + j) * s] * m.y[(size_t)a * s];
+        st[j] = (m.g[(size_t)(D + j) * s] - acc) / kappa;
+      }
+      ik_pose_trial(Rp, pp, st, Rn, pn);
     }
     double emn;
-    const double cn = ik_frames_eval(c, p, qn, target, w, wr, rot_mask, dof_mask, Rp, pp, po, f.tq,
-                                     m.dv + (size_t)((1 - cur) * n) * s, s, &emn);
+    const double cn = ik_eval<V>(c, p, qn, r, V::pose ? Rn : Rp, V::pose ? pn : pp, po, m.tq,
+                                 m.dv + (size_t)((1 - cur) * n) * s, s, &emn);
     if (pd && cn < cost) {
       for (int d = 0; d < D; ++d) m.q[(size_t)d * s] = m.qn[(size_t)d * s];
+      if constexpr (V::pose) {
+        for (int i = 0; i < 9; ++i) Rp[i] = Rn[i];
+        for (int i = 0; i < 3; ++i) pp[i] = pn[i];
+      }
       cur = 1 - cur;
       cost = cn;
       emax = emn;
@@ -910,22 +706,84 @@ CDX_HD int frame_ik_row(const cdx_chain& c, const cdx_ik_params& p, const double
     }
   }
   const double* dc = m.dv + (size_t)(cur * n) * s;
-  {
-    int j = 0;
-    for (int k = 0; k < T; ++k) {
-      const double d[3] = {dc[(size_t)(3 * k) * s], dc[(size_t)(3 * k + 1) * s], dc[(size_t)(3 * k + 2) * s]};
-      err[k] = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
-      rot_err[k] = 0.0;
-      if ((rot_mask >> k) & 1u) {
+  for (int k = 0, j = 0; k < T; ++k) {
+    const double d[3] = {dc[(size_t)(3 * k) * s], dc[(size_t)(3 * k + 1) * s], dc[(size_t)(3 * k + 2) * s]};
+    r.err[k] = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+    if constexpr (V::frames) {
+      r.rot_err[k] = 0.0;
+      if ((r.rot_mask >> k) & 1u) {
         const double* ro = dc + (size_t)(3 * T + 3 * j) * s;
         const double a = ro[0], b = ro[(size_t)s], cc = ro[(size_t)2 * s];
-        rot_err[k] = sqrt((a * a + b * b) + cc * cc);
+        r.rot_err[k] = sqrt((a * a + b * b) + cc * cc);
         ++j;
       }
     }
   }
+  if constexpr (V::pose) {
+    for (int i = 0; i < 3; ++i) r.palm_pos[i] = pp[i];
+    for (int i = 0; i < 9; ++i) r.palm_rot[i] = Rp[i];
+  }
   *iters = it;
   return status;
+}
+
+// The three solves: what each takes and writes (null as stated at the top).
+CDX_HD int ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0, const double* target,
+                  const double* palm, const double* w, const IkMem& m, double* err, int32_t* iters) {
+  IkRow r{};
+  r.q0 = q0, r.target = target, r.w = w, r.err = err, r.palm = palm;
+  return ik_lm_row<IkFixed>(c, p, po, r, m, iters);
+}
+CDX_HD int ik_pose_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0,
+                       const double* target, const double* palm0_pos, const double* palm0_rot, const double* w,
+                       const IkMem& m, double* palm_pos, double* palm_rot, double* err, int32_t* iters) {
+  IkRow r{};
+  r.q0 = q0, r.target = target, r.w = w, r.err = err;
+  r.palm0_pos = palm0_pos, r.palm0_rot = palm0_rot, r.palm_pos = palm_pos, r.palm_rot = palm_rot;
+  return ik_lm_row<IkPose>(c, p, po, r, m, iters);
+}
+CDX_HD int frame_ik_row(const cdx_chain& c, const cdx_ik_params& p, const double* po, const Q0Row& q0,
+                        const double* target, const double* target_rot, const double* palm, const double* w,
+                        const double* wr, uint32_t rot_mask, uint32_t dof_mask, const IkMem& m, double* err,
+                        double* rot_err, int32_t* iters) {
+  IkRow r{};
+  r.q0 = q0, r.target = target, r.w = w, r.err = err, r.palm = palm;
+  r.target_rot = target_rot, r.wr = wr, r.rot_mask = rot_mask, r.dof_mask = dof_mask, r.rot_err = rot_err;
+  return ik_lm_row<IkFrames>(c, p, po, r, m, iters);
+}
+
+// What every entry of the solves checks first, device and host, in this order: the chain (chain_code, cdx_fk.h: null →
+// CDX_ECHAIN, sizes over the descriptor's → CDX_EINVAL, a malformed tree or an over-deep tip → CDX_ECHAIN), the
+// parameters (ik_prepare, into *p), then E and q_dtype.
+CDX_HD int ik_call_code(const cdx_chain* c, const cdx_ik_params* params, int64_t E, int32_t q_dtype, cdx_ik_params* p) {
+  int rc = chain_code(c);
+  if (rc) return rc;
+  rc = ik_prepare(params, c->n_dofs, p);
+  if (rc) return rc;
+  if (E < 0 || (q_dtype != CDX_DTYPE_F32 && q_dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
+  return CDX_OK;
+}
+
+// po [3] = palm_offset, or 0 for null; CDX_EINVAL for a non-finite entry.
+CDX_HD int ik_offset_code(const double* palm_offset, double* po) {
+  for (int i = 0; i < 3; ++i) {
+    po[i] = palm_offset ? palm_offset[i] : 0.0;
+    if (!__builtin_isfinite(po[i])) return CDX_EINVAL;
+  }
+  return CDX_OK;
+}
+
+// Row e of the batch's q0 [E][D], and of its q: m.q, or q0 as it was given for a status-2 row.
+CDX_HD Q0Row ik_q0_row(const void* q0, int f64, int64_t e, int D) {
+  return Q0Row{f64 ? (const void*)((const double*)q0 + e * D) : (const void*)((const float*)q0 + e * D), f64};
+}
+CDX_HD void ik_store_q(void* q, const void* q0, int f64, int64_t e, int D, int st, const IkMem& m) {
+  for (int d = 0; d < D; ++d) {
+    if (f64)
+      ((double*)q)[e * D + d] = st == 2 ? ((const double*)q0)[e * D + d] : (double)m.q[(size_t)d * m.s];
+    else
+      ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : m.q[(size_t)d * m.s];
+  }
 }
 
 }  // namespace cdx

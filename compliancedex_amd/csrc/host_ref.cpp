@@ -332,6 +332,22 @@ int64_t depth_unproject(const D* depth, int32_t W, int32_t H, int32_t stride, co
   return n;
 }
 
+// The rows of an IK entry of variant V, one after the other in one row's storage: row(e, q0's row, storage) is the
+// variant's solve of row e and returns its status.
+template <class V, class ROW>
+int ik_host_rows(const cdx_chain& c, int64_t E, const void* q0, int32_t q_dtype, uint32_t rot_mask, void* q,
+                 int32_t* status, ROW&& row) {
+  const int T = c.n_tips, D = c.n_dofs, f64 = q_dtype == CDX_DTYPE_F64;
+  std::vector<double> mem((cdx::ik_mem_bytes<V>(T, D, rot_mask) + 7) / 8);
+  const cdx::IkMem m = cdx::ik_mem_at<V>(mem.data(), T, D, rot_mask, 0, 1);
+  for (int64_t e = 0; e < E; ++e) {
+    const int st = row(e, cdx::ik_q0_row(q0, f64, e, D), m);
+    cdx::ik_store_q(q, q0, f64, e, D, st, m);
+    status[e] = st;
+  }
+  return CDX_OK;
+}
+
 }  // namespace
 
 extern "C" {
@@ -357,7 +373,7 @@ int cdxh_fk_backward(const cdx_chain* c, const float* q, int64_t B, const float*
 
 // Geometric fingertip Jacobians and the batched IK solve (cdx_ik.h), with the device entries' argument checks.
 int cdxh_fk_jacobian(const cdx_chain* c, const float* q, int64_t B, float* lin, float* ang) {
-  const int rc = cdx::ik_chain_code(c);
+  const int rc = cdx::chain_code(c);
   if (rc) return rc;
   if (B < 0) return CDX_EINVAL;
   if (B == 0) return CDX_OK;
@@ -371,35 +387,19 @@ int cdxh_fk_jacobian(const cdx_chain* c, const float* q, int64_t B, float* lin, 
 int cdxh_ik_solve(const cdx_chain* c, const cdx_ik_params* params, int64_t E, const void* q0, int32_t q_dtype,
                   const double* target, const double* palm, const double* palm_offset, const double* w, void* q,
                   double* err, int32_t* iters, int32_t* status) {
-  int rc = cdx::ik_chain_code(c);
-  if (rc) return rc;
   cdx_ik_params p;
-  rc = cdx::ik_prepare(params, c->n_dofs, &p);
-  if (rc) return rc;
-  if (E < 0 || (q_dtype != CDX_DTYPE_F32 && q_dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
-  if (E == 0) return CDX_OK;
-  if (!q0 || !target || !q || !err || !iters || !status) return CDX_ECHAIN;
   double po[3];
-  for (int i = 0; i < 3; ++i) {
-    po[i] = palm_offset ? palm_offset[i] : 0.0;
-    if (!__builtin_isfinite(po[i])) return CDX_EINVAL;
-  }
-  const int T = c->n_tips, D = c->n_dofs, f64 = q_dtype == CDX_DTYPE_F64;
-  std::vector<double> mem((cdx::ik_mem_bytes(T, D) + 7) / 8);
-  const cdx::IkMem m = cdx::ik_mem_at(mem.data(), T, D, 0, 1);
-  for (int64_t e = 0; e < E; ++e) {
-    const cdx::Q0Row q0r{f64 ? (const void*)((const double*)q0 + e * D) : (const void*)((const float*)q0 + e * D), f64};
-    const int st = cdx::ik_row(*c, p, po, q0r, target + e * T * 3, palm ? palm + e * 6 : nullptr,
-                               w ? w + e * T : nullptr, m, err + e * T, iters + e);
-    for (int d = 0; d < D; ++d) {
-      if (f64)
-        ((double*)q)[e * D + d] = st == 2 ? ((const double*)q0)[e * D + d] : (double)m.q[d];
-      else
-        ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : m.q[d];
-    }
-    status[e] = st;
-  }
-  return CDX_OK;
+  int rc = cdx::ik_call_code(c, params, E, q_dtype, &p);
+  if (rc || E == 0) return rc;
+  if (!q0 || !target || !q || !err || !iters || !status) return CDX_ECHAIN;
+  rc = cdx::ik_offset_code(palm_offset, po);
+  if (rc) return rc;
+  const int T = c->n_tips;
+  return ik_host_rows<cdx::IkFixed>(*c, E, q0, q_dtype, 0, q, status,
+                                    [&](int64_t e, const cdx::Q0Row& q0r, const cdx::IkMem& m) {
+    return cdx::ik_row(*c, p, po, q0r, target + e * T * 3, palm ? palm + e * 6 : nullptr, w ? w + e * T : nullptr, m,
+                       err + e * T, iters + e);
+  });
 }
 
 // The free-wrist solve (ik_pose_row), with cdx_ik_solve_pose's argument checks.
@@ -407,37 +407,21 @@ int cdxh_ik_solve_pose(const cdx_chain* c, const cdx_ik_params* params, int64_t 
                        const double* target, const double* palm0_pos, const double* palm0_rot, const double* palm_offset,
                        const double* w, void* q, double* palm_pos, double* palm_rot, double* err, int32_t* iters,
                        int32_t* status) {
-  int rc = cdx::ik_chain_code(c);
-  if (rc) return rc;
   cdx_ik_params p;
-  rc = cdx::ik_prepare(params, c->n_dofs, &p);
-  if (rc) return rc;
-  if (E < 0 || (q_dtype != CDX_DTYPE_F32 && q_dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
-  if (E == 0) return CDX_OK;
+  double po[3];
+  int rc = cdx::ik_call_code(c, params, E, q_dtype, &p);
+  if (rc || E == 0) return rc;
   if (!q0 || !target || !q || !palm_pos || !palm_rot || !err || !iters || !status) return CDX_ECHAIN;
   if (!palm0_pos != !palm0_rot) return CDX_ECHAIN;
-  double po[3];
-  for (int i = 0; i < 3; ++i) {
-    po[i] = palm_offset ? palm_offset[i] : 0.0;
-    if (!__builtin_isfinite(po[i])) return CDX_EINVAL;
-  }
-  const int T = c->n_tips, D = c->n_dofs, f64 = q_dtype == CDX_DTYPE_F64;
-  std::vector<double> mem((cdx::ik_mem_bytes(T, D + 6) + 7) / 8);
-  const cdx::IkMem m = cdx::ik_mem_at(mem.data(), T, D + 6, 0, 1);
-  for (int64_t e = 0; e < E; ++e) {
-    const cdx::Q0Row q0r{f64 ? (const void*)((const double*)q0 + e * D) : (const void*)((const float*)q0 + e * D), f64};
-    const int st = cdx::ik_pose_row(*c, p, po, q0r, target + e * T * 3, palm0_pos ? palm0_pos + e * 3 : nullptr,
-                                    palm0_rot ? palm0_rot + e * 9 : nullptr, w ? w + e * T : nullptr, m,
-                                    palm_pos + e * 3, palm_rot + e * 9, err + e * T, iters + e);
-    for (int d = 0; d < D; ++d) {
-      if (f64)
-        ((double*)q)[e * D + d] = st == 2 ? ((const double*)q0)[e * D + d] : (double)m.q[d];
-      else
-        ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : m.q[d];
-    }
-    status[e] = st;
-  }
-  return CDX_OK;
+  rc = cdx::ik_offset_code(palm_offset, po);
+  if (rc) return rc;
+  const int T = c->n_tips;
+  return ik_host_rows<cdx::IkPose>(*c, E, q0, q_dtype, 0, q, status,
+                                   [&](int64_t e, const cdx::Q0Row& q0r, const cdx::IkMem& m) {
+    return cdx::ik_pose_row(*c, p, po, q0r, target + e * T * 3, palm0_pos ? palm0_pos + e * 3 : nullptr,
+                            palm0_rot ? palm0_rot + e * 9 : nullptr, w ? w + e * T : nullptr, m, palm_pos + e * 3,
+                            palm_rot + e * 9, err + e * T, iters + e);
+  });
 }
 
 // The pose-target solve (frame_ik_row), with cdx_ik_solve_frames' argument checks.  device_trig = 0: the FK's sines
@@ -449,40 +433,25 @@ int cdxh_ik_solve_frames(const cdx_chain* c, const cdx_ik_params* params, int64_
                          uint64_t dof_mask64, void* q, double* err, double* rot_err, int32_t* iters, int32_t* status,
                          int32_t device_trig) {
   const cdx::HostDeviceTrig trig(device_trig ? 1 : 0);
-  int rc = cdx::ik_chain_code(c);
-  if (rc) return rc;
   cdx_ik_params p;
-  rc = cdx::ik_prepare(params, c->n_dofs, &p);
+  double po[3];
+  int rc = cdx::ik_call_code(c, params, E, q_dtype, &p);
   if (rc) return rc;
-  if (E < 0 || (q_dtype != CDX_DTYPE_F32 && q_dtype != CDX_DTYPE_F64)) return CDX_EINVAL;
-  const int T = c->n_tips, D = c->n_dofs, f64 = q_dtype == CDX_DTYPE_F64;
+  const int T = c->n_tips, D = c->n_dofs;
   rc = cdx::ik_frames_mask_code(T, D, rot_mask64, dof_mask64);
   if (rc) return rc;
   const uint32_t rot_mask = (uint32_t)rot_mask64, dof_mask = (uint32_t)dof_mask64;
-  if (cdx::ik_frames_bytes(T, D, rot_mask) > 65536) return CDX_EINVAL;
+  if (cdx::ik_mem_bytes<cdx::IkFrames>(T, D, rot_mask) > 65536) return CDX_EINVAL;
   if (E == 0) return CDX_OK;
   if (!q0 || !target_pos || !q || !err || !rot_err || !iters || !status || (rot_mask && !target_rot)) return CDX_ECHAIN;
-  double po[3];
-  for (int i = 0; i < 3; ++i) {
-    po[i] = palm_offset ? palm_offset[i] : 0.0;
-    if (!__builtin_isfinite(po[i])) return CDX_EINVAL;
-  }
-  std::vector<double> mem((cdx::ik_frames_bytes(T, D, rot_mask) + 7) / 8);
-  const cdx::IkFrameMem f = cdx::ik_frames_mem_at(mem.data(), T, D, rot_mask, 0, 1);
-  for (int64_t e = 0; e < E; ++e) {
-    const cdx::Q0Row q0r{f64 ? (const void*)((const double*)q0 + e * D) : (const void*)((const float*)q0 + e * D), f64};
-    const int st = cdx::frame_ik_row(*c, p, po, q0r, target_pos + e * T * 3, target_rot ? target_rot + e * T * 9 : nullptr,
-                                     palm ? palm + e * 6 : nullptr, w ? w + e * T : nullptr, wr ? wr + e * T : nullptr,
-                                     rot_mask, dof_mask, f, err + e * T, rot_err + e * T, iters + e);
-    for (int d = 0; d < D; ++d) {
-      if (f64)
-        ((double*)q)[e * D + d] = st == 2 ? ((const double*)q0)[e * D + d] : (double)f.m.q[d];
-      else
-        ((float*)q)[e * D + d] = st == 2 ? ((const float*)q0)[e * D + d] : f.m.q[d];
-    }
-    status[e] = st;
-  }
-  return CDX_OK;
+  rc = cdx::ik_offset_code(palm_offset, po);
+  if (rc) return rc;
+  return ik_host_rows<cdx::IkFrames>(*c, E, q0, q_dtype, rot_mask, q, status,
+                                     [&](int64_t e, const cdx::Q0Row& q0r, const cdx::IkMem& m) {
+    return cdx::frame_ik_row(*c, p, po, q0r, target_pos + e * T * 3, target_rot ? target_rot + e * T * 9 : nullptr,
+                             palm ? palm + e * 6 : nullptr, w ? w + e * T : nullptr, wr ? wr + e * T : nullptr, rot_mask,
+                             dof_mask, m, err + e * T, rot_err + e * T, iters + e);
+  });
 }
 
 // Rigid-body dynamics (cdx_dyn.h) row by row, with the device entries' argument checks; every pointer is host memory.

@@ -90,16 +90,15 @@ def _rows(x, E, shape, name, device):
         raise ValueError(f"{name} must have shape {(E, *shape)} or {tuple(shape)}, got {tuple(x.shape)}")
     return x.contiguous()
 
+_Call = namedtuple("_Call", ["lib", "dev", "E", "T", "D", "target", "params", "q0", "dtype", "w", "po", "q", "err",
+                             "iters", "status", "chain"])
 
-def solve_ik(robot_model, target, link_names, offsets=None, q0=None, palm_pose=None, palm_offset=None, weights=None,
-             ref_q=None, rho=0.0, max_iters=50, tol=1e-5, **lm):
-    """Joint angles whose fingertips ``link_names`` (+ ``offsets``) reach ``target`` [E, T, 3] → IKResult.
 
-    ``q0`` [E, D] or [D] (float32 / float64; None: ``ref_q``, or the middle of the limits without one);
-    ``palm_pose`` [E, 6] or [6]: position + XYZ Euler angles held fixed, as ProbabilisticGraspOptimizer.forward_kinematics
-    (None: identity); ``palm_offset`` 3 host floats added to every fingertip, as the Kin optimisers do; ``weights``
-    [E, T] or [T] ≥ 0, 0 drops a fingertip; ``ref_q`` (host sequence) and ``rho`` the rest-pose term; ``lm``: mu0,
-    mu_min, mu_max, nu.  Limits come from ``get_joint_limits()``.  Runs on the current stream without waiting for it."""
+def _prepare(robot_model, target, target_name, link_names, offsets, q0, palm_offset, weights, ref_q, rho, max_iters,
+             tol, lm):
+    """What the three solves share → _Call: the target [E, T, 3] (``target_name``: the argument's name in messages),
+    the joint box and cdx_ik_params, q0 [E, D], the weights, palm_offset as a ctypes array, the outputs every solve
+    has (q, err, iters, status), the chain descriptor and q0's dtype code."""
     lib = N.load()
     dev = robot_model._device
     T, D = len(link_names), robot_model._n_dofs
@@ -107,14 +106,13 @@ def solve_ik(robot_model, target, link_names, offsets=None, q0=None, palm_pose=N
     if target.ndim == 2 and target.shape == (T, 3):
         target = target.unsqueeze(0)
     if target.ndim != 3 or target.shape[1:] != (T, 3):
-        raise ValueError(f"target must have shape [E, {T}, 3], got {tuple(target.shape)}")
+        raise ValueError(f"{target_name} must have shape [E, {T}, 3], got {tuple(target.shape)}")
     if not target.is_cuda:
         raise RuntimeError("compliancedex_amd IK runs on the GPU only")
     E = target.shape[0]
     target = target.contiguous()
     lower, upper = joint_box(robot_model.get_joint_limits())
-    ref = _host_list(ref_q)
-    params = ik_params(lower, upper, ref, rho, max_iters, tol, **lm)
+    params = ik_params(lower, upper, _host_list(ref_q), rho, max_iters, tol, **lm)
     if q0 is None:
         q0 = torch.tensor([params.ref_q[d] for d in range(D)], dtype=torch.float64, device=dev)
     else:
@@ -126,7 +124,6 @@ def solve_ik(robot_model, target, link_names, offsets=None, q0=None, palm_pose=N
     if q0.shape != (E, D):
         raise ValueError(f"q0 must have shape {(E, D)} or {(D,)}, got {tuple(q0.shape)}")
     q0 = q0.detach().contiguous()
-    palm = _rows(palm_pose, E, (6,), "palm_pose", dev)
     w = _rows(weights, E, (T,), "weights", dev)
     po = _host_list(palm_offset)
     if po is not None and len(po) != 3:
@@ -138,10 +135,25 @@ def solve_ik(robot_model, target, link_names, offsets=None, q0=None, palm_pose=N
     status = torch.empty(E, dtype=torch.int32, device=dev)
     chain = robot_model._descriptor(link_names, offsets)
     dtype = N.DTYPE_F64 if q0.dtype == torch.float64 else N.DTYPE_F32
-    N.check(lib.cdx_ik_solve(chain, C.byref(params), E, N.ptr(q0), dtype, N.ptr(target), N.ptr(palm), po_c, N.ptr(w),
-                             None, N.ptr(q), N.ptr(err), N.ptr(iters), N.ptr(status), N.stream_ptr(dev)),
-            "cdx_ik_solve")
-    return IKResult(q, err, iters, status)
+    return _Call(lib, dev, E, T, D, target, params, q0, dtype, w, po_c, q, err, iters, status, chain)
+
+
+def solve_ik(robot_model, target, link_names, offsets=None, q0=None, palm_pose=None, palm_offset=None, weights=None,
+             ref_q=None, rho=0.0, max_iters=50, tol=1e-5, **lm):
+    """Joint angles whose fingertips ``link_names`` (+ ``offsets``) reach ``target`` [E, T, 3] → IKResult.
+
+    ``q0`` [E, D] or [D] (float32 / float64; None: ``ref_q``, or the middle of the limits without one);
+    ``palm_pose`` [E, 6] or [6]: position + XYZ Euler angles held fixed, as ProbabilisticGraspOptimizer.forward_kinematics
+    (None: identity); ``palm_offset`` 3 host floats added to every fingertip, as the Kin optimisers do; ``weights``
+    [E, T] or [T] ≥ 0, 0 drops a fingertip; ``ref_q`` (host sequence) and ``rho`` the rest-pose term; ``lm``: mu0,
+    mu_min, mu_max, nu.  Limits come from ``get_joint_limits()``.  Runs on the current stream without waiting for it."""
+    c = _prepare(robot_model, target, "target", link_names, offsets, q0, palm_offset, weights, ref_q, rho, max_iters,
+                 tol, lm)
+    palm = _rows(palm_pose, c.E, (6,), "palm_pose", c.dev)
+    N.check(c.lib.cdx_ik_solve(c.chain, C.byref(c.params), c.E, N.ptr(c.q0), c.dtype, N.ptr(c.target), N.ptr(palm),
+                               c.po, N.ptr(c.w), None, N.ptr(c.q), N.ptr(c.err), N.ptr(c.iters), N.ptr(c.status),
+                               N.stream_ptr(c.dev)), "cdx_ik_solve")
+    return IKResult(c.q, c.err, c.iters, c.status)
 
 
 def euler_xyz_matrix(angles):
@@ -195,50 +207,17 @@ def solve_ik_pose(robot_model, target, link_names, offsets=None, q0=None, palm_p
     the joints towards ``ref_q`` and damps the pose's step; it never pulls the pose.  The pose is not unique where the
     joints can make up for it: different starts give different, equally valid hands
     (results.hand_pose_from_contacts ranks them).  Runs on the current stream without waiting for it."""
-    lib = N.load()
-    dev = robot_model._device
-    T, D = len(link_names), robot_model._n_dofs
-    target = torch.as_tensor(target, dtype=torch.float64, device=dev)
-    if target.ndim == 2 and target.shape == (T, 3):
-        target = target.unsqueeze(0)
-    if target.ndim != 3 or target.shape[1:] != (T, 3):
-        raise ValueError(f"target must have shape [E, {T}, 3], got {tuple(target.shape)}")
-    if not target.is_cuda:
-        raise RuntimeError("compliancedex_amd IK runs on the GPU only")
-    E = target.shape[0]
-    target = target.contiguous()
-    lower, upper = joint_box(robot_model.get_joint_limits())
-    params = ik_params(lower, upper, _host_list(ref_q), rho, max_iters, tol, **lm)
-    if q0 is None:
-        q0 = torch.tensor([params.ref_q[d] for d in range(D)], dtype=torch.float64, device=dev)
-    else:
-        q0 = torch.as_tensor(q0, device=dev)
-        if q0.dtype not in (torch.float32, torch.float64):
-            q0 = q0.to(torch.float64)
-    if q0.shape == (D,):
-        q0 = q0.expand(E, D)
-    if q0.shape != (E, D):
-        raise ValueError(f"q0 must have shape {(E, D)} or {(D,)}, got {tuple(q0.shape)}")
-    q0 = q0.detach().contiguous()
-    pos0, rot0 = _start_pose(palm_pose0, E, dev)
-    w = _rows(weights, E, (T,), "weights", dev)
-    po = _host_list(palm_offset)
-    if po is not None and len(po) != 3:
-        raise ValueError("palm_offset must have 3 entries")
-    po_c = (C.c_double * 3)(*po) if po is not None else None
-    q = torch.empty_like(q0)
-    palm_pos = torch.empty(E, 3, dtype=torch.float64, device=dev)
-    palm_rot = torch.empty(E, 3, 3, dtype=torch.float64, device=dev)
-    err = torch.empty(E, T, dtype=torch.float64, device=dev)
-    iters = torch.empty(E, dtype=torch.int32, device=dev)
-    status = torch.empty(E, dtype=torch.int32, device=dev)
-    chain = robot_model._descriptor(link_names, offsets)
-    dtype = N.DTYPE_F64 if q0.dtype == torch.float64 else N.DTYPE_F32
-    N.check(lib.cdx_ik_solve_pose(chain, C.byref(params), E, N.ptr(q0), dtype, N.ptr(target), N.ptr(pos0), N.ptr(rot0),
-                                  po_c, N.ptr(w), None, N.ptr(q), N.ptr(palm_pos), N.ptr(palm_rot), N.ptr(err),
-                                  N.ptr(iters), N.ptr(status), N.stream_ptr(dev)), "cdx_ik_solve_pose")
+    c = _prepare(robot_model, target, "target", link_names, offsets, q0, palm_offset, weights, ref_q, rho, max_iters,
+                 tol, lm)
+    pos0, rot0 = _start_pose(palm_pose0, c.E, c.dev)
+    palm_pos = torch.empty(c.E, 3, dtype=torch.float64, device=c.dev)
+    palm_rot = torch.empty(c.E, 3, 3, dtype=torch.float64, device=c.dev)
+    N.check(c.lib.cdx_ik_solve_pose(c.chain, C.byref(c.params), c.E, N.ptr(c.q0), c.dtype, N.ptr(c.target),
+                                    N.ptr(pos0), N.ptr(rot0), c.po, N.ptr(c.w), None, N.ptr(c.q), N.ptr(palm_pos),
+                                    N.ptr(palm_rot), N.ptr(c.err), N.ptr(c.iters), N.ptr(c.status),
+                                    N.stream_ptr(c.dev)), "cdx_ik_solve_pose")
     palm_pose = torch.cat([palm_pos, matrix_to_euler_xyz(palm_rot)], 1)
-    return IKPoseResult(q, palm_pose, palm_pos, palm_rot, err, iters, status)
+    return IKPoseResult(c.q, palm_pose, palm_pos, palm_rot, c.err, c.iters, c.status)
 
 
 def quaternion_matrix(quat):
@@ -291,18 +270,9 @@ def solve_ik_frames(robot_model, target_pos, target_rot, link_names, offsets=Non
     ``q0`` (clamped to the limits) and take no part in the ``rho`` term.  ``base_pose`` [E, 6] or [6]: the pose of the
     chain's root (position + XYZ Euler angles; None: identity).  The other arguments are ``solve_ik``'s.  Runs on the
     current stream without waiting for it."""
-    lib = N.load()
-    dev = robot_model._device
-    T, D = len(link_names), robot_model._n_dofs
-    target = torch.as_tensor(target_pos, dtype=torch.float64, device=dev)
-    if target.ndim == 2 and target.shape == (T, 3):
-        target = target.unsqueeze(0)
-    if target.ndim != 3 or target.shape[1:] != (T, 3):
-        raise ValueError(f"target_pos must have shape [E, {T}, 3], got {tuple(target.shape)}")
-    if not target.is_cuda:
-        raise RuntimeError("compliancedex_amd IK runs on the GPU only")
-    E = target.shape[0]
-    target = target.contiguous()
+    c = _prepare(robot_model, target_pos, "target_pos", link_names, offsets, q0, palm_offset, weights, ref_q, rho,
+                 max_iters, tol, lm)
+    E, T, D, dev = c.E, c.T, c.D, c.dev
     rot = torch.as_tensor(target_rot, device=dev)
     if rot.shape[-1] == 4 and rot.shape[-2:] != (3, 3):
         rot = quaternion_matrix(rot)
@@ -322,38 +292,14 @@ def solve_ik_frames(robot_model, target_pos, target_rot, link_names, offsets=Non
         dof_mask |= 1 << d
     if not dof_mask:
         raise ValueError("joints: at least one joint must be solved")
-    lower, upper = joint_box(robot_model.get_joint_limits())
-    params = ik_params(lower, upper, _host_list(ref_q), rho, max_iters, tol, **lm)
-    if q0 is None:
-        q0 = torch.tensor([params.ref_q[d] for d in range(D)], dtype=torch.float64, device=dev)
-    else:
-        q0 = torch.as_tensor(q0, device=dev)
-        if q0.dtype not in (torch.float32, torch.float64):
-            q0 = q0.to(torch.float64)
-    if q0.shape == (D,):
-        q0 = q0.expand(E, D)
-    if q0.shape != (E, D):
-        raise ValueError(f"q0 must have shape {(E, D)} or {(D,)}, got {tuple(q0.shape)}")
-    q0 = q0.detach().contiguous()
     base = _rows(base_pose, E, (6,), "base_pose", dev)
-    w = _rows(weights, E, (T,), "weights", dev)
     if isinstance(rot_weights, (int, float)):
         rot_weights = [float(rot_weights)] * T
     wr = _rows(rot_weights, E, (T,), "rot_weights", dev)
-    po = _host_list(palm_offset)
-    if po is not None and len(po) != 3:
-        raise ValueError("palm_offset must have 3 entries")
-    po_c = (C.c_double * 3)(*po) if po is not None else None
-    q = torch.empty_like(q0)
-    err = torch.empty(E, T, dtype=torch.float64, device=dev)
     chord = torch.empty(E, T, dtype=torch.float64, device=dev)
-    iters = torch.empty(E, dtype=torch.int32, device=dev)
-    status = torch.empty(E, dtype=torch.int32, device=dev)
-    chain = robot_model._descriptor(link_names, offsets)
-    dtype = N.DTYPE_F64 if q0.dtype == torch.float64 else N.DTYPE_F32
-    N.check(lib.cdx_ik_solve_frames(chain, C.byref(params), E, N.ptr(q0), dtype, N.ptr(target), N.ptr(rot), N.ptr(base),
-                                    po_c, N.ptr(w), N.ptr(wr), rot_mask, dof_mask, None, N.ptr(q), N.ptr(err),
-                                    N.ptr(chord), N.ptr(iters), N.ptr(status), N.stream_ptr(dev)),
+    N.check(c.lib.cdx_ik_solve_frames(c.chain, C.byref(c.params), E, N.ptr(c.q0), c.dtype, N.ptr(c.target), N.ptr(rot),
+                                      N.ptr(base), c.po, N.ptr(c.w), N.ptr(wr), rot_mask, dof_mask, None, N.ptr(c.q),
+                                      N.ptr(c.err), N.ptr(chord), N.ptr(c.iters), N.ptr(c.status), N.stream_ptr(dev)),
             "cdx_ik_solve_frames")
     rot_err = 2.0 * torch.asin(torch.clamp(0.5 * chord, max=1.0))
-    return IKFrameResult(q, err, rot_err, iters, status)
+    return IKFrameResult(c.q, c.err, rot_err, c.iters, c.status)
