@@ -22,6 +22,12 @@ Drop-in operators (same names / arguments as the reference):
                                candidates in one launch with a duality-gap certificate per row, parity with SCS
                                unpinned
   force_eq_reward              optimize_pregrasp.py:73-118
+  grasp_equilibrium / disturbance_report / max_payload / load_directions / gravity_loads /
+  EquilibriumResult / DisturbanceReport / results.robustness_for_results
+                               the PyBullet lift test of verify_pregrasp.py:82-121 asked quasi-statically: the exact
+                               spring equilibrium of force_eq_reward's model for E grasps under W dead loads each in
+                               one launch, with margins, normal forces, the object's displacement and a verdict per
+                               grasp; no rollout, parity with PyBullet not attempted
   farthest_point_down_sample   open3d's PointCloud.farthest_point_down_sample (optimize_pregrasp.py:904)
   cast_rays / occluded         open3d's RaycastingScene.cast_rays (concatenate_pcd.py:41-49)
   Camera / render_depth / depth_to_pointcloud / observable_pointcloud
@@ -68,6 +74,8 @@ from .ik import IKFrameResult, IKPoseResult, IKResult, solve_ik, solve_ik_frames
 from .dynamics import HoldingReport, holding_torques, impedance_torques  # noqa: F401
 from .wrench import (MinWrenchResult, compute_margin, min_wrench, minimum_wrench_reward,  # noqa: F401
                      solve_minimum_wrench)
+from .stability import (DisturbanceReport, EquilibriumResult, PayloadResult, disturbance_report,  # noqa: F401
+                        grasp_equilibrium, gravity_loads, load_directions, max_payload)
 from .hand import HandSpheres, HandTerm, hand_collision, penetration_report, spheres_from_urdf  # noqa: F401
 from .trajectory import (ApproachPlan, TrajectoryOptimizer, TrajectoryResult, interpolate, plan_approach,  # noqa: F401
                          retime, seed_trajectories, trajectory_report)

@@ -8,8 +8,8 @@ import ctypes as C
 import os
 import threading
 
-from ._native import (LIB_DIR, CdxChain, CdxCollision, CdxForceEq, CdxGpisModeBuffers, CdxGpisModeOpt,
-                      CdxGpisModeParams, CdxHand, CdxHandParams, CdxIkParams, CdxProblem, CdxTrajParams, CdxWrenchParams)
+from ._native import (LIB_DIR, CdxChain, CdxCollision, CdxEquilLimits, CdxEquilParams, CdxForceEq, CdxGpisModeBuffers,
+                      CdxGpisModeOpt, CdxGpisModeParams, CdxHand, CdxHandParams, CdxIkParams, CdxProblem, CdxTrajParams, CdxWrenchParams)
 
 _P = C.c_void_p
 _I32 = C.c_int32
@@ -29,6 +29,8 @@ _SIGS = {
     "cdxh_dyn_inertia": (C.c_int, [_CHAIN, _P, _I64, _P, _I32, _P]),
     "cdxh_dyn_forward": (C.c_int, [_CHAIN, _P, _I64, _P, _P, _P, _I32, _I32, _I32, _P, _I32, _P]),
     "cdxh_min_wrench": (C.c_int, [C.POINTER(CdxWrenchParams), _I64] + [_P] * 10),
+    "cdxh_grasp_equilibrium": (C.c_int, [C.POINTER(CdxEquilParams), _I64, _I64] + [_P] * 6 + [_I32] + [_P] * 10),
+    "cdxh_equil_reduce": (C.c_int, [C.POINTER(CdxEquilLimits), _I64, _I64, _I32] + [_P] * 13),
     "cdxh_hand_prepare": (C.c_int, [_I32, _I32, _P, _P, _P, _I32, _P, _P, _HAND]),
     "cdxh_hand_spheres": (C.c_int, [_CHAIN, _HAND, _I64] + [_P] * 5),
     "cdxh_hand_cost": (C.c_int, [_HAND, _HAND_PARAMS, _I64] + [_P] * 7),

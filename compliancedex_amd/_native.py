@@ -61,6 +61,16 @@ class CdxDyn(C.Structure):
                 ("inertia", (C.c_double * 6) * MAX_BODIES), ("damping", C.c_double * MAX_DOFS)]
 
 
+class CdxEquilParams(C.Structure):
+    _fields_ = [("n_tips", C.c_int32), ("max_iters", C.c_int32), ("mu", C.c_double), ("tol", C.c_double),
+                ("mu0", C.c_double), ("mu_min", C.c_double), ("mu_max", C.c_double), ("nu", C.c_double)]
+
+
+class CdxEquilLimits(C.Structure):
+    _fields_ = [("margin_min", C.c_double), ("min_normal_force", C.c_double), ("max_shift", C.c_double),
+                ("max_chord", C.c_double)]
+
+
 class CdxWrenchParams(C.Structure):
     _fields_ = [("n_tips", C.c_int32), ("max_iters", C.c_int32), ("check_every", C.c_int32), ("_pad", C.c_int32),
                 ("mu", C.c_double), ("min_force", C.c_double), ("reg", C.c_double), ("rho", C.c_double),
@@ -257,6 +267,9 @@ _SIGS = {
     "cdx_min_wrench": (C.c_int, [C.POINTER(CdxWrenchParams), _I64] + [_P] * 11),
     "cdx_wrench_rows_per_block": (C.c_int32, [C.c_int32]),
     "cdx_wrench_abi_size": (C.c_size_t, []),
+    "cdx_grasp_equilibrium": (C.c_int, [C.POINTER(CdxEquilParams), _I64, _I64] + [_P] * 6 + [C.c_int32] + [_P] * 11),
+    "cdx_equil_reduce": (C.c_int, [C.POINTER(CdxEquilLimits), _I64, _I64, C.c_int32] + [_P] * 14),
+    "cdx_equil_abi_sizes": (None, [C.POINTER(C.c_size_t)]),
     "cdx_hand_bytes": (C.c_size_t, [C.c_int32, C.c_int32]),
     "cdx_hand_abi_sizes": (None, [C.POINTER(C.c_size_t)]),
     "cdx_hand_prepare": (C.c_int, [C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P, C.POINTER(CdxHand), _P]),
@@ -340,6 +353,7 @@ _ABI_SIZES = [
     ("cdx_ik_abi_size", [CdxIkParams], "IK"),
     ("cdx_dyn_abi_size", [CdxDyn], "dynamics"),
     ("cdx_wrench_abi_size", [CdxWrenchParams], "wrench"),
+    ("cdx_equil_abi_sizes", [CdxEquilParams, CdxEquilLimits], "equilibrium"),
     ("cdx_hand_abi_sizes", [CdxHand, CdxHandParams], "hand"),
     ("cdx_traj_abi_sizes", [CdxTrajParams], "trajectory"),
 ]

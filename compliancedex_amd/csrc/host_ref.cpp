@@ -1,6 +1,6 @@
 // Host (x86) build of the per-candidate device code in cdx_fk.h / cdx_cost.h / cdx_collision.h /
 // cdx_sdf.h / cdx_gpis_mode.h / cdx_field.h / cdx_fps.h / cdx_mesh.h / cdx_sample.h / cdx_knn.h /
-// cdx_wrench.h / cdx_hand.h / cdx_traj.h.
+// cdx_wrench.h / cdx_hand.h / cdx_traj.h / cdx_equil.h.
 //
 // TEST-ONLY: libcdx_host.so lets the CPU test suite check the hand-derived backward
 // (Kabsch/SVD, cost terms, FK) against the oracle's autograd without a GPU.  The
@@ -14,6 +14,7 @@
 #include "cdx_collision.h"
 #include "cdx_cost.h"
 #include "cdx_dyn.h"
+#include "cdx_equil.h"
 #include "cdx_field.h"
 #include "cdx_fps.h"
 #include "cdx_gpis_mode.h"
@@ -534,6 +535,54 @@ int cdxh_min_wrench(const cdx_wrench_params* params, int64_t E, const double* ti
   for (int64_t e = 0; e < E; ++e)
     status[e] = cdx::mw_row(*params, tips + e * T * 3, normals + e * T * 3, m, forces + e * T * 3, wrench + e,
                             margin + e * T, dual + e * 6, gap + e, iters + e, grad_tips ? grad_tips + e * T * 3 : nullptr);
+  return CDX_OK;
+}
+
+// The disturbance-load test (cdx_equil.h) item by item and its reduction row by row, with the device entries' argument
+// checks.
+int cdxh_grasp_equilibrium(const cdx_equil_params* params, int64_t E, int64_t W, const double* contact,
+                           const double* target, const double* stiffness, const double* normal,
+                           const double* load_force, const double* load_point, int32_t loads_shared, double* rot,
+                           double* trans, double* force, double* normal_force, double* margin, double* shift,
+                           double* chord, uint8_t* stable, int32_t* iters, int32_t* status) {
+  const int rc = cdx::eq_params_code(params);
+  if (rc) return rc;
+  if (E < 0 || W < 0) return CDX_EINVAL;
+  if (E == 0 || W == 0) return CDX_OK;
+  if (!contact || !target || !stiffness || !normal || !load_force || !load_point || !normal_force || !margin ||
+      !shift || !chord || !stable || !iters || !status)
+    return CDX_EINVAL;
+  if (E > 0x7fffffff / W || E * W > 0x7fffffff / params->n_tips) return CDX_EINVAL;
+  const int T = params->n_tips;
+  for (int64_t e = 0; e < E; ++e) {
+    cdx::EqRow row;
+    const bool ok = cdx::eq_row_prepare(T, contact + e * T * 3, target + e * T * 3, stiffness + e * T, normal + e * T * 3, &row);
+    for (int64_t w = 0; w < W; ++w) {
+      const int64_t item = e * W + w, l = loads_shared ? w : item;
+      status[item] = cdx::equil_row(*params, row, ok, normal + e * T * 3, load_force + l * 3, load_point + l * 3,
+                                    rot ? rot + item * 9 : nullptr, trans ? trans + item * 3 : nullptr,
+                                    force ? force + item * T * 3 : nullptr, normal_force + item * T, margin + item * T,
+                                    shift + item, chord + item, stable + item, iters + item);
+    }
+  }
+  return CDX_OK;
+}
+
+int cdxh_equil_reduce(const cdx_equil_limits* limits, int64_t E, int64_t W, int32_t n_tips, const double* margin,
+                      const double* normal_force, const double* shift, const double* chord, const uint8_t* stable,
+                      const int32_t* status, double* worst_margin, int32_t* worst_load, int32_t* worst_tip,
+                      double* max_shift, double* max_chord, int32_t* n_failed, uint8_t* holds) {
+  if (!limits || E < 0 || W < 0 || W > 0x7fffffff || n_tips < 1 || n_tips > CDX_MAX_TIPS) return CDX_EINVAL;
+  if (E == 0 || W == 0) return CDX_OK;
+  if (!margin || !normal_force || !shift || !chord || !stable || !status || !worst_margin || !worst_load ||
+      !worst_tip || !max_shift || !max_chord || !n_failed || !holds)
+    return CDX_EINVAL;
+  for (int64_t e = 0; e < E; ++e) {
+    const int64_t at = e * W;
+    cdx::equil_reduce_row(W, n_tips, margin + at * n_tips, normal_force + at * n_tips, shift + at, chord + at,
+                          stable + at, status + at, *limits, worst_margin + e, worst_load + e, worst_tip + e,
+                          max_shift + e, max_chord + e, n_failed + e, holds + e);
+  }
   return CDX_OK;
 }
 

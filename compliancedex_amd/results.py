@@ -155,6 +155,33 @@ def approach_for_results(robot_model, hand, q_start, results, obj, floor_z=None,
                          palm_pose=wrist, floor_z=floor_z, **plan)
 
 
+def robustness_for_results(results, obj, mu, mass, com=None, directions=26, g=9.81, exp_name=None, data_dir="data",
+                           device="cuda", **report):
+    """Does every stored grasp hold an object of ``mass`` kg in any orientation of the hand: ``results`` is
+    ``load_results``' dict (or None: the five files are loaded from ``exp_name`` / ``data_dir``); the springs are its
+    ``contact``, ``target`` and ``compliance`` rows; the outward normals at the contacts come from ``obj`` — a GPIS
+    (``compute_normal``) or a mesh as ``hand.object_distance`` takes it (the signed normal of the TorchSDF query); the
+    loads are the weight in ``directions`` directions (``stability.gravity_loads``) acting at ``com`` ([3] or [E, 3];
+    None: each grasp's stiffness centre).  → stability.DisturbanceReport; ``report``: options of
+    ``stability.disturbance_report`` (limits, tol, max_iters)."""
+    import torch
+    from .gpis import GPIS
+    from .stability import disturbance_report, gravity_loads
+    if results is None:
+        results = load_results(exp_name, data_dir)
+    contact, target, comp = (torch.as_tensor(_np(results[k]), dtype=torch.float64, device=device)
+                             for k in ("contact", "target", "compliance"))
+    X = contact.reshape(-1, 3).contiguous()
+    if isinstance(obj, GPIS):
+        normal = obj.compute_normal(X)
+    else:
+        from .hand import object_distance
+        normal = object_distance(obj, X)[1]
+    force, point = gravity_loads(mass, g, directions, com)
+    return disturbance_report(contact, target, comp, normal.reshape(contact.shape).to(torch.float64), mu, force,
+                              com=point, **report)
+
+
 # ------------------------------------------------------------------ from a stored grasp to the arm
 def _chain_of(model):
     return model.chain if hasattr(model, "chain") else model

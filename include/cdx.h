@@ -479,6 +479,59 @@ int cdx_min_wrench(const cdx_wrench_params* params, int64_t E, const double* tip
 int32_t cdx_wrench_rows_per_block(int32_t n_tips);
 size_t cdx_wrench_abi_size(void);
 
+/* Batched disturbance-load test (the rule is csrc/cdx_equil.h): the spring equilibrium of E grasps under W dead loads
+ * each, the reference's quasi-static model of a compliant grasp (force_eq_reward, optimize_pregrasp.py:73-118: sticking
+ * contacts, every fingertip a spring of its own stiffness towards its target) solved exactly for any load, every
+ * (grasp, load) item its own Levenberg–Marquardt solve on the exact Hessian, all E·W items in one launch, float64, no
+ * workspace.  Item index e·W + w.
+ *   contact, target, normal [E*T*3], stiffness [E*T] f64 (normals outward, need not be unit);
+ *   load_force, load_point: [W*3] used by every row if loads_shared != 0, else [E*W*3]; the force is constant in the
+ *   world frame and acts at the body-fixed point load_point (world coordinates at the nominal pose).
+ * Outputs per item (f64 unless noted; rot, trans and force may be NULL and are then skipped):
+ *   rot [9] row-major, trans [3]: the object's displacement, x = rot·p + trans;  force [T*3] of each spring on the object;
+ *   normal_force [T], margin [T] = (−F/‖F‖)·(rot·n̂) − 1/sqrt(1 + mu²);  shift: displacement of the stiffness centre;
+ *   chord = 2·sin(θ/2) of rot;  stable u8: the energy's Hessian at the returned pose is positive definite;  iters i32;
+ *   status i32: 0 = net force ≤ tol·Fs and net torque ≤ tol·Fs·ℓ, 1 = max_iters used (finite outputs), 2 = a
+ *   non-finite input, a stiffness ≤ 0 or a zero normal in the row (all its W items), or a non-finite load (that item):
+ *   float outputs NaN, stable 0, iters 0.
+ * CDX_EINVAL, with nothing launched: a null params or required pointer, E < 0, W < 0, E·W·T beyond 2^31 − 1, n_tips
+ *   outside 1 … CDX_MAX_TIPS, max_iters < 0, mu / tol / mu0 / mu_min / mu_max / nu not finite and positive.  E = 0 or
+ *   W = 0 is a no-op. */
+typedef struct {
+  int32_t n_tips;
+  int32_t max_iters;
+  double mu;       /* friction coefficient */
+  double tol;
+  double mu0;      /* Levenberg–Marquardt damping: start, floor, ceiling, factor */
+  double mu_min;
+  double mu_max;
+  double nu;
+} cdx_equil_params;
+int cdx_grasp_equilibrium(const cdx_equil_params* params, int64_t E, int64_t W, const double* contact,
+                          const double* target, const double* stiffness, const double* normal,
+                          const double* load_force, const double* load_point, int32_t loads_shared, double* rot,
+                          double* trans, double* force, double* normal_force, double* margin, double* shift,
+                          double* chord, uint8_t* stable, int32_t* iters, int32_t* status, cdx_stream_t stream);
+/* The verdict per grasp row from those outputs, one launch, no atomics.  An item holds when status = 0 and stable, every
+ * margin > margin_min, every normal_force ≥ min_normal_force, shift ≤ max_shift and chord ≤ max_chord.
+ *   worst_margin [E] f64: the least margin over the row's items with status ≠ 2 (NaN if none); worst_load, worst_tip [E]
+ *   i32: where (the first in the order w, tip on a tie; −1 if none); max_shift, max_chord [E] f64 over the same items;
+ *   n_failed [E] i32: items that do not hold; holds [E] u8: n_failed = 0.
+ * CDX_EINVAL: a null pointer, E < 0, W < 0 or beyond 2^31 − 1, n_tips outside 1 … CDX_MAX_TIPS.  E = 0 or W = 0 is a
+ *   no-op. */
+typedef struct {
+  double margin_min;
+  double min_normal_force;
+  double max_shift;
+  double max_chord;
+} cdx_equil_limits;
+int cdx_equil_reduce(const cdx_equil_limits* limits, int64_t E, int64_t W, int32_t n_tips, const double* margin,
+                     const double* normal_force, const double* shift, const double* chord, const uint8_t* stable,
+                     const int32_t* status, double* worst_margin, int32_t* worst_load, int32_t* worst_tip,
+                     double* max_shift, double* max_chord, int32_t* n_failed, uint8_t* holds, cdx_stream_t stream);
+/* sizeof(cdx_equil_params), sizeof(cdx_equil_limits) into out[2]. */
+void cdx_equil_abi_sizes(size_t* out);
+
 /* ------------------------------------------------------ prob-mode closure -------
  * Replaces ProbabilisticGraspOptimizer.closure (optimize_pregrasp.py:741-769) —
  * forward AND backward for E candidates — plus its callees compute_loss (:713-739),
