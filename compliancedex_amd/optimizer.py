@@ -75,11 +75,14 @@ class _Collision(torch.autograd.Function):
 
 class ProbabilisticGraspOptimizer:
     def __init__(self, robot_urdf, ee_link_names, ee_link_offsets=EE_OFFSETS, palm_offset=WRIST_OFFSET,
-                 num_iters=1000, optimize_target=False, ref_q=None, tip_bounding_box=(FINGERTIP_LB, FINGERTIP_UB),
-                 pregrasp_coefficients=((0.8, 0.8, 0.8, 0.8),) * 3, pregrasp_weights=(0.1, 0.8, 0.1),
+                 num_iters=1000, optimize_target=False, ref_q=None, tip_bounding_box=None,
+                 pregrasp_coefficients=None, pregrasp_weights=(0.1, 0.8, 0.1),
                  anchor_link_names=None, anchor_link_offsets=None, collision_pairs=None,
                  collision_pair_threshold=0.02, mass=0.1, com=(0.0, 0.0, 0.0), gravity=True, uncertainty=20.0,
                  optimize_palm=False, device="cuda", seed=0, collision=False):
+        """``tip_bounding_box`` (lb, ub): one row of 3 per fingertip, or a single row for every fingertip (default: the
+        reference's box, FINGERTIP_LB / FINGERTIP_UB's row).  ``pregrasp_coefficients`` [K ≤ 4, T]: default 0.8 for
+        every fingertip at three levels.  Both are checked against the fingertip count here."""
         self.device = torch.device(device)
         self.ref_q = torch.tensor(list(ref_q)).to(self.device)  # float32 (:634)
         self.robot_model = DifferentiableRobotModel(robot_urdf, device=device)
@@ -89,8 +92,16 @@ class ProbabilisticGraspOptimizer:
         self.palm_offset = torch.from_numpy(np.asarray(palm_offset, dtype=np.float64)).to(self.device)
         self.optimize_target = optimize_target
         self.optimize_palm = optimize_palm
-        self.tip_bounding_box = [torch.tensor(tip_bounding_box[0]).to(self.device).view(-1, 3),
-                                 torch.tensor(tip_bounding_box[1]).to(self.device).view(-1, 3)]
+        T = len(self.ee_link_names)
+        if tip_bounding_box is None:
+            tip_bounding_box = (FINGERTIP_LB[:3], FINGERTIP_UB[:3])
+        self.tip_bounding_box = [self._box_rows(b, T) for b in tip_bounding_box]
+        if pregrasp_coefficients is None:
+            pregrasp_coefficients = ((0.8,) * T,) * 3
+        if any(len(r) != T for r in pregrasp_coefficients) or not 1 <= len(pregrasp_coefficients) <= N.MAX_LEVELS:
+            raise ValueError(f"pregrasp_coefficients must be [K <= {N.MAX_LEVELS}, {T}]: one column per fingertip")
+        if len(pregrasp_weights) != len(pregrasp_coefficients):
+            raise ValueError("one pregrasp weight per level")
         self.pregrasp_coefficients = torch.tensor([list(r) for r in pregrasp_coefficients]).to(self.device)
         self.pregrasp_weights = torch.tensor(list(pregrasp_weights)).double().to(self.device)
         self.anchor_link_names = anchor_link_names
@@ -113,13 +124,22 @@ class ProbabilisticGraspOptimizer:
         self._graphs = {}
         self.optim = None
 
+    def _box_rows(self, bound, T):
+        """One bound of the fingertip box as [T, 3]: a row per fingertip, or a single row ([3] or [1, 3]) for all."""
+        b = torch.tensor(bound)
+        if b.numel() == 0 or b.numel() % 3 or b.numel() // 3 not in (1, T):
+            raise ValueError(f"tip_bounding_box bounds must hold 1 or {T} rows of 3 (one per fingertip), got "
+                             f"{b.numel()} values")
+        return b.reshape(-1, 3).expand(T, 3).contiguous().to(self.device)
+
     # ------------------------------------------------------------------ FK
     def forward_kinematics(self, joint_angles, palm_poses=None):
-        """World fingertips R(euler XYZ)·tip + palm_pos, [E, 4, 3] f64 (:657-669)."""
+        """World fingertips R(euler XYZ)·tip + palm_pos, [E, T, 3] f64 (:657-669)."""
         if palm_poses is None:
             palm_poses = self.palm_offset
         tips = self.robot_model.compute_forward_kinematics(joint_angles.float(), self.ee_link_names,
-                                                           offsets=self.ee_link_offsets)[0].double().view(-1, 4, 3)
+                                                           offsets=self.ee_link_offsets)[0].double()
+        tips = tips.view(-1, len(self.ee_link_names), 3)
         R = euler_angles_to_matrix(palm_poses[:, 3:], convention="XYZ")
         return torch.bmm(R, tips.transpose(1, 2)).transpose(1, 2) + palm_poses[:, :3].unsqueeze(1)
 
@@ -306,7 +326,7 @@ class ProbabilisticGraspOptimizer:
         opt_compliance = compliance.clone()
         opt_target_pose = target_pose.clone()
         opt_value = torch.inf * torch.ones(num_envs, dtype=torch.float64, device=joint_angles.device)
-        opt_margin = torch.zeros(num_envs, 4, dtype=torch.float64, device=joint_angles.device)
+        opt_margin = torch.zeros(num_envs, len(self.ee_link_names), dtype=torch.float64, device=joint_angles.device)
         opt_palm_poses = self.palm_offset.clone()
         p = self.problem(gpis, friction_mu)  # the loop's cumulative screen record starts at zero
         self._ensure_ws(p, num_envs, joint_angles.device)

@@ -13,7 +13,6 @@ import torch
 
 from ._native import MAX_DOFS, MAX_LEVELS, MAX_TIPS, CdxGpis, CdxProblem
 
-DEFAULT_COEFFS = [[0.8, 0.8, 0.8, 0.8]] * 3
 DEFAULT_WEIGHTS = [0.1, 0.8, 0.1]
 
 
@@ -21,18 +20,21 @@ def cos_friction(mu):
     return float(torch.sqrt(1 / (1 + torch.tensor(mu) ** 2)))
 
 
-def build_problem(chain_desc, gpis_desc=None, ref_q=(), coeffs=DEFAULT_COEFFS, weights=DEFAULT_WEIGHTS, mu=1,
+def build_problem(chain_desc, gpis_desc=None, ref_q=(), coeffs=None, weights=DEFAULT_WEIGHTS, mu=1,
                   mass=0.1, com=(0.0, 0.0, 0.0), gravity=True, M=2.0, gravity_acc=10.0, uncertainty=20.0,
                   optimize_palm=True):
-    """chain_desc: a ``cdx_chain`` with the fingertips (and offsets) set; gpis_desc: ``cdx_gpis``."""
+    """chain_desc: a ``cdx_chain`` with the fingertips (and offsets) set; gpis_desc: ``cdx_gpis``.
+    ``coeffs`` [K, n_tips]: default 0.8 for every fingertip at three levels."""
     p = CdxProblem()
     ctypes.memmove(ctypes.byref(p.chain), ctypes.byref(chain_desc), ctypes.sizeof(chain_desc))
     if gpis_desc is not None:
         ctypes.memmove(ctypes.byref(p.gpis), ctypes.byref(gpis_desc), ctypes.sizeof(CdxGpis))
     T = chain_desc.n_tips
+    if coeffs is None:
+        coeffs = [[0.8] * T] * 3
     coeffs_t = torch.tensor(coeffs)  # float32 like the reference
     K = coeffs_t.shape[0]
-    if not 1 <= K <= MAX_LEVELS or coeffs_t.shape[1] != T or T > MAX_TIPS:
+    if coeffs_t.dim() != 2 or not 1 <= K <= MAX_LEVELS or coeffs_t.shape[1] != T or T > MAX_TIPS:
         raise ValueError(f"pregrasp coefficients must be [K<= {MAX_LEVELS}, {T}]")
     if len(weights) != K:
         raise ValueError("one pregrasp weight per level")

@@ -326,18 +326,21 @@ def contact_margin(tip, target, normal, mu):
     return (0.1 * torch.log(ang + 1) + 0.9 * torch.log(m + 1)).sum(dim=1)
 
 
-PREGRASP_COEFFS = [[0.8] * 4] * 3
 PREGRASP_WEIGHTS = [0.1, 0.8, 0.1]
 
 
 class OracleProblem:
-    """The prob-mode optimiser's fixed data (optimize_pregrasp.py:614-655)."""
+    """The prob-mode optimiser's fixed data (optimize_pregrasp.py:614-655).  The fingertip count is
+    ``len(ee_links)``; ``coeffs`` defaults to 0.8 for every fingertip at three levels."""
 
     def __init__(self, chain, ee_links, ee_offsets, ref_q, gpis, mu=1, mass=0.1, com=(0.0, 0.0, 0.0),
                  gravity=True, uncertainty=20.0, optimize_palm=True,
-                 coeffs=PREGRASP_COEFFS, weights=PREGRASP_WEIGHTS):
+                 coeffs=None, weights=PREGRASP_WEIGHTS):
         self.chain = chain
         self.ee_links = list(ee_links)
+        self.n_tips = len(self.ee_links)
+        if coeffs is None:
+            coeffs = [[0.8] * self.n_tips] * 3
         self.ee_offsets = [list(map(float, o)) for o in ee_offsets]
         self.ref_q = torch.tensor(list(map(float, ref_q)))          # float32 (:634)
         self.gpis = gpis
@@ -350,7 +353,8 @@ class OracleProblem:
 
     def forward_kinematics(self, q, palm):
         """Fingertips in world: R(euler XYZ)·tip + palm_pos (optimize_pregrasp.py:657-669)."""
-        tips = self.chain.forward_kinematics(q.float(), self.ee_links, self.ee_offsets)[0].double().view(-1, 4, 3)
+        tips = self.chain.forward_kinematics(q.float(), self.ee_links, self.ee_offsets)[0].double()
+        tips = tips.view(-1, self.n_tips, 3)
         R = euler_xyz(palm[:, 3:])
         return torch.bmm(R, tips.transpose(1, 2)).transpose(1, 2) + palm[:, :3].unsqueeze(1)
 
@@ -376,7 +380,7 @@ class OracleProblem:
     def closure(self, q, comp, target, palm_pos, palm_ori, noise):
         """One cost+grad eval for all E candidates (optimize_pregrasp.py:741-769).
         ``noise`` [K·E, 3, 3] is the Kabsch ``rand_like`` draw.  Returns
-        (loss, total_loss [E], total_margin [E,4], pregrasp_tip [E,4,3], flip [K·E])
+        (loss, total_loss [E], total_margin [E,T], pregrasp_tip [E,T,3], flip [K·E]), T = len(ee_links),
         and leaves gradients in the leaves' ``.grad``."""
         E = q.shape[0]
         K = len(self.coeffs)
@@ -385,10 +389,10 @@ class OracleProblem:
         target_ext = target.repeat(K, 1, 1)
         pre_ext = pre.repeat(K, 1, 1)
         co = self.coeffs.repeat_interleave(E, dim=0)
-        all_tip = target_ext + co.view(-1, 4, 1) * (pre_ext - target_ext)
+        all_tip = target_ext + co.view(-1, self.n_tips, 1) * (pre_ext - target_ext)
         l, margin, flip = self.compute_loss(all_tip, q.repeat(K, 1), target_ext, comp.repeat(K, 1), noise)
         total_loss = (self.weights.unsqueeze(1) * l.view(-1, E)).sum(dim=0)
-        total_margin = (self.weights.view(-1, 1, 1) * margin.view(-1, E, 4)).sum(dim=0)
+        total_margin = (self.weights.view(-1, 1, 1) * margin.view(-1, E, self.n_tips)).sum(dim=0)
         pre_dist, _ = self.gpis.pred(pre)
         total_loss = total_loss - pre_dist.sum(dim=1) * 5.0
         if self.optimize_palm:

@@ -140,9 +140,10 @@ def depths(case):
 
 def robot_dict(case, config=None):
     b, links = bodies(case)
-    return dict(name=case, bodies=b, config=dict(ee_link_name=links, ee_link_offset=tip_offsets(case),
-                                                 ref_q=[0.0] * sum(x["joint"] != "fixed" for x in b[1:]),
-                                                 **(config or {})))
+    cfg = dict(ee_link_name=links, ee_link_offset=tip_offsets(case),
+               ref_q=[0.0] * sum(x["joint"] != "fixed" for x in b[1:]))
+    cfg.update(config or {})  # (may replace the fingertips: a subset of the tips)
+    return dict(name=case, bodies=b, config=cfg)
 
 
 def write_json(case, tmp_path, config=None):

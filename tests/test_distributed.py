@@ -272,15 +272,18 @@ def test_optimize_sharded_one_object_per_rank_gloo_world2():
 
 
 @pytest.mark.gpu
-@pytest.mark.parametrize("E,cap", [(4096, 4096), (4096, 7), (1, 3), (0, 5), (3000, 1500), (5000, 2100), (2049, 9000),
-                                   (1024, 0), (130, 70), (65, 64)])
-def test_native_pack_equals_cpu_layout(E, cap):
+@pytest.mark.parametrize("E,cap,T,D", [pytest.param(E, cap, 4, 16, id=f"{E}-{cap}") for E, cap in
+                                       [(4096, 4096), (4096, 7), (1, 3), (0, 5), (3000, 1500), (5000, 2100),
+                                        (2049, 9000), (1024, 0), (130, 70), (65, 64)]] +
+                         [pytest.param(130, 50, T, D, id=f"130-50-T{T}-D{D}") for T, D in [(1, 2), (3, 9), (8, 23)]])
+def test_native_pack_equals_cpu_layout(E, cap, T, D):
     """cdx_pack_survivors (the GPU pack: per-tile counts, then the rows — two launches over the chip,
     header counts written on the device, no host sync, no memset) produces bit for bit the buffer of the CPU (torch-ops) layout: survivors in
     candidate order, overflow counted in the header, unused rows zero — also when the buffer was dirty
     before (the kernel zeroes them itself); NaN margins do not survive.  Ragged sizes cross the
-    kernel's 64-candidate tiles with the capacity cut inside a tile."""
-    d = _local(3, E=E)
+    kernel's 64-candidate tiles with the capacity cut inside a tile; other fingertip and joint counts than the
+    Allegro's (T, D) = (4, 16) give other record widths 5 + T + D + T + 3T + 6."""
+    d = _local(3, E=E, D=D, T=T)
     if E:
         d["margin"][0, 0] = float("nan")
     cpu = pack_survivors(cap, 5, 1, 10, **d)

@@ -43,7 +43,7 @@ def _opt(hand="allegro"):
                                             optimize_target=True, optimize_palm=True, device=DEV)
 
 
-def _closure(opt, gpis, inputs, screen=True, delta_scale=1.0):
+def _closure(opt, gpis, inputs, screen=True, delta_scale=1.0, noise=None):
     q, comp, target, palm = inputs
     p = opt.problem(gpis, 1)
     delta = p.gpis.screen_delta
@@ -54,7 +54,8 @@ def _closure(opt, gpis, inputs, screen=True, delta_scale=1.0):
     try:
         t = [torch.from_numpy(np.ascontiguousarray(a)).to(DEV).requires_grad_(True)
              for a in (q, comp, target, palm[:, :3], palm[:, 3:])]
-        noise = torch.from_numpy(np.random.default_rng(7).random((3 * q.shape[0], 3, 3))).to(DEV)
+        if noise is None:
+            noise = torch.from_numpy(np.random.default_rng(7).random((3 * q.shape[0], 3, 3))).to(DEV)
         opt.closure(*t, 1, gpis, q.shape[0], kabsch_noise=noise)
         torch.cuda.synchronize()
         out = dict(total_loss=opt.total_loss.cpu().numpy(), total_margin=opt.total_margin.cpu().numpy(),
