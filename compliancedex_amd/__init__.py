@@ -28,6 +28,16 @@ Drop-in operators (same names / arguments as the reference):
                                spring equilibrium of force_eq_reward's model for E grasps under W dead loads each in
                                one launch, with margins, normal forces, the object's displacement and a verdict per
                                grasp; no rollout, parity with PyBullet not attempted
+  GPIS.pred_joint / normal_uncertainty / sample_joint / sample_normals / gpis_joint_cov / NormalUncertainty /
+  shape_uncertainty_report / ShapeUncertaintyReport
+                               the posterior of (f, ∇f) per query, a 4-vector Gaussian (the reference has none; its
+                               compute_multinormals, gpis.py:89-111, takes normals from nested subsets of the inducing
+                               points, a heuristic with no probabilistic meaning): how well a contact's normal (an
+                               angular std) and the surface's position (metres) are known, draws of both, and the
+                               probability that a grasp holds under disturbance_report's loads when the normals are
+                               drawn.  The angular std at the packaged states is large (medians of a CPU float64
+                               prototype 4 mm off the surface: 0.41 rad banana, 0.51 rad lego, 1.13 rad mug): the TPS
+                               prior leaves the pointwise normal poorly determined
   farthest_point_down_sample   open3d's PointCloud.farthest_point_down_sample (optimize_pregrasp.py:904)
   cast_rays / occluded         open3d's RaycastingScene.cast_rays (concatenate_pcd.py:41-49)
   Camera / render_depth / depth_to_pointcloud / observable_pointcloud
@@ -54,7 +64,7 @@ Drop-in operators (same names / arguments as the reference):
   HandTerm                     that cost as a term of the joint-space optimisers' loss: optimize(..., hand_term=…)
 All compute runs in libcdx.so (HIP, gfx950); importing works without a GPU, calling does not.
 """
-from .gpis import GPIS  # noqa: F401
+from .gpis import GPIS, NormalUncertainty, gpis_joint_cov  # noqa: F401
 from .optimizer import (EE_OFFSETS, FINGERTIP_LB, FINGERTIP_UB, WRIST_OFFSET,  # noqa: F401
                         ProbabilisticGraspOptimizer, euler_angles_to_matrix)
 from .anneal import PregraspAnnealer  # noqa: F401
@@ -74,8 +84,9 @@ from .ik import IKFrameResult, IKPoseResult, IKResult, solve_ik, solve_ik_frames
 from .dynamics import HoldingReport, holding_torques, impedance_torques  # noqa: F401
 from .wrench import (MinWrenchResult, compute_margin, min_wrench, minimum_wrench_reward,  # noqa: F401
                      solve_minimum_wrench)
-from .stability import (DisturbanceReport, EquilibriumResult, PayloadResult, disturbance_report,  # noqa: F401
-                        grasp_equilibrium, gravity_loads, load_directions, max_payload)
+from .stability import (DisturbanceReport, EquilibriumResult, PayloadResult, ShapeUncertaintyReport,  # noqa: F401
+                        disturbance_report, grasp_equilibrium, gravity_loads, load_directions, max_payload,
+                        shape_uncertainty_report)
 from .hand import HandSpheres, HandTerm, hand_collision, penetration_report, spheres_from_urdf  # noqa: F401
 from .trajectory import (ApproachPlan, TrajectoryOptimizer, TrajectoryResult, interpolate, plan_approach,  # noqa: F401
                          retime, seed_trajectories, trajectory_report)

@@ -8,7 +8,7 @@ import ctypes as C
 import os
 import threading
 
-from ._native import (LIB_DIR, CdxChain, CdxCollision, CdxEquilLimits, CdxEquilParams, CdxForceEq, CdxGpisModeBuffers,
+from ._native import (LIB_DIR, CdxChain, CdxCollision, CdxEquilLimits, CdxEquilParams, CdxForceEq, CdxGpis, CdxGpisModeBuffers,
                       CdxGpisModeOpt, CdxGpisModeParams, CdxHand, CdxHandParams, CdxIkParams, CdxProblem, CdxTrajParams, CdxWrenchParams)
 
 _P = C.c_void_p
@@ -49,6 +49,8 @@ _SIGS = {
     "cdxh_gpis_mode_cost": (C.c_int, _MODE + [C.POINTER(CdxGpisModeBuffers), _I64, _I32, _P, _U64, _I32]),
     "cdxh_gpis_mode_step": (C.c_int, _MODE + [C.POINTER(CdxGpisModeOpt), C.POINTER(CdxGpisModeBuffers), _I64, _I32,
                                               _I32, _I32]),
+    "cdxh_gpis_joint": (C.c_int, [C.POINTER(CdxGpis), _P, _I64, _P]),
+    "cdxh_gpis_kernel_values": (C.c_int, [_I32, _F64, _F64, _F64, _P]),
     "cdxh_svd3": (None, [_P] * 4),
     "cdxh_sdf_forward": (None, [_P, _I64, _P, _I64] + [_P] * 5),
     "cdxh_face_dist2": (None, [_P, _P, _I64, _P, _P]),

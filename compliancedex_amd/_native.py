@@ -209,6 +209,8 @@ _SIGS = {
     "cdx_gpis_mean": (C.c_int, [C.POINTER(CdxGpis), _P, _I64, _P, _P, _P, _P]),
     "cdx_gpis_std_workspace": (C.c_size_t, [C.POINTER(CdxGpis), _I64]),
     "cdx_gpis_std": (C.c_int, [C.POINTER(CdxGpis), _P, _I64, _P, _P, _P, _P]),
+    "cdx_gpis_joint_workspace": (C.c_size_t, [C.POINTER(CdxGpis), _I64]),
+    "cdx_gpis_joint": (C.c_int, [C.POINTER(CdxGpis), _P, _I64, _P, _P, _P]),
     "cdx_gpis_screen_bytes": (C.c_size_t, [C.c_int32]),
     "cdx_gpis_screen_prepare": (C.c_int, [C.POINTER(CdxGpis), _P, _P]),
     "cdx_gpis_screen_set_bands": (C.c_int, [C.POINTER(CdxGpis), C.POINTER(C.c_double), _P]),

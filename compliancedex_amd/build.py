@@ -21,7 +21,7 @@ ARCH = os.environ.get("CDX_OFFLOAD_ARCH", "gfx950")
 
 HIP_SOURCES = ["cdx_gpis.hip", "cdx_screen.hip", "cdx_fit.hip", "cdx_closure.hip", "cdx_sdf.hip", "cdx_optim.hip", "cdx_exchange.hip", "cdx_kin.hip",
                "cdx_gpis_mode.hip", "cdx_field.hip", "cdx_fps.hip", "cdx_ray.hip", "cdx_mesh.hip", "cdx_sample.hip", "cdx_knn.hip", "cdx_ik.hip",
-               "cdx_wrench.hip", "cdx_hand.hip", "cdx_dyn.hip", "cdx_traj.hip", "cdx_equil.hip"]
+               "cdx_wrench.hip", "cdx_hand.hip", "cdx_dyn.hip", "cdx_traj.hip", "cdx_equil.hip", "cdx_gpis_joint.hip"]
 FP_CONTRACT_OFF = ("cdx_sdf.hip", "cdx_closure.hip", "cdx_kin.hip", "cdx_gpis_mode.hip", "cdx_fps.hip", "cdx_ray.hip", "cdx_mesh.hip", "cdx_sample.hip", "cdx_knn.hip", "cdx_ik.hip", "cdx_wrench.hip", "cdx_hand.hip", "cdx_dyn.hip", "cdx_traj.hip", "cdx_equil.hip")  # see build_device
 HIPCC = os.environ.get("HIPCC", shutil.which("hipcc") or "/opt/rocm/bin/hipcc")
 

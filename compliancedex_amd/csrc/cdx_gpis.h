@@ -85,4 +85,13 @@ CDX_HD double gpis_k0(double R) {
   return 0.3 + 0.7 * (R * R * R);
 }
 
+// κ = −k″(0) along any axis: the prior variance of ∂f/∂x_i (the gradient's prior covariance is κ·I, and its prior
+// covariance with f is zero).  TPS: k″ = 12r − 6R → 6R; RBF: 1/σ².
+template <int KT>
+CDX_HD double gpis_kappa(double R, double inv_s2) {
+  if (KT == CDX_KERNEL_TPS) return 6.0 * R;
+  if (KT == CDX_KERNEL_RBF) return inv_s2;
+  return 0.3 * inv_s2 + 0.7 * (6.0 * R);
+}
+
 }  // namespace cdx

@@ -17,6 +17,7 @@
 #include "cdx_equil.h"
 #include "cdx_field.h"
 #include "cdx_fps.h"
+#include "cdx_gpis_joint.h"
 #include "cdx_gpis_mode.h"
 #include "cdx_hand.h"
 #include "cdx_ik.h"
@@ -350,6 +351,33 @@ int ik_host_rows(const cdx_chain& c, int64_t E, const void* q0, int32_t q_dtype,
 }
 
 }  // namespace
+
+// Host build of cdx_gpis_joint (same arguments without the workspace and the stream; the descriptor's X1 and Linv_t are
+// host pointers, Linv_t the caller's own factor): the rule of cdx_gpis_joint.h as plain loops, the columns in their
+// order in one sum.  tests/test_joint_cpu.py checks it against a numpy statement of Σ.
+template <int KT>
+static void host_gpis_joint(const cdx_gpis& g, const double* X, int64_t M, double* cov) {
+  const double R = g.R, inv_s2 = 1.0 / (g.sigma * g.sigma);
+  std::vector<double> b((size_t)g.N * 4);
+  for (int64_t m = 0; m < M; ++m) {
+    const double* x = X + 3 * m;
+    for (int j = 0; j < g.N; ++j) {
+      const double* xj = g.X1 + 3 * (int64_t)j;
+      for (int c = 0; c < 4; ++c)
+        b[(size_t)j * 4 + c] = cdx::gpis_joint_entry<KT>(x[0] - xj[0], x[1] - xj[1], x[2] - xj[2], c, R, inv_s2);
+    }
+    double gram[cdx::JOINT_OUT] = {};
+    for (int n = 0; n < g.N; ++n) {
+      double w[4] = {0.0, 0.0, 0.0, 0.0};
+      for (int j = 0; j <= n; ++j) {  // L⁻ᵀ is upper triangular
+        const double l = g.Linv_t[(int64_t)j * g.N_pad + n];
+        for (int c = 0; c < 4; ++c) w[c] = fma(l, b[(size_t)j * 4 + c], w[c]);
+      }
+      cdx::gpis_joint_gram(w, gram);
+    }
+    for (int e = 0; e < cdx::JOINT_OUT; ++e) cov[m * cdx::JOINT_OUT + e] = cdx::gpis_joint_prior<KT>(e, R, inv_s2) - gram[e];
+  }
+}
 
 extern "C" {
 
@@ -1162,6 +1190,39 @@ int cdxh_sample_draw(const void* faces, int32_t dtype, int64_t F, const uint64_t
     if (bary) { bary[2 * row] = u; bary[2 * row + 1] = v; }
   }
   return CDX_OK;
+}
+
+int cdxh_gpis_joint(const cdx_gpis* g, const double* X, int64_t M, double* cov) {
+  if (!g || !g->X1 || !g->Linv_t || g->N <= 0 || g->N_pad < g->N) return CDX_EINVAL;
+  if (g->kernel < 0 || g->kernel > 2) return CDX_EKERNEL;
+  if (M < 0 || (M > 0 && (!X || !cov))) return CDX_EINVAL;
+  switch (g->kernel) {
+    case CDX_KERNEL_TPS: host_gpis_joint<CDX_KERNEL_TPS>(*g, X, M, cov); break;
+    case CDX_KERNEL_RBF: host_gpis_joint<CDX_KERNEL_RBF>(*g, X, M, cov); break;
+    default: host_gpis_joint<CDX_KERNEL_JOINT>(*g, X, M, cov); break;
+  }
+  return CDX_OK;
+}
+
+// gpis_kappa / gpis_k0 / gpis_k of csrc/cdx_gpis.h for one kernel id: out4 = (k, kd, k0, κ) at squared distance r2.
+int cdxh_gpis_kernel_values(int32_t kernel, double r2, double R, double sigma, double* out4) {
+  if (!out4) return CDX_EINVAL;
+  const double inv_s2 = 1.0 / (sigma * sigma);
+  switch (kernel) {
+    case CDX_KERNEL_TPS:
+      cdx::gpis_k<CDX_KERNEL_TPS>(r2, R, inv_s2, out4[0], out4[1]);
+      out4[2] = cdx::gpis_k0<CDX_KERNEL_TPS>(R); out4[3] = cdx::gpis_kappa<CDX_KERNEL_TPS>(R, inv_s2);
+      return CDX_OK;
+    case CDX_KERNEL_RBF:
+      cdx::gpis_k<CDX_KERNEL_RBF>(r2, R, inv_s2, out4[0], out4[1]);
+      out4[2] = cdx::gpis_k0<CDX_KERNEL_RBF>(R); out4[3] = cdx::gpis_kappa<CDX_KERNEL_RBF>(R, inv_s2);
+      return CDX_OK;
+    case CDX_KERNEL_JOINT:
+      cdx::gpis_k<CDX_KERNEL_JOINT>(r2, R, inv_s2, out4[0], out4[1]);
+      out4[2] = cdx::gpis_k0<CDX_KERNEL_JOINT>(R); out4[3] = cdx::gpis_kappa<CDX_KERNEL_JOINT>(R, inv_s2);
+      return CDX_OK;
+  }
+  return CDX_EKERNEL;
 }
 
 // cdx::philox4x32_10 for the known-answer vectors: counter [4], key [2] → out [4].

@@ -12,7 +12,12 @@ two without the lattice leaving the device; ``fit_pointcloud`` goes from a raw s
 (farthest-point sampling by cdx_fps, then the reference's recipe: pointcloud.py); ``tomesh`` turns a lattice field into
 a watertight triangle mesh by marching tetrahedra on the device (cdx_gpis_mesh_count / _place, the rule of
 csrc/cdx_mesh.h; the reference's Poisson reconstruction is not reproduced) and ``surface_mesh`` goes from the state to
-that mesh, optionally refined along the lattice edges, without the lattice leaving the device.
+that mesh, optionally refined along the lattice edges, without the lattice leaving the device.  ``pred_joint`` is the
+posterior of the value and its gradient together, a 4-vector Gaussian per query (cdx_gpis_joint: Σ = P0 − WᵀW, three
+more whitened columns a query than the std pass); ``normal_uncertainty`` turns it into the covariance of the unit
+normal, an angular standard deviation and the standard deviation of the surface's position, and ``sample_joint`` /
+``sample_normals`` draw from it — the probabilistic counterpart of ``compute_multinormals``, whose nested subsets of
+the inducing points (gpis.py:89-111) are a heuristic with no such meaning.
 
 Differences in *how*, not *what*: ``fit`` builds R and E11 with cdx_gpis_fit, and L⁻¹ (E11 = LLᵀ),
 E11⁻¹ and α = L⁻ᵀL⁻¹y1 are factored once per state on the device by cdx_gpis_factor (blocked
@@ -24,6 +29,7 @@ from __future__ import annotations
 
 import ctypes
 import os
+from collections import namedtuple
 
 import numpy as np
 import torch
@@ -36,6 +42,19 @@ _PKG_STATES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "data", "
 SCREEN_MARGIN = 32.0
 CALIB_QUERIES = 8192      # near the object (displaced inducing points, bounding box ± 5 cm)
 CALIB_FAR_QUERIES = 4096  # 5 cm … 3.5R from the inducing points (the screen's whole finite range)
+
+
+NormalUncertainty = namedtuple("NormalUncertainty", ["normal", "cov_normal", "angle_std", "offset_std"])
+NormalUncertainty.__doc__ = """At queries […, 3]: normal […, 3] = ∇mean/‖∇mean‖; cov_normal […, 3, 3], the first-order
+covariance of the unit normal (I − n̂n̂ᵀ)·Σ_g·(I − n̂n̂ᵀ)/‖∇mean‖² with Σ_g the posterior covariance of the gradient;
+angle_std […] = sqrt(trace cov_normal), the angular standard deviation in rad (first order: a value near or above 1 says
+that the normal is hardly determined, not that it is known to that angle); offset_std […] = sqrt(max(Σ00, 0))/‖∇mean‖,
+the standard deviation of the surface's position along the normal, in metres."""
+
+# Upper-triangle order of cdx_gpis_joint's 10 entries → the 4 × 4 matrix.
+_TRIU = [(a, b) for a in range(4) for b in range(a, 4)]
+_FILL = [[_TRIU.index((min(a, b), max(a, b))) for b in range(4)] for a in range(4)]
+PIVOT_REL = 1e-12  # a Cholesky pivot ≤ this × its prior entry gets no noise
 
 
 def _require_cuda(t, what):
@@ -77,6 +96,7 @@ class _State:
         self.desc.screen_delta = 0.0
         self.ws = None
         self.screen_ws = None
+        self.joint_ws = None
         self.screen_err, bands = self._calibrate_screen(X1[:n].to(torch.float64), R, kernel)
         # the closure keeps every fingertip whose estimate is within 2Δ_f of its group's leader
         k0 = {"tps": float(R) ** 3, "rbf": 1.0, "joint": 0.3 + 0.7 * float(R) ** 3}[kernel]
@@ -194,6 +214,83 @@ def gpis_std(state, X, want_grad=True):
         N.check(lib.cdx_gpis_std(state.desc, N.ptr(X), M, N.ptr(std), N.ptr(gstd), N.ptr(ws),
                                  N.stream_ptr(X.device)), "cdx_gpis_std")
     return std, gstd
+
+
+def gpis_joint_cov(state, X):
+    """The posterior covariance of (f, ∂f/∂x, ∂f/∂y, ∂f/∂z) at X [M, 3] → [M, 10], the upper triangle row-major
+    (ff, fx, fy, fz, xx, xy, xz, yy, yz, zz), signed (cdx_gpis_joint)."""
+    lib = N.load()
+    X = X.contiguous()
+    M = X.shape[0]
+    cov = torch.empty(M, 10, dtype=torch.float64, device=X.device)
+    if M:
+        need = lib.cdx_gpis_joint_workspace(state.desc, M)
+        if getattr(state, "joint_ws", None) is None or state.joint_ws.numel() < need:
+            state.joint_ws = torch.empty(max(need, 1), dtype=torch.uint8, device=X.device)
+        N.check(lib.cdx_gpis_joint(state.desc, N.ptr(X), M, N.ptr(cov), N.ptr(state.joint_ws), N.stream_ptr(X.device)),
+                "cdx_gpis_joint")
+    return cov
+
+
+def joint_prior(kernel, R, sigma):
+    """(k0, κ, κ, κ): the prior variances of the value and of the gradient's components (csrc/cdx_gpis.h)."""
+    R, inv_s2 = float(R), 1.0 / (float(sigma) * float(sigma))
+    k0, kappa = {"tps": (R ** 3, 6.0 * R), "rbf": (1.0, inv_s2),
+                 "joint": (0.3 + 0.7 * R ** 3, 0.3 * inv_s2 + 0.7 * 6.0 * R)}[kernel]
+    return (k0, kappa, kappa, kappa)
+
+
+def joint_cov_matrix(cov10):
+    """[…, 10] upper triangle → the symmetric […, 4, 4]."""
+    idx = torch.tensor(_FILL, dtype=torch.long, device=cov10.device)
+    return cov10[..., idx]
+
+
+def normal_covariance(grad, cov):
+    """The delta method for n̂ = g/‖g‖ at the mean gradient ``grad`` […, 3] with the joint covariance ``cov``
+    […, 4, 4] → NormalUncertainty.  Pure torch ops."""
+    norm = grad.norm(dim=-1, keepdim=True)
+    n = grad / norm
+    P = torch.eye(3, dtype=grad.dtype, device=grad.device) - n.unsqueeze(-1) * n.unsqueeze(-2)
+    cn = P @ cov[..., 1:, 1:] @ P / (norm * norm).unsqueeze(-1)
+    tr = cn.diagonal(dim1=-2, dim2=-1).sum(-1)
+    return NormalUncertainty(n, cn, tr.clamp(min=0.0).sqrt(), cov[..., 0, 0].clamp(min=0.0).sqrt() / norm.squeeze(-1))
+
+
+def joint_cholesky(cov, prior):
+    """The lower factor L […, 4, 4] of cov […, 4, 4], L·Lᵀ = cov, written out element by element (no batched LAPACK
+    call, nothing raises).  A pivot ≤ PIVOT_REL × its prior entry — a component the data determine, or an indefinite Σ
+    far from the data — zeroes its column: that component gets no noise of its own."""
+    L = [[None] * 4 for _ in range(4)]
+    zero = torch.zeros_like(cov[..., 0, 0])
+    for j in range(4):
+        d = cov[..., j, j]
+        for k in range(j):
+            d = d - L[j][k] * L[j][k]
+        ok = d > PIVOT_REL * prior[j]
+        root = torch.where(ok, d, torch.ones_like(d)).sqrt()
+        L[j][j] = torch.where(ok, root, zero)
+        for i in range(j + 1, 4):
+            v = cov[..., i, j]
+            for k in range(j):
+                v = v - L[i][k] * L[j][k]
+            L[i][j] = torch.where(ok, v / root, zero)
+        for i in range(j):
+            L[i][j] = zero
+    return torch.stack([torch.stack(row, -1) for row in L], -2)
+
+
+def _standard_normal(shape, device, generator):
+    """The sampler's noise: float64 standard normals on ``device`` (``generator``: a generator of that device)."""
+    return torch.randn(shape, dtype=torch.float64, device=device, generator=generator)
+
+
+def normals_from_samples(samples):
+    """Joint draws […, 4] → (unit normals […, 3], surface offsets […] = −f/‖g‖: where, along the drawn normal and to
+    first order, the drawn surface lies from the query)."""
+    g = samples[..., 1:]
+    norm = g.norm(dim=-1)
+    return g / norm.unsqueeze(-1), -samples[..., 0] / norm
 
 
 class _Pred(torch.autograd.Function):
@@ -414,6 +511,46 @@ class GPIS:
             weights.append(w.reshape(1))
         weights = torch.hstack(weights)
         return torch.stack(normals, dim=1), weights / weights.sum()
+
+    # ------------------------------------------------- joint posterior of (f, ∇f)
+    def pred_joint(self, X2):
+        """(mean4 […, 4], cov […, 4, 4]): the posterior of (f, ∂f/∂x, ∂f/∂y, ∂f/∂z) at X2 […, 3], a Gaussian per
+        query (queries are not correlated with each other here).  mean4 is (mean, ∇mean) of cdx_gpis_mean, cov the
+        symmetric fill of cdx_gpis_joint's 10 entries; cov[…, 0, 0] is the signed variance whose sqrt|·| ``pred``
+        returns.  Positive definite near the data; a TPS or joint state is indefinite farther than R from an inducing
+        point, and the matrix is returned as it is.  Detached: no autograd."""
+        _require_cuda(X2, "GPIS query")
+        lead = list(X2.shape[:-1])
+        X = X2.detach().reshape(-1, 3).to(torch.float64).contiguous()
+        st = self.native_state()
+        mean, gmean, _ = gpis_mean(st, X, want_grad=True)
+        cov = joint_cov_matrix(gpis_joint_cov(st, X))
+        return torch.cat([mean.unsqueeze(1), gmean], 1).view(lead + [4]), cov.view(lead + [4, 4])
+
+    def _joint_prior(self):
+        return joint_prior(self.kernel, float(self.R) if hasattr(self, "R") else 0.0, self.sigma)
+
+    def normal_uncertainty(self, X2):
+        """How well the surface normal and the surface's position are known at X2 […, 3] → NormalUncertainty (first
+        order in the gradient's posterior covariance; torch ops on ``pred_joint``)."""
+        mean4, cov = self.pred_joint(X2)
+        return normal_covariance(mean4[..., 1:], cov)
+
+    def sample_joint(self, X2, num_samples, generator=None):
+        """``num_samples`` draws of (f, ∇f) at every query of X2 […, 3] → […, S, 4]: mean4 + L·z with L the 4 × 4 factor
+        of ``joint_cholesky`` and z standard normal from ``generator`` (a generator of the queries' device).  Every query
+        is drawn on its own: the correlation between queries is not modelled."""
+        return self._draw_joint(*self.pred_joint(X2), num_samples, generator)
+
+    def _draw_joint(self, mean4, cov, num_samples, generator):
+        L = joint_cholesky(cov, self._joint_prior())
+        z = _standard_normal(list(mean4.shape[:-1]) + [int(num_samples), 4], mean4.device, generator)
+        return mean4.unsqueeze(-2) + (L.unsqueeze(-3) @ z.unsqueeze(-1)).squeeze(-1)
+
+    def sample_normals(self, X2, num_samples, generator=None):
+        """(unit normals […, S, 3], surface offsets […, S]) of ``sample_joint``'s draws (``normals_from_samples``);
+        with no noise a draw is the mean normal ∇mean/‖∇mean‖."""
+        return normals_from_samples(self.sample_joint(X2, num_samples, generator))
 
     def get_visualization_data(self, lb, ub, steps=100, fused=False):
         """Mean / std / normal on a steps³ grid (gpis.py:113-125).  ``fused=True`` evaluates the whole grid with

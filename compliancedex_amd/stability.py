@@ -39,6 +39,13 @@ PayloadResult.__doc__ = """payload [E]: the largest load magnitude tried at whic
 where it does not hold unloaded); upper [E]: the smallest magnitude tried at which it failed (``hi`` where none did:
 payload == hi then means "at least hi")."""
 
+ShapeUncertaintyReport = namedtuple("ShapeUncertaintyReport", ["hold_probability", "holds_mean", "angle_std",
+                                                               "offset_std", "mean", "samples"])
+ShapeUncertaintyReport.__doc__ = """Per grasp: hold_probability [E] float64, the fraction of the drawn sets of normals
+under which the grasp holds; holds_mean [E] bool, the verdict with the mean normals; angle_std [E, T] (rad) and
+offset_std [E, T] (m) of ``GPIS.normal_uncertainty`` at the contacts; ``mean``, the DisturbanceReport of the mean
+normals, and ``samples``, the one of the E·S drawn rows (row e·S + s)."""
+
 # Defaults of the verdict: a contact may not leave its friction cone (margin > 0) nor pull (normal force ≥ 0), and the
 # object may not move more than 2 cm or turn more than 2·asin(0.35/2) ≈ 20° — beyond that the fingertip springs of the
 # model are no longer the hand.
@@ -242,3 +249,48 @@ def max_payload(contact, target, compliance, normals, mu, directions=26, hi=20.0
         lo, up = torch.where(ok, mid, lo), torch.where(ok | at_hi, up, mid)
     nan = torch.full_like(lo, float("nan"))
     return PayloadResult(torch.where(at_zero, lo, nan), torch.where(at_zero, up, torch.zeros_like(up)))
+
+
+def shape_uncertainty_report(gpis, contact, target, compliance, mu, load_force, samples=64, generator=None,
+                             load_point=None, com=None, **kw):
+    """With which probability does a grasp hold under the loads of ``disturbance_report`` when the shape is only known
+    as the GPIS knows it → ShapeUncertaintyReport.
+
+    ``gpis``: the GPIS the contacts lie on; contact, target [E, T, 3] and compliance [E, T] as in ``disturbance_report``,
+    whose remaining arguments (load_point, com, tol, max_iters, lm, the limits) pass through.  ``samples`` sets of
+    normals are drawn per grasp, every contact's from the pointwise posterior of (f, ∇f) there
+    (``GPIS.sample_normals``, ``generator`` a generator of the contacts' device), and ``disturbance_report`` runs once on
+    the E·samples rows and once on the mean normals (``GPIS.compute_normal``).  hold_probability is the fraction of a
+    grasp's sets under which it holds.
+
+    Out of scope: the contacts are drawn independently of each other — the posterior's cross-covariance between two
+    contacts, which is large for neighbouring fingertips, is not modelled — and only the normals are drawn: the contact
+    positions stay where they are, although the surface's position is uncertain as well (``offset_std`` says by how
+    much).  It adds no kernel of its own and reads nothing back."""
+    from . import gpis as G
+    S = int(samples)
+    if S < 1:
+        raise ValueError("at least one sample")
+    if not isinstance(contact, torch.Tensor) or contact.ndim != 3 or contact.shape[2] != 3:
+        raise ValueError("contact must be a tensor of shape [E, T, 3]")
+    E, T = contact.shape[0], contact.shape[1]
+    pts = contact.detach().to(torch.float64)
+    mean4, cov = gpis.pred_joint(pts)
+    unc = G.normal_covariance(mean4[..., 1:], cov)
+    normals, _ = G.normals_from_samples(gpis._draw_joint(mean4, cov, S, generator))  # [E, T, S, 3]
+    rep_mean = disturbance_report(contact, target, compliance, gpis.compute_normal(pts), mu, load_force,
+                                  load_point=load_point, com=com, **kw)
+
+    def rows(x, per_grasp_ndim):
+        """A per-grasp argument repeated for the grasp's S rows; anything shared by the grasps as it is."""
+        if x is None:
+            return None
+        if isinstance(x, torch.Tensor) and x.ndim == per_grasp_ndim and x.shape[0] == E:
+            return x.repeat_interleave(S, 0)
+        x = torch.as_tensor(x, dtype=torch.float64, device=contact.device)
+        return x.repeat_interleave(S, 0) if x.ndim == per_grasp_ndim else x
+    rep = disturbance_report(rows(contact, 3), rows(target, 3), rows(compliance, 2),
+                             normals.permute(0, 2, 1, 3).reshape(E * S, T, 3), mu, rows(load_force, 3),
+                             load_point=rows(load_point, 3), com=rows(com, 2), **kw)
+    prob = rep.holds.view(E, S).to(torch.float64).mean(1)
+    return ShapeUncertaintyReport(prob, rep_mean.holds, unc.angle_std, unc.offset_std, rep_mean, rep)

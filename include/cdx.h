@@ -85,6 +85,20 @@ size_t cdx_gpis_std_workspace(const cdx_gpis* g, int64_t M);
 int cdx_gpis_std(const cdx_gpis* g, const double* X, int64_t M, double* std, double* grad_std,
                  void* workspace, cdx_stream_t stream);
 
+/* Workspace bytes cdx_gpis_joint needs for M queries (the partial sums of its column splits). */
+size_t cdx_gpis_joint_workspace(const cdx_gpis* g, int64_t M);
+
+/* Posterior covariance of (f, ∂f/∂x, ∂f/∂y, ∂f/∂z) at M query points, the 4-vector Gaussian whose mean
+ * cdx_gpis_mean gives (the reference has no such function; its compute_multinormals, gpis.py:89-111, samples normals
+ * from nested subsets of the inducing points instead): Σ = P0 − WᵀW with W = L^{-1}·[k, ∂ₓk, ∂ᵧk, ∂_z k] (fp64 MFMA,
+ * the four columns generated on chip) and the prior P0 = diag(k0, κ, κ, κ), κ = −k″(0).  Reads Linv_t, X1, N, N_pad,
+ * kernel, R, sigma.  X [M*3]; cov [M*10]: the upper triangle of Σ row-major — ff, fx, fy, fz, xx, xy, xz, yy, yz, zz —
+ * signed (Σ00 = the signed variance of cdx_gpis_std; far from the data the TPS form is indefinite).  A row's entries
+ * have the same bits whatever M and its neighbours; a query with a non-finite coordinate gives NaN in its own row.
+ * Return codes as cdx_gpis_std; M = 0 is a no-op; nothing is written on a refusal. */
+int cdx_gpis_joint(const cdx_gpis* g, const double* X, int64_t M, double* cov, void* workspace,
+                   cdx_stream_t stream);
+
 /* On-device fit.  Replaces GPIS.fit (gpis.py:33-40):
  *   R   = max_ij ‖X1_i − X1_j‖ for the TPS / joint kernels (device scalar; 0 for RBF),
  *   E11 = K(X1, X1) + diag(noise²)   [N*N] row-major; noise [N] per point (nullable = 0).
